@@ -21,10 +21,13 @@ starts the N ranks itself (torch.distributed.run); with a rendezvous of another 
 
 The headline runs WITH the loss bookkeeping (--loss 1): the instantiation ./word2bits runs (it prints "Epoch Loss").
 
-Prints ONE JSON line on rank 0 (contract in the task description) with extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed
+step) with extra objects:
   roofline     -- algorithmic HBM bytes per launch / hipEvent-measured launch duration vs 8 TB/s, min / median / max per
                   launch, and the HBM bytes of the calibrated rocprofv3 counters (quoted from profiles/r06_pmc_worker.json:
                   traffic_measured_in_this_run = false)
+A plain run does only what that line needs: set-up, --warmup steps, the --steps timed steps, the line.  Everything
+else it can measure runs only with --full (and there as selected by --cpu-baseline / --also-*):
   cpu_baseline -- the reference CPU program (oracle/_ref/word2bits_stock, built from the unmodified reference sources)
                   on all host threads, training phase of a whole epoch over a bounded corpus of the same shape;
                   cpu_baseline_1thread (the same with -threads 1, a 20 s sample), cpu_baseline_configs0 (BASELINE
@@ -34,6 +37,14 @@ Prints ONE JSON line on rank 0 (contract in the task description) with extra obj
                   plain kernel beside it; partial_device = the headline shape on a 22 M-token stream; the explicit
                   sentence-resident kernel), e2e (./word2bits end to end, measured in this run; the reference's side quoted
                   from profiles/), us_per_word_per_worker
+  (--form eval: two_rounding_mode, answers_differ_between_modes and the reference evaluator's cpu_baseline)
+
+--dump-outputs DIR writes, after the timed steps, outputs that are the same in every run of the same command to
+DIR/<name>.npy (float32 / float64), so that two builds can be compared output for output.  Worker form: the timed
+trainer's [words done, alpha], and a race-free replay of the timed path's training kernel (one worker, same
+configuration and stream): a fixed sample of its trained u / v rows and its loss (dump_outputs says why the timed
+trainer's own rows are not written: they vary between runs under Hogwild).  --form eval: answers, scores.  The tuples
+form refuses the option.
 """
 import argparse
 import json
@@ -122,7 +133,76 @@ def parse():
     ap.add_argument("--eval-questions", type=int, default=19544, help="--form eval: questions (questions-words.txt)")
     ap.add_argument("--eval-kind", choices=["1bit", "fp"], default="1bit")
     ap.add_argument("--eval-cpu-questions", type=int, default=24)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline line does not need: CPU baselines, the other legs and shapes, the "
+                         "end-to-end run (--form eval: the two-rounding mode and the reference evaluator)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.form == "tuples":
+        ap.error("--dump-outputs: the worker form and --form eval only (the tuples form's rows differ from run to run)")
+    return args
+
+
+def host_cores():
+    """host CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets one (a
+    share of a larger machine shows all of the machine's CPUs in os.cpu_count())"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "0")) or n)
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+def dump_rows(V, D):
+    """the fixed sample of model rows --dump-outputs writes: the most frequent quarter of it plus a seeded draw of the
+    other rows, at most 4096 rows and 16 MB per table"""
+    n = min(V, 4096, max(1, (16 << 20) // (4 * D)))
+    hot = n // 4
+    rng = np.random.default_rng(12345)
+    return np.sort(np.concatenate([np.arange(hot), hot + rng.choice(V - hot, n - hot, replace=False)]))
+
+
+def model_rows(tr, rows):
+    """rows of u and v as the trainer holds them (what w2b_get_model returns for those rows), gathered on the device"""
+    import torch
+    V, D = tr.vocab_size, tr.layer1_size
+    out = []
+    for ptr in tr.model_device_ptrs():
+        m = tr.device_tensor(ptr, V * D).view(V, D)
+        out.append(m.index_select(0, torch.from_numpy(rows).to(m.device)).cpu().numpy().astype(np.float32))
+    return out
+
+
+def dump_outputs(path, t, replay):
+    """--dump-outputs, worker form.  The timed trainer's Hogwild workers race on shared rows (as the reference's threads
+    do): its trained rows and its loss sum differ from run to run, by far more than rounding, so they cannot be compared
+    output for output.  What is written instead:
+      epoch_state.npy            timed trainer after the last timed step: [words done, alpha] (independent of how the
+                                 workers interleave)
+      replay_u_rows.npy,         the same training code, configuration and token stream with ONE worker from InitNet
+      replay_v_rows.npy,         (REPLAY_STEPS launches of REPLAY_POSITIONS positions): no races, so the trained rows
+      replay_state.npy           (dump_rows() sample) and [words done, alpha, loss sum] are the same bits in every run and
+                                 change with any change to the kernel's arithmetic"""
+    os.makedirs(path, exist_ok=True)
+    _, wca, alpha, _ = t.epoch_status(want_loss=False)
+    np.save(os.path.join(path, "epoch_state.npy"), np.array([wca, alpha], np.float64))
+    tr = replay()
+    for _ in range(REPLAY_STEPS):
+        tr.train_step(REPLAY_POSITIONS)
+    tr.synchronize()
+    u, v = model_rows(tr, dump_rows(tr.vocab_size, tr.layer1_size))
+    _, wca, alpha, loss = tr.epoch_status(want_loss=True)
+    tr.close()
+    np.save(os.path.join(path, "replay_u_rows.npy"), u)
+    np.save(os.path.join(path, "replay_v_rows.npy"), v)
+    np.save(os.path.join(path, "replay_state.npy"), np.array([wca, alpha, loss], np.float64))
+
+
+REPLAY_STEPS, REPLAY_POSITIONS = 2, 4096
 
 
 def latest_profile(name):
@@ -275,7 +355,7 @@ def cpu_baseline_reference(args, path):
     """the headline shape on ALL host threads, training phase of a whole epoch over the bounded corpus"""
     if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "word2bits_stock")):
         return None
-    cores = os.cpu_count() or 1
+    cores = host_cores()
     r = RefProbe(path, ref_flags(args), cores).result()
     if not r:
         return None
@@ -327,7 +407,7 @@ def cpu_baseline_port(args):
     ids[999::1000] = 0
     cn = np.bincount(ids, minlength=V).astype(np.int64)
     cn[cn == 0] = 1
-    cores = os.cpu_count() or 1
+    cores = host_cores()
     o = OracleState(cn, D, window=args.window, negative=args.negative, bitlevel=args.bitlevel,
                     num_threads=cores, iters=1, sample=0.0, table_size=100_000_000, compute_loss=0)
     starts = (np.arange(cores, dtype=np.int64) * (n // cores))
@@ -359,15 +439,15 @@ def run_eval_form(args):
     path = write_vectors_file(os.path.join(tempfile.mkdtemp(), "v.bin"), [("w%d" % i).encode() for i in range(V)], M)
     b = rng.integers(0, V, (3, Q)).astype(np.int32)
     peak = {True: 78.6e12, False: 39.3e12}    # multiply-adds/s: 256 CU x 4 SIMD x 64 flop/clk x 2.4 GHz / 2 (fused), /4
-    modes, answers = {}, {}
-    for fused in (True, False):
+    modes, answers, scores = {}, {}, {}
+    for fused in ((True, False) if args.full else (True,)):
         ev = w2b.Evaluator(path, 0, 0, fused=fused)
         for _ in range(warmup):
             ev.top1(*b)
         ev.timing()
         t0 = time.perf_counter()
         for _ in range(steps):
-            answers[fused], _ = ev.top1(*b)
+            answers[fused], scores[fused] = ev.top1(*b)
         wall = (time.perf_counter() - t0) / steps
         ms, launches, macs = ev.timing()
         rate = macs / (ms * 1e-3)
@@ -384,12 +464,17 @@ def run_eval_form(args):
                                "reference's stock (FMA) build" % (Q, V, D, args.eval_kind)},
         "roofline": {"bound": "mfma", "achieved": f["achieved"], "peak": f["peak"], "unit": "TFLOP/s",
                      "frac": f["frac"], "traffic": None, "kernel": "k_eval_scores_mfma", "avg_launch_ms": f["kernel_ms"]},
-        "two_rounding_mode": {"kernel": "k_eval_scores<false> (packed fp32 VALU)", **modes[False]},
-        "answers_differ_between_modes": int((answers[True] != answers[False]).sum()),
     }
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "answers.npy"), answers[True].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), scores[True].astype(np.float32))
+    if args.full:
+        result["two_rounding_mode"] = {"kernel": "k_eval_scores<false> (packed fp32 VALU)", **modes[False]}
+        result["answers_differ_between_modes"] = int((answers[True] != answers[False]).sum())
     exe = ref_binary("compute_accuracy")
     n = args.eval_cpu_questions
-    if exe and n > 0 and args.cpu_baseline != "none":
+    if args.full and exe and n > 0 and args.cpu_baseline != "none":
         qs = ": s\n" + "".join("w%d w%d w%d w%d\n" % (b[0, i], b[1, i], b[2, i], b[2, i]) for i in range(n))
         t0 = time.perf_counter()
         subprocess.run([exe, path, "0", "0"], input=b"", capture_output=True)
@@ -863,6 +948,18 @@ def main():
             # host-driven collective (torch.distributed) the host waits for every chunk
             "overlapped": torch_sync is None,
             "chunk_bytes": min(8 * V * D, 256 << 20)}
+    if args.dump_outputs and rank == 0:
+        def replay():
+            tr = w2b.Trainer(V, D, W, K, args.bitlevel, num_threads=1, iter=1, alpha=0.05, sample=0.0, reg=0.0,
+                             train_words=train_words * world, compute_loss=True, device=local_rank,
+                             relaxed_coherence=bool(args.relaxed), window_cache=wcache, row_groups=rgroups, **tune)
+            tr.init_net()
+            tr.set_vocab_counts(counts, 100_000_000)
+            tr.set_corpus_device(stream.data_ptr(), per_rank_tokens)
+            tr.set_shards(np.zeros(1, np.int64))
+            tr.epoch_begin()
+            return tr
+        dump_outputs(args.dump_outputs, t, replay)
     t.close()
 
     def timed_leg(tr, wps):
@@ -883,7 +980,7 @@ def main():
                 "roofline_frac": wps * bpw / ((rms / 1e3) / max(1, rl)) / HBM_PEAK}
 
     ref1 = cpu_path = None
-    if rank == 0 and world == 1 and args.cpu_baseline == "reference" and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "word2bits_stock")):
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "reference" and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "word2bits_stock")):
         # the CPU legs use one bounded corpus; the ONE-thread run of the reference (BASELINE.md section 4 asks for -threads 1
         # and -threads $(nproc)) starts now and runs on one host core next to the GPU legs below; the all-threads run and
         # the configs[0] run follow when the GPU is done, alone on the host
@@ -892,7 +989,7 @@ def main():
             ref1 = RefProbe(cpu_path, ref_flags(args), 1, sample_seconds=args.cpu_1thread_seconds)
         except Exception:
             ref1 = None
-    if world == 1 and args.also_legs and args.form == "worker" and not args.relaxed:
+    if args.full and world == 1 and args.also_legs and args.form == "worker" and not args.relaxed:
         # the other instantiation of the same kernel: ./word2bits always books the loss (it prints "Epoch Loss", ref :539),
         # so the headline does too; a host that does not want the number can switch it off (compute_loss = 0)
         leg = timed_leg(make_trainer(False, loss=not args.loss), words_per_step)
@@ -902,7 +999,7 @@ def main():
             leg = timed_leg(make_trainer(False, bitlevel=2), words_per_step)
             leg["note"] = "same steps at bitlevel 2 (BASELINE configs[2] quantizer)"
             result["bitlevel2"] = leg
-    if world == 1 and args.also_relaxed and not args.relaxed:
+    if args.full and world == 1 and args.also_relaxed and not args.relaxed:
         # same steps, same data, relaxed row coherence -- reported beside the headline
         if args.form == "worker":          # relaxed rows run the plain worker kernel with its own residency
             probe = w2b.Trainer(2, D, W, K, args.bitlevel, num_threads=1, device=local_rank, relaxed_coherence=True,
@@ -929,12 +1026,12 @@ def main():
             "roofline_frac": words_per_step * bpw / ((rms / 1e3) / max(1, rl)) / HBM_PEAK,
             "note": "plain cached row accesses: hot rows are private per XCD L2 within a launch (not the default)"}
         t2.close()
-    if (world == 1 and args.also_shapes and workload_name(args) == "BASELINE configs[1]" and args.form == "worker"
+    if (args.full and world == 1 and args.also_shapes and workload_name(args) == "BASELINE configs[1]" and args.form == "worker"
             and not args.relaxed and args.loss and not tune):
         result["other_shapes"] = other_shapes()
     if rank == 0:
         cb = None
-        if world == 1 and args.cpu_baseline != "none":
+        if args.full and world == 1 and args.cpu_baseline != "none":
             try:
                 if ref1 is not None:
                     r1 = ref1.result()
@@ -949,7 +1046,7 @@ def main():
                 if args.cpu_baseline == "reference" and args.cpu_cfg0:
                     result["cpu_baseline_configs0"] = cpu_baseline_cfg0()
             except Exception as e:            # the GPU number must still be reported
-                cb = {"value": None, "unit": "words/s", "cores": os.cpu_count(), "kind": "port",
+                cb = {"value": None, "unit": "words/s", "cores": host_cores(), "kind": "port",
                       "sample": "failed: %r" % (e,)}
             finally:
                 if cpu_path:
@@ -961,7 +1058,7 @@ def main():
         result["cpu_baseline"] = cb
         # end-to-end wall times of ./word2bits and the reference program on one file (tools/e2e_compare.py): the GPU side
         # (3 s) is measured in THIS run; the reference side (167 s on 256 host threads) is quoted from the committed file
-        if world == 1 and workload_name(args).startswith("BASELINE configs[1]") and args.also_shapes:
+        if args.full and world == 1 and workload_name(args).startswith("BASELINE configs[1]") and args.also_shapes:
             try:
                 quoted = json.load(open(latest_profile("e2e.json")))
                 tmp = os.path.join("/tmp", "w2b_e2e_%d.json" % os.getpid())

@@ -59,7 +59,7 @@ def test_cpu_legs_of_bench_read_the_reference_programs_stdout():
     path = bench.write_cpu_corpus(a)
     try:
         whole = bench.cpu_baseline_reference(a, path)
-        assert whole["kind"] == "reference" and whole["cores"] == (os.cpu_count() or 1) and whole["value"] > 1000
+        assert whole["kind"] == "reference" and whole["cores"] == bench.host_cores() and whole["value"] > 1000
         assert "424995 tokens" in whole["sample"] or "tokens =" in whole["sample"]
         r = bench.RefProbe(path, bench.ref_flags(a), 1, sample_seconds=4.0).result()
         assert r and 1000 < r["words_per_s"] < 5e6
@@ -67,3 +67,20 @@ def test_cpu_legs_of_bench_read_the_reference_programs_stdout():
     finally:
         os.remove(path)
         os.rmdir(os.path.dirname(path))
+
+
+def test_host_cores_is_the_share_this_process_may_use(monkeypatch):
+    """the CPU legs size their thread count by bench.host_cores(): the affinity mask, capped by OMP_NUM_THREADS"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    allowed = len(os.sched_getaffinity(0))
+    monkeypatch.delenv("OMP_NUM_THREADS", raising=False)
+    assert bench.host_cores() == allowed
+    monkeypatch.setenv("OMP_NUM_THREADS", "1")
+    assert bench.host_cores() == 1
+    monkeypatch.setenv("OMP_NUM_THREADS", str(allowed + 7))
+    assert bench.host_cores() == allowed
+    monkeypatch.setenv("OMP_NUM_THREADS", "not a number")
+    assert bench.host_cores() == allowed

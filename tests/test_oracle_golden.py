@@ -1,7 +1,8 @@
 """not gpu: pins the CPU oracle (oracle/w2b_oracle.c) against
   (1) committed golden output files produced by the UNMODIFIED reference program
       (tests/golden/*.vec, generator tests/golden/make_golden.py), byte for byte;
-  (2) the reference binary itself where oracle/_ref/ exists (built from /root/reference);
+  (2) the reference binary itself on generated corpora: live where oracle/_ref/ is built, else what it wrote there
+      before (sha256 in tests/golden/live_reference.json);
   (3) the known answers printed in the reference's README (README.md:12-17,122-131).
 """
 import ctypes as C
@@ -11,10 +12,27 @@ import os
 import numpy as np
 import pytest
 
-from w2b_testlib import GOLDEN, oracle, ref_binary, run_ref, write_corpus, read_vectors
+from w2b_testlib import GOLDEN, oracle, ref_binary, reference_sha, run_ref, sha256, write_corpus, read_vectors
 
 META = json.load(open(os.path.join(GOLDEN, "golden.json")))
 CORPUS = os.path.join(GOLDEN, "corpus_small.txt")
+
+
+def live_reference_sha(key, name, corpus, flags, threads=1, runs=1):
+    """sha256 of the reference's output file on this corpus: the live binary where it is built (run `runs` times,
+    every run byte-identical), else its recording"""
+    def produce():
+        if ref_binary(name) is None:
+            return None
+        outs = []
+        for rep in range(runs):
+            o = corpus + ".r%d.vec" % rep
+            run_ref(name, corpus, o, threads=threads, **flags)
+            outs.append(open(o, "rb").read())
+        assert all(o == outs[0] for o in outs)
+        return outs[0]
+    inputs = open(corpus, "rb").read() + repr((name, threads, sorted(flags.items()))).encode()
+    return reference_sha(key, inputs, produce)
 
 
 def run_oracle(train, out, flags, threads=1):
@@ -50,7 +68,6 @@ def test_oracle_vocab_matches_reference_counts():
         L.w2bo_vocab_free(vb)
 
 
-@pytest.mark.skipif(ref_binary("word2bits_nofma") is None, reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("flags", [
     dict(bitlevel=1, size=20, window=8, negative=24, iter=2, min_count=5, binary=1),
     dict(bitlevel=2, size=24, window=5, negative=5, iter=1, min_count=2, binary=1, sample=1e-2),
@@ -58,10 +75,10 @@ def test_oracle_vocab_matches_reference_counts():
 ])
 def test_oracle_vs_live_reference_binary(flags, tmp_path):
     corpus = write_corpus(str(tmp_path / "c.txt"), seed=3, vocab=200, n_tokens=12000)
-    ref_out, ora_out = str(tmp_path / "r.vec"), str(tmp_path / "o.vec")
-    run_ref("word2bits_nofma", corpus, ref_out, threads=1, **flags)
+    ora_out = str(tmp_path / "o.vec")
+    want = live_reference_sha("oracle_vs_live[bitlevel%d]" % flags["bitlevel"], "word2bits_nofma", corpus, flags)
     run_oracle(corpus, ora_out, flags)
-    assert open(ref_out, "rb").read() == open(ora_out, "rb").read()
+    assert sha256(open(ora_out, "rb").read()) == want
 
 
 def test_quantize_truth_table():
@@ -106,7 +123,6 @@ def test_init_net_is_the_readme_pattern():
     assert np.abs(flat).max() <= 0.5
 
 
-@pytest.mark.skipif(ref_binary("word2bits_nofma") is None, reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("seed", range(16))
 def test_oracle_vs_live_reference_random_flags(seed, tmp_path):
     """a seeded sweep over the flag space (all bitlevels incl. 3, -size 1..40, -window 1..10, -negative 0..12,
@@ -121,13 +137,12 @@ def test_oracle_vs_live_reference_random_flags(seed, tmp_path):
     corpus = write_corpus(str(tmp_path / "c.txt"), seed=seed, vocab=int(rng.integers(20, 400)),
                           n_tokens=int(rng.integers(2000, 9000)), line_len=int(rng.integers(3, 60)),
                           quirks=bool(rng.integers(0, 2)))
-    ref_out, ora_out = str(tmp_path / "r.vec"), str(tmp_path / "o.vec")
-    run_ref("word2bits_nofma", corpus, ref_out, threads=1, **flags)
+    ora_out = str(tmp_path / "o.vec")
+    want = live_reference_sha("random_flags[%d]" % seed, "word2bits_nofma", corpus, flags)
     run_oracle(corpus, ora_out, flags)
-    assert open(ref_out, "rb").read() == open(ora_out, "rb").read(), flags
+    assert sha256(open(ora_out, "rb").read()) == want, flags
 
 
-@pytest.mark.skipif(ref_binary("word2bits_nofma") is None, reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("threads,prefix,flags", [
     (4, b"", dict(bitlevel=1, size=12, window=5, iter=1, sample=0.0)),
     (4, b"", dict(bitlevel=0, size=9, window=3, iter=2, sample=1e-2)),
@@ -142,12 +157,9 @@ def test_multi_thread_shard_logic_vs_live_reference(threads, prefix, flags, tmp_
     corpus = write_disjoint_shard_corpus(str(tmp_path / "c.txt"), n_shards=threads, seed=threads, prefix=prefix)
     f = dict(negative=0, min_count=1, binary=1)
     f.update(flags)
-    outs = []
-    for rep in range(2):                                   # the reference really is deterministic here
-        o = str(tmp_path / ("r%d.vec" % rep))
-        run_ref("word2bits_nofma", corpus, o, threads=threads, **f)
-        outs.append(open(o, "rb").read())
-    assert outs[0] == outs[1]
+    # (two live runs: the reference really is deterministic here)
+    want = live_reference_sha("multi_thread[%d-bitlevel%d]" % (threads, flags["bitlevel"]),
+                              "word2bits_nofma", corpus, f, threads=threads, runs=2)
     ora = str(tmp_path / "o.vec")
     run_oracle(corpus, ora, f, threads=threads)
-    assert open(ora, "rb").read() == outs[0]
+    assert sha256(open(ora, "rb").read()) == want

@@ -8,7 +8,8 @@ generated from integers is committed as tests/golden/reduce_vocab.json (generato
   (1) the oracle's restatement (w2bo_vocab_learn_ex / w2bo_run_ex) reproduces the fixture: vocabulary size, word count,
       vocabulary order, and the sha256 of the complete output file of a training run -- i.e. every count, since the
       unigram table and the sub-sampling are built from them;
-  (2) the same against the live binary on other corpora, where oracle/_ref exists;
+  (2) the same against the binary on other corpora: live where oracle/_ref exists, else its recorded output
+      (tests/golden/live_reference.json);
   (3) the product's ingest (w2b_corpus_load_ex: parallel tokeniser + sequential replay) equals the oracle: words,
       counts, token stream, shard starts -- also when the file is cut into many pieces.
 """
@@ -21,7 +22,7 @@ import numpy as np
 import pytest
 
 import word2bits_amd as w2b
-from w2b_testlib import GOLDEN, oracle, ref_binary, run_ref, write_reduce_vocab_corpus
+from w2b_testlib import GOLDEN, oracle, ref_binary, reference_sha, run_ref, sha256, write_reduce_vocab_corpus
 
 META = json.load(open(os.path.join(GOLDEN, "reduce_vocab.json")))
 HASH = 3000
@@ -75,15 +76,21 @@ def test_oracle_reproduces_the_reference_with_a_small_hash_table(kind, tmp_path)
         assert words[0] != "</s>" and "</s>" in words[1:]
 
 
-@pytest.mark.skipif(ref_binary("word2bits_nofma_hash3000") is None, reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("kind,seed", [("zipf", 1), ("wipe", 2), ("zipf", 3)])
 def test_oracle_vs_live_reference_with_a_small_hash_table(kind, seed, tmp_path):
     corpus = write_reduce_vocab_corpus(str(tmp_path / "c.txt"), kind, seed=seed)
     flags = dict(bitlevel=1, size=6, window=4, negative=3, iter=1, min_count=2, binary=1)
     ref_out, ora_out = str(tmp_path / "r.vec"), str(tmp_path / "o.vec")
-    run_ref("word2bits_nofma_hash3000", corpus, ref_out, threads=1, **flags)
+
+    def produce():                        # the live binary where it is built, else its recording
+        if ref_binary("word2bits_nofma_hash3000") is None:
+            return None
+        run_ref("word2bits_nofma_hash3000", corpus, ref_out, threads=1, **flags)
+        return open(ref_out, "rb").read()
+    inputs = open(corpus, "rb").read() + repr(("word2bits_nofma_hash3000", sorted(flags.items()))).encode()
+    want = reference_sha("small_hash_table[%s-%d]" % (kind, seed), inputs, produce)
     oracle_run(corpus, ora_out, flags)
-    assert open(ref_out, "rb").read() == open(ora_out, "rb").read()
+    assert sha256(open(ora_out, "rb").read()) == want
 
 
 @pytest.mark.parametrize("host_split", [None, (7, 1), (64, 64)])

@@ -205,6 +205,39 @@ def ref_binary(name):
     return p if os.path.exists(p) else None
 
 
+LIVE_REF_JSON = os.path.join(GOLDEN, "live_reference.json")
+
+
+def sha256(data):
+    import hashlib
+    return hashlib.sha256(data).hexdigest()
+
+
+def reference_sha(key, inputs, produce):
+    """sha256 of what the unmodified reference program writes for one test case.
+
+    `inputs` are the bytes that determine the case (files, flags, stdin); `produce()` runs the live binary and returns
+    its output bytes, or None where oracle/_ref/ is not built.  Live runs are checked against the recording in
+    tests/golden/live_reference.json (W2B_RECORD_LIVE_REF=1 rewrites it from them); without the binary the recording
+    stands in, for exactly the inputs it was made from."""
+    import json
+    rec = json.load(open(LIVE_REF_JSON)) if os.path.exists(LIVE_REF_JSON) else {}
+    live = produce()
+    if live is not None:
+        entry = {"inputs": sha256(inputs), "output": sha256(live)}
+        if os.environ.get("W2B_RECORD_LIVE_REF") == "1":
+            rec[key] = entry
+            with open(LIVE_REF_JSON, "w") as f:
+                json.dump(rec, f, indent=0, sort_keys=True)
+                f.write("\n")
+        elif rec.get(key, {}).get("inputs") == entry["inputs"]:
+            assert rec[key]["output"] == entry["output"], "live reference differs from its recording: %s" % key
+        return entry["output"]
+    assert key in rec, "no recorded reference output for %s (oracle/_ref/ not built here)" % key
+    assert rec[key]["inputs"] == sha256(inputs), "inputs of %s differ from the recorded ones" % key
+    return rec[key]["output"]
+
+
 def run_ref(name, train, output, **kw):
     """Run oracle/_ref/<name> with word2bits flags; returns stdout."""
     exe = ref_binary(name)

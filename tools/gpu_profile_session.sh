@@ -7,7 +7,7 @@ OUT=gpurun_out/${RND}_profile
 mkdir -p $OUT
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-echo "== bench default"; timeout 1200 python bench.py > $OUT/bench_default.log 2>$OUT/bench_default.err; tail -1 $OUT/bench_default.log | cut -c1-600
+echo "== bench default"; timeout -k 10 1200 python bench.py --full > $OUT/bench_default.log 2>$OUT/bench_default.err; tail -1 $OUT/bench_default.log | cut -c1-600
 form=worker
 K=$(tail -1 $OUT/bench_default.log | python -c "import json,sys; print(json.loads(sys.stdin.read())['roofline']['kernel'])")
 echo "kernel of the default workload: $K"
@@ -32,11 +32,11 @@ pmc cfg5 k_train_resident --vocab 3700000 --dim 1000 --negative 12
 pmc tuples k_train_tuples --form tuples
 pmc d200 k_train_ --vocab 60238 --dim 200
 echo "== evaluator"
-timeout 300 python bench.py --form eval --steps 5 --warmup 1 2>/dev/null | tail -1 > $OUT/eval_bench.json; cut -c1-300 $OUT/eval_bench.json
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_eval -o $RND -- python $R/bench.py --form eval --steps 5 --warmup 1 --eval-cpu-questions 0 > /dev/null 2>&1)
+timeout -k 10 300 python bench.py --form eval --steps 5 --warmup 1 --full 2>/dev/null | tail -1 > $OUT/eval_bench.json; cut -c1-300 $OUT/eval_bench.json
+(cd "$(mktemp -d)" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_eval -o $RND -- python $R/bench.py --form eval --steps 5 --warmup 1 --full --eval-cpu-questions 0 > /dev/null 2>&1)
 head -3 $OUT/prof_eval/${RND}_kernel_stats.csv | cut -c1-200
 echo "== tuples form (coherent rows)"
-timeout 300 python bench.py --form tuples --cpu-baseline none --also-shapes 0 2>/dev/null | tail -1 > $OUT/bench_tuples.json; cut -c1-300 $OUT/bench_tuples.json
+timeout -k 10 300 python bench.py --form tuples --full --cpu-baseline none --also-shapes 0 2>/dev/null | tail -1 > $OUT/bench_tuples.json; cut -c1-300 $OUT/bench_tuples.json
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_stats_tuples -o $RND -- python $R/bench.py --form tuples --steps 8 --warmup 2 --cpu-baseline none --also-relaxed 0 --also-shapes 0 > /dev/null 2>&1)
 head -3 $OUT/prof_stats_tuples/${RND}_kernel_stats.csv | cut -c1-250
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*counter_collection.csv" -delete; find $OUT -name "*.db" -delete

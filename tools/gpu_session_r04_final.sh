@@ -16,7 +16,7 @@ fi
 echo "== (5a) end to end: ./word2bits"
 timeout 600 python tools/e2e_compare.py $OUT/e2e.json --only hip 2>&1 | tail -1 | cut -c1-400
 echo "== (2) bench (the driver's command)"
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2>$OUT/bench_default.err
+timeout -k 10 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.log 2>$OUT/bench_default.err
 tail -1 $OUT/bench_default.log | cut -c1-1200
 echo "== (5b) end to end: the reference program on the host cores (background)"
 (timeout 1500 python tools/e2e_compare.py $OUT/e2e.json --only ref > $OUT/e2e_ref.log 2>&1; echo e2e-ref done) &
@@ -36,8 +36,8 @@ python tools/pmc_summary.py $OUT/prof_FETCH_SIZE/${RND}_counter_collection.csv $
 echo "== (4) cache-resident bound (row_probe small)"
 timeout 120 tools/row_probe small 2>&1 | tee $OUT/row_probe_small.txt
 echo "== (6) evaluator"
-timeout 300 python bench.py --form eval --steps 5 --warmup 1 2>/dev/null | tail -1 > $OUT/eval_bench.json; cut -c1-300 $OUT/eval_bench.json
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_eval -o $RND -- python $R/bench.py --form eval --steps 5 --warmup 1 --eval-cpu-questions 0 > /dev/null 2>&1)
+timeout -k 10 300 python bench.py --form eval --steps 5 --warmup 1 --full 2>/dev/null | tail -1 > $OUT/eval_bench.json; cut -c1-300 $OUT/eval_bench.json
+(cd "$(mktemp -d)" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_eval -o $RND -- python $R/bench.py --form eval --steps 5 --warmup 1 --full --eval-cpu-questions 0 > /dev/null 2>&1)
 head -3 $OUT/prof_eval/${RND}_kernel_stats.csv | cut -c1-200
 echo "== kernel stats of the other shapes (plain = automatic; sentence-resident = explicit)"
 S="--steps 8 --warmup 2 --tokens 30000000 --cpu-baseline none --also-relaxed 0 --also-legs 0 --also-shapes 0"

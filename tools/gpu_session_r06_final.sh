@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 echo "== (1) bench (the driver's command)"
 T0=$(date +%s)
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2>$OUT/bench_default.err
+timeout -k 10 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.log 2>$OUT/bench_default.err
 echo "bench wall: $(( $(date +%s) - T0 )) s"
 tail -1 $OUT/bench_default.log | cut -c1-1200
 K=$(tail -1 $OUT/bench_default.log | python -c "import json,sys; print(json.loads(sys.stdin.read())['roofline']['kernel'])")
@@ -41,8 +41,8 @@ echo "== (4) counters: the row-group kernel's short-row legs"
 pmc d200 k_train_groups --tokens 30000000 --vocab 60238 --dim 200
 pmc d400b2 k_train_groups --tokens 30000000 --vocab 60238 --dim 400 --bitlevel 2
 echo "== (5) evaluator"
-timeout 300 python bench.py --form eval --steps 5 --warmup 1 2>/dev/null | tail -1 > $OUT/eval_bench.json; cut -c1-300 $OUT/eval_bench.json
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_eval -o $RND -- python $R/bench.py --form eval --steps 5 --warmup 1 --eval-cpu-questions 0 > /dev/null 2>&1)
+timeout -k 10 300 python bench.py --form eval --steps 5 --warmup 1 --full 2>/dev/null | tail -1 > $OUT/eval_bench.json; cut -c1-300 $OUT/eval_bench.json
+(cd "$(mktemp -d)" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_eval -o $RND -- python $R/bench.py --form eval --steps 5 --warmup 1 --full --eval-cpu-questions 0 > /dev/null 2>&1)
 head -3 $OUT/prof_eval/${RND}_kernel_stats.csv | cut -c1-200
 echo "== (6) smoke"
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2

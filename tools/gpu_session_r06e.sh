@@ -34,7 +34,7 @@ rm -f /tmp/cfg1_100m.txt /tmp/headline.txt
 echo "== (3) fidelity tests that changed / are new"
 timeout 1800 python -m pytest tests/test_gpu_fidelity.py -q -m gpu -s -k "literally or second_held_out or long_streams" 2>&1 | grep -E "FIDELITY|passed|failed|Error|assert" | cut -c1-400 | tee $OUT/pytest_fidelity_new.txt
 echo "== (4) bench (the driver's command)"
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2>$OUT/bench_default.err
+timeout -k 10 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.log 2>$OUT/bench_default.err
 tail -1 $OUT/bench_default.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']

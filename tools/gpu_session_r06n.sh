@@ -25,5 +25,5 @@ PY
 done
 rm -f /tmp/cfg1_100m.txt
 timeout 2400 python -m pytest tests -q -m gpu -s 2>&1 | grep -E "FIDELITY|EXCHANGE|passed|failed|FAILED|Error" | cut -c1-300 | tee $OUT/pytest_gpu.txt
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2>/dev/null; tail -1 $OUT/bench_default.log | cut -c1-400
+timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.log 2>/dev/null; tail -1 $OUT/bench_default.log | cut -c1-400
 echo "== done"
