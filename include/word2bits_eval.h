@@ -58,6 +58,29 @@ int w2b_eval_get_matrix(w2b_eval *e, float *out);
 int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                   int32_t *best, float *bestd);
 
+/* ref :155-177 with N = k (the reference ships N = 1): per question the k best rows in the reference's order -- score
+ * descending, equal scores in ascending row order (the strict-greater insertion of ref :167) -- among the rows other
+ * than b1, b2, b3 whose score is > 0.  best[q*k + j], bestd[q*k + j], j = 0..k-1; a list of fewer than k rows ends in
+ * row -1 / score 0 (ref :164-165).  bestd may be NULL.  Scores are the bits w2b_eval_top1 produces, and k = 1 returns
+ * exactly what w2b_eval_top1 returns.  1 <= k <= W2B_EVAL_MAX_K, else W2B_EINVAL. */
+#define W2B_EVAL_MAX_K 64
+int w2b_eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t k,
+                  int32_t *best, float *bestd);
+/* The neighbours of a word: vec = M[row], only `row` is skipped.  Equals w2b_eval_topk(b1 = b2 = b3 = rows). */
+int w2b_eval_neighbors(w2b_eval *e, int64_t nq, const int32_t *rows, int32_t k, int32_t *best, float *bestd);
+/* Upper bound in bytes for the device scratch (candidate slots) of one top-k launch; 0 = the default, 1 GiB.  The
+ * questions are scored in chunks that fit, never smaller than 128 questions.  Results never depend on it. */
+int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes);
+
+/* The text form of ./nearest.  Every line of `queries[0..len)` is split on white space and upper-cased (C locale):
+ *   one word W        the neighbours of W                    three words A B C    the analogy (B - A) + C
+ * and answered by "<words joined by one space>:\n" followed by one line "<rank>\t<word>\t<score %.6f>\n" per result
+ * (rank from 1; a short list simply ends).  Empty lines are skipped; any other number of words gives
+ * "<words>: expected 1 or 3 words\n", a word that w2b_eval_lookup does not find "<words>: not in vocabulary: <WORD>\n"
+ * (the first such word).  All lines are scored in one w2b_eval_topk batch.  *out is malloc'ed; release it with
+ * w2b_eval_free_text. */
+int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out, int64_t *out_len);
+
 /* ref :94,113-188: the program's stdout for the question stream `questions[0..len)` (what the reference reads
  * from stdin with scanf("%s")), including "Starting eval...".  *out is malloc'ed; release it with
  * w2b_eval_free_text. */
@@ -69,8 +92,8 @@ void w2b_eval_free_text(char *text);
  * The two-rounding mode always runs on the vector ALU.  (Round 2 read this from the environment.) */
 int w2b_eval_set_kernel(w2b_eval *e, int32_t variant);
 
-/* Device time (HIP events on the evaluator's stream) and launch count of the score kernel since load or since
- * the last call; `macs` = multiply-adds those launches performed (questions x padded rows x padded size). */
+/* Device time (HIP events on the evaluator's stream) and launch count of the score kernel (top-1 and top-k; the
+ * top-k time includes its merge kernel) since load or since the last call; `macs` = multiply-adds those launches performed (questions x padded rows x padded size). */
 int w2b_eval_timing_read(w2b_eval *e, double *kernel_ms, int64_t *launches, double *macs);
 
 #ifdef __cplusplus

@@ -138,6 +138,10 @@ SIGNATURES = {
     "w2b_eval_lookup": (C.c_int64, [vp, C.c_char_p]),
     "w2b_eval_get_matrix": (C.c_int, [vp, f32p]),
     "w2b_eval_top1": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, i32p, f32p]),
+    "w2b_eval_topk": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, C.c_int32, i32p, f32p]),
+    "w2b_eval_neighbors": (C.c_int, [vp, C.c_int64, i32p, C.c_int32, i32p, f32p]),
+    "w2b_eval_nearest_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp), i64p]),
+    "w2b_eval_set_topk_scratch": (C.c_int, [vp, C.c_int64]),
     "w2b_eval_transcript": (C.c_int, [vp, C.c_char_p, C.c_int64, C.POINTER(vp), i64p]),
     "w2b_eval_free_text": (None, [vp]),
     "w2b_eval_set_kernel": (C.c_int, [vp, C.c_int32]),

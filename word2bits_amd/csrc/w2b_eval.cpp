@@ -17,6 +17,7 @@ namespace {
 constexpr int64_t kMaxW = 50;            // ref :24 max_w
 constexpr int64_t kTile = 256;           // padding unit of rows / questions (covers both kernels' tiles)
 constexpr int64_t kChunkQ = 1 << 16;     // questions per launch
+constexpr int64_t kTopkScratch = 1ll << 30;   // default bound of the top-k slot scratch of one launch
 
 inline bool is_space(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }   // isspace, C locale
 inline char c_upper(char c) { return (c >= 'a' && c <= 'z') ? (char)(c - 32) : c; }     // toupper, C locale
@@ -46,6 +47,10 @@ struct w2b_eval {
   double kernel_ms = 0;                                 // score-kernel time since the last timing_read
   int64_t launches = 0;
   double macs = 0;
+  // top-k scratch of one launch: bound / buckets / slot counts / slots / merged keys
+  void *tk_buf = nullptr;
+  size_t tk_bytes = 0;
+  int64_t tk_budget = 0;                                // 0 = kTopkScratch
 };
 
 static void eval_release(w2b_eval *e) {
@@ -55,6 +60,7 @@ static void eval_release(w2b_eval *e) {
   if (e->Q) (void)hipFree(e->Q);
   if (e->b123) (void)hipFree(e->b123);
   if (e->best) (void)hipFree(e->best);
+  if (e->tk_buf) (void)hipFree(e->tk_buf);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -262,6 +268,20 @@ extern "C" int w2b_eval_get_matrix(w2b_eval *e, float *out) {
   return W2B_OK;
 }
 
+// the per-call buffers of `np` (padded) questions
+static int eval_reserve_questions(w2b_eval *e, int64_t np) {
+  if (np <= e->cap_q) return W2B_OK;
+  if (e->Q) (void)hipFree(e->Q);
+  if (e->b123) (void)hipFree(e->b123);
+  if (e->best) (void)hipFree(e->best);
+  e->Q = nullptr; e->b123 = nullptr; e->best = nullptr; e->cap_q = 0;
+  if (hipMalloc(&e->Q, (size_t)np * e->ld * 4) != hipSuccess || hipMalloc(&e->b123, (size_t)np * 12) != hipSuccess ||
+      hipMalloc(&e->best, (size_t)np * 8) != hipSuccess)
+    return W2B_ENOMEM;
+  e->cap_q = np;
+  return W2B_OK;
+}
+
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                              int32_t *best, float *bestd) {
   if (!e || nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !best)))
@@ -274,16 +294,7 @@ extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const i
   for (int64_t q0 = 0; q0 < nq; q0 += kChunkQ) {
     const int64_t n = (nq - q0 < kChunkQ) ? nq - q0 : kChunkQ;
     const int64_t np = (n + kTile - 1) / kTile * kTile;
-    if (np > e->cap_q) {
-      if (e->Q) (void)hipFree(e->Q);
-      if (e->b123) (void)hipFree(e->b123);
-      if (e->best) (void)hipFree(e->best);
-      e->Q = nullptr; e->b123 = nullptr; e->best = nullptr; e->cap_q = 0;
-      if (hipMalloc(&e->Q, (size_t)np * e->ld * 4) != hipSuccess || hipMalloc(&e->b123, (size_t)np * 12) != hipSuccess ||
-          hipMalloc(&e->best, (size_t)np * 8) != hipSuccess)
-        return efail(W2B_ENOMEM, "w2b_eval_top1: device allocation failed");
-      e->cap_q = np;
-    }
+    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, "w2b_eval_top1: device allocation failed");
     int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
     EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
@@ -318,6 +329,97 @@ extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const i
       }
     }
   }
+  return W2B_OK;
+}
+
+
+// ------------------------------------------------------------------------------------ top-k
+// ref :155-177 with N = k.  The questions go through the scan in chunks sized so that the slot scratch of one launch
+// (w2b_internal.h) stays within the budget; a chunk is never smaller than one 128-question tile.
+static int eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t k,
+                     int32_t *best, float *bestd, const char *who) {
+  if (!e || nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !best)))
+    return efail(W2B_EINVAL, std::string(who) + ": bad argument");
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, std::string(who) + ": k must be 1..64");
+  for (int64_t q = 0; q < nq; q++)
+    if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
+      return efail(W2B_EINVAL, std::string(who) + ": question row out of range");
+  EHIP(hipSetDevice(e->device));
+  int nunits = 0, cap = 0;
+  w2b_eval_topk_layout(e->words, k, e->fused && e->variant != 0, &nunits, &cap);
+  // per question: bound + k buckets + one byte per slot (zeroed together), k merged keys, nunits slots of cap keys
+  const int64_t zero_q = 8 + 8 * (int64_t)k + nunits, per_q = zero_q + 8 * (int64_t)k + 8 * (int64_t)nunits * cap;
+  const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+  int64_t chunk = budget / per_q / 128 * 128;
+  if (chunk < 128) chunk = 128;
+  if (chunk > kChunkQ) chunk = kChunkQ;
+  std::vector<unsigned long long> keys;
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int64_t n = (nq - q0 < chunk) ? nq - q0 : chunk;
+    const int64_t np = (n + kTile - 1) / kTile * kTile;
+    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
+    const size_t zero_bytes = ((size_t)n * zero_q + 7) / 8 * 8, need = (size_t)n * per_q + 8;
+    if (need > e->tk_bytes) {
+      if (e->tk_buf) (void)hipFree(e->tk_buf);
+      e->tk_buf = nullptr;
+      e->tk_bytes = 0;
+      if (hipMalloc(&e->tk_buf, need) != hipSuccess) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
+      e->tk_bytes = need;
+    }
+    unsigned long long *bound = (unsigned long long *)e->tk_buf, *bkt = bound + n;
+    unsigned char *cnt = (unsigned char *)(bkt + n * k);
+    unsigned long long *merged = (unsigned long long *)((char *)e->tk_buf + zero_bytes), *slots = merged + n * k;
+    int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
+    EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
+    EHIP(hipMemsetAsync(e->tk_buf, 0, zero_bytes, e->stream));
+    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
+    hipEvent_t t0, t1;
+    EHIP(hipEventCreate(&t0));
+    EHIP(hipEventCreate(&t1));
+    EHIP(hipEventRecord(t0, e->stream));
+    hipError_t le = w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3,
+                                         k, bound, bkt, slots, cnt, merged, e->variant, e->stream);
+    if (le == hipSuccess) le = hipEventRecord(t1, e->stream);
+    keys.assign((size_t)n * k, 0ull);   // (no rows: nothing is launched and every list is empty)
+    if (le == hipSuccess && e->words > 0)
+      le = hipMemcpyAsync(keys.data(), merged, (size_t)n * k * 8, hipMemcpyDeviceToHost, e->stream);
+    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+    float ms = 0;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, t0, t1);
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    if (le != hipSuccess) return efail(W2B_EHIP, std::string(who) + ": " + hipGetErrorString(le));
+    e->kernel_ms += ms;
+    e->launches++;
+    e->macs += (double)n * (double)e->words * (double)e->size;
+    for (int64_t i = 0; i < n * k; i++) {
+      const unsigned long long key = keys[(size_t)i];
+      best[q0 * k + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
+      if (bestd) {
+        const uint32_t bits = (uint32_t)(key >> 32);
+        memcpy(&bestd[q0 * k + i], &bits, 4);
+      }
+    }
+  }
+  return W2B_OK;
+}
+
+extern "C" int w2b_eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
+                             int32_t k, int32_t *best, float *bestd) {
+  return eval_topk(e, nq, b1, b2, b3, k, best, bestd, "w2b_eval_topk");
+}
+
+// vec = (M[r] - M[r]) + M[r]: M[r] up to the sign of a zero, which no chain that starts at +0 can see
+extern "C" int w2b_eval_neighbors(w2b_eval *e, int64_t nq, const int32_t *rows, int32_t k, int32_t *best, float *bestd) {
+  return eval_topk(e, nq, rows, rows, rows, k, best, bestd, "w2b_eval_neighbors");
+}
+
+extern "C" int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes) {
+  if (!e || bytes < 0) return efail(W2B_EINVAL, "w2b_eval_set_topk_scratch: bad argument");
+  e->tk_budget = bytes;
   return W2B_OK;
 }
 
@@ -451,6 +553,80 @@ extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t l
   appendf(txt, "Questions seen / total: %d %d   %.2f %% \n", TQS, TQ, TQS / (float)TQ * 100);
   char *buf = (char *)malloc(txt.size() + 1);
   if (!buf) return efail(W2B_ENOMEM, "w2b_eval_transcript: out of memory");
+  memcpy(buf, txt.data(), txt.size());
+  buf[txt.size()] = 0;
+  *out = buf;
+  if (out_len) *out_len = (int64_t)txt.size();
+  return W2B_OK;
+}
+
+
+// ------------------------------------------------------------------------------------ nearest: the text form
+extern "C" int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out,
+                                     int64_t *out_len) {
+  if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_nearest_text: bad argument");
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_nearest_text: k must be 1..64");
+  *out = nullptr;
+  struct Line { std::string head; std::string error; int64_t q; };
+  std::vector<Line> lines;
+  std::vector<int32_t> b1s, b2s, b3s;
+  for (int64_t pos = 0; pos < len;) {
+    int64_t end = pos;
+    while (end < len && queries[end] != '\n') end++;
+    std::vector<std::string> tok;
+    for (int64_t i = pos; i < end;) {
+      while (i < end && is_space((unsigned char)queries[i])) i++;
+      const int64_t s0 = i;
+      while (i < end && !is_space((unsigned char)queries[i])) i++;
+      if (i > s0) {
+        tok.emplace_back(queries + s0, (size_t)(i - s0));
+        upper_inplace(tok.back());                                  // ref :118
+      }
+    }
+    pos = end + 1;
+    if (tok.empty()) continue;
+    Line ln{std::string(), std::string(), -1};
+    for (size_t i = 0; i < tok.size(); i++) ln.head += (i ? " " : "") + tok[i];
+    if (tok.size() != 1 && tok.size() != 3) {
+      ln.error = "expected 1 or 3 words";
+    } else {
+      int64_t r[3] = {0, 0, 0};
+      for (size_t i = 0; i < tok.size() && ln.error.empty(); i++) {
+        r[i] = w2b_eval_lookup(e, tok[i].c_str());
+        if (r[i] == e->words) ln.error = "not in vocabulary: " + tok[i];
+      }
+      if (ln.error.empty()) {
+        if (tok.size() == 1) r[1] = r[2] = r[0];
+        ln.q = (int64_t)b1s.size();
+        b1s.push_back((int32_t)r[0]);
+        b2s.push_back((int32_t)r[1]);
+        b3s.push_back((int32_t)r[2]);
+      }
+    }
+    lines.push_back(ln);
+  }
+  std::vector<int32_t> best(b1s.size() * (size_t)k);
+  std::vector<float> bestd(b1s.size() * (size_t)k);
+  if (!b1s.empty()) {
+    const int rc = w2b_eval_topk(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), k, best.data(), bestd.data());
+    if (rc != W2B_OK) return rc;
+  }
+  std::string txt;
+  for (const Line &ln : lines) {
+    txt += ln.head;
+    if (!ln.error.empty()) {
+      txt += ": " + ln.error + "\n";
+      continue;
+    }
+    txt += ":\n";
+    for (int j = 0; j < k; j++) {
+      const int32_t c = best[(size_t)(ln.q * k + j)];
+      if (c < 0) break;
+      appendf(txt, "%d\t%s\t%.6f\n", j + 1, e->vocab.data() + (int64_t)c * kMaxW, (double)bestd[(size_t)(ln.q * k + j)]);
+    }
+  }
+  char *buf = (char *)malloc(txt.size() + 1);
+  if (!buf) return efail(W2B_ENOMEM, "w2b_eval_nearest_text: out of memory");
   memcpy(buf, txt.data(), txt.size());
   buf[txt.size()] = 0;
   *out = buf;

@@ -130,6 +130,14 @@ hipError_t w2b_launch_eval_queries(const float *M, long long ld, long long nq, c
 hipError_t w2b_launch_eval_scores(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
                                   const int *b1, const int *b2, const int *b3, unsigned long long *best,
                                   int variant /* 0: vector-ALU kernel always; else MFMA when fused */, hipStream_t s);
+// top-k form of the scan (ref :155-177 with N = k).  Per question: `nunits` slots of `cap` keys (`keys`), one byte per
+// slot (`cnt`, zeroed by the caller), k bucket keys (`bkt`, zeroed) and the bound (`bound`, zeroed); w2b_eval_topk_layout
+// gives nunits and cap.  out[q * k + j] = the j-th best key (score bits << 32 | ~row), 0 when fewer rows qualify.
+void w2b_eval_topk_layout(long long words, int k, bool mfma, int *nunits, int *cap);
+hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
+                                const int *b1, const int *b2, const int *b3, int k, unsigned long long *bound,
+                                unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
+                                unsigned long long *out, int variant, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

@@ -81,11 +81,53 @@ __device__ __forceinline__ f32x2 mac2(float a, f32x2 b, f32x2 acc) {
   return acc + av * b;    // two roundings: -ffp-contract=off for this TU
 }
 
-template <bool FUSED>
-__global__ void __launch_bounds__(ETHREADS, 2)
-k_eval_scores(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int q_tiles,
-              int c_tiles, int c_per_xcd, const int *__restrict__ b1, const int *__restrict__ b2,
-              const int *__restrict__ b3, unsigned long long *__restrict__ best) {
+// ------------------------------------------------------------------------------------ top-k (ref :155-177, N = k)
+// The scans below end either in the arg-max (TOPK = false: the kernels k_eval_scores / k_eval_scores_mfma) or in the
+// top-k selection (TOPK = true: k_eval_topk / k_eval_topk_mfma): same main loop, other epilogue.  A "unit" is the
+// set of rows whose scores for one question sit in one lane (vector ALU: 8 rows) or one lane pair (MFMA: 64 rows);
+// every (question, unit) owns a slot of `cap` = min(k, rows per unit) keys in `keys` and a byte in `cnt` (zeroed by
+// the host) that says how many of them were written.  The key is the arg-max's: score bits << 32 | ~row, unique
+// per row, and descending key order is the reference's order (score down, equal scores by ascending row).
+// `bound[q]` is a lower bound on the question's k-th best key; keys that do not beat it are dropped, which is what
+// keeps the epilogue short and the slots almost empty.  It has two sources, both lock free:
+//   * a unit that holds more than cap = k candidates keeps the k largest and publishes its k-th;
+//   * bkt[q][j], j = unit % k, is the largest key seen in the units of residue j: k keys of k different rows, so
+//     their minimum bounds the k-th best from below (with every row scanned it is about the 3k-th best score).
+// A stale bound is only lower.  A key above the final bound was above every bound its unit saw, so it was dropped
+// only if its unit held k larger ones: k_eval_topk_merge finds the exact top k among the slots.
+struct TopkArgs {
+  unsigned long long *keys;   // [nq][nunits][cap]
+  unsigned char *cnt;         // [nq][nunits]
+  unsigned long long *bkt;    // [nq][k]
+  int k, cap, nunits;
+};
+
+__device__ __forceinline__ unsigned long long ld_key(const unsigned long long *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// `key` is the largest candidate of (q, unit)
+__device__ inline void topk_note_max(unsigned long long *bkt, int k, unsigned long long *bound, int q, int unit,
+                                     unsigned long long key) {
+  unsigned long long *b = bkt + (long long)q * k;
+  const unsigned long long old = atomicMax(&b[unit % k], key);
+  if (old >= key) return;
+  const unsigned long long cur = ld_key(&bound[q]);
+  if (old > cur) return;                 // the bucket was not the smallest one: the minimum stays
+  unsigned long long mn = ~0ull;
+#pragma unroll 8
+  for (int j = 0; j < k; j++) {
+    const unsigned long long v = ld_key(&b[j]);
+    mn = v < mn ? v : mn;
+  }
+  if (mn > cur) atomicMax(&bound[q], mn);
+}
+
+template <bool FUSED, bool TOPK>
+__device__ __forceinline__ void
+eval_scores_body(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int q_tiles,
+                 int c_tiles, int c_per_xcd, const int *__restrict__ b1, const int *__restrict__ b2,
+                 const int *__restrict__ b3, unsigned long long *__restrict__ best, const TopkArgs &tk) {
   __shared__ float As[2][EBK][ELD];
   __shared__ float Bs[2][EBK][ELD];
   __shared__ unsigned long long skey[EBM];
@@ -146,6 +188,50 @@ k_eval_scores(const float *__restrict__ Q, const float *__restrict__ M, int nq, 
     // the other buffer is rewritten only after the next barrier of the following iteration's compute
   }
 
+  if constexpr (TOPK) {
+    // unit = (row tile, tx): the thread's 8 rows of a question; cap = min(k, 8), so every key above the bound fits
+    // (for k < 8 the smallest are dropped: the slot keeps the cap largest)
+    const int unit = ct * 16 + tx;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int ml = (i < 4) ? ty * 4 + i : 64 + ty * 4 + (i - 4);
+      const int q = m0 + ml;
+      if (q >= nq) continue;
+      const int e1 = b1[q], e2 = b2[q], e3 = b3[q];
+      const unsigned long long bnd = ld_key(&best[q]);
+      unsigned long long ks[8];
+      int n = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int c = n0 + ((j < 2) ? tx * 4 + j * 2 + h : 64 + tx * 4 + (j - 2) * 2 + h);
+          const float d = acc[i][j][h];
+          const unsigned long long k2 =
+              ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
+          const bool ok = c < words && c != e1 && c != e2 && c != e3 && d > 0.f && k2 > bnd;
+          ks[j * 2 + h] = ok ? k2 : 0ull;
+          n += ok ? 1 : 0;
+        }
+      if (n == 0) continue;
+      unsigned long long *slot = tk.keys + ((long long)q * tk.nunits + unit) * tk.cap;
+      unsigned long long prev = ~0ull, mx = 0ull;
+      const int nw = n < tk.cap ? n : tk.cap;
+      for (int w = 0; w < nw; w++) {         // descending: the largest key below the one written last
+        unsigned long long cur = 0ull;
+#pragma unroll
+        for (int x = 0; x < 8; x++) cur = (ks[x] < prev && ks[x] > cur) ? ks[x] : cur;
+        slot[w] = cur;
+        if (w == 0) mx = cur;
+        prev = cur;
+      }
+      tk.cnt[(long long)q * tk.nunits + unit] = (unsigned char)nw;
+      if (n >= tk.k) atomicMax(&best[q], prev);     // k keys of this unit are >= prev (then cap == k)
+      topk_note_max(tk.bkt, tk.k, best, q, unit, mx);
+    }
+    return;
+  }
+
   // epilogue: strict-greater arg-max with ties to the lowest row (ref :166-175, N = 1, bestd starts at 0)
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -170,6 +256,22 @@ k_eval_scores(const float *__restrict__ Q, const float *__restrict__ M, int nq, 
   }
   __syncthreads();
   if (tid < EBM && skey[tid] && m0 + tid < nq) atomicMax(&best[m0 + tid], skey[tid]);
+}
+
+template <bool FUSED>
+__global__ void __launch_bounds__(ETHREADS, 2)
+k_eval_scores(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int q_tiles,
+              int c_tiles, int c_per_xcd, const int *__restrict__ b1, const int *__restrict__ b2,
+              const int *__restrict__ b3, unsigned long long *__restrict__ best) {
+  eval_scores_body<FUSED, false>(Q, M, nq, words, ld, q_tiles, c_tiles, c_per_xcd, b1, b2, b3, best, TopkArgs{});
+}
+
+template <bool FUSED>
+__global__ void __launch_bounds__(ETHREADS, 2)
+k_eval_topk(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int q_tiles,
+            int c_tiles, int c_per_xcd, const int *__restrict__ b1, const int *__restrict__ b2,
+            const int *__restrict__ b3, unsigned long long *__restrict__ bound, const TopkArgs tk) {
+  eval_scores_body<FUSED, true>(Q, M, nq, words, ld, q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
 }
 
 // ------------------------------------------------------------------------------------ fused mode on the matrix cores
@@ -208,10 +310,12 @@ typedef __attribute__((address_space(3))) volatile float lds_vf;
 //     two other workgroups instead of one.  At most 8 reads per burst: the LDS wait counter has four bits.
 // Measured and rejected: persistent workgroups that walk their tiles as one slab stream
 // (with or without the arg-max of tile t riding between the MFMAs of tile t+1): 5-10 % slower than this.
-__global__ void __launch_bounds__(ETHREADS, 3)
-k_eval_scores_mfma(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int nh,
-                   int q_tiles, int c_tiles, int c_per_xcd, int q_group, const int *__restrict__ b1,
-                   const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ best) {
+template <bool TOPK>
+__device__ __forceinline__ void
+eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int nh,
+                      int q_tiles, int c_tiles, int c_per_xcd, int q_group, const int *__restrict__ b1,
+                      const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ best,
+                      const TopkArgs &tk) {
   constexpr int MK = 16;
   // row pitch 130 floats: the staging writes of a 32-lane group (4 k-quads x 8 rows) fall on 32 different banks
   // (4 * 130 = 8 mod 32); the fragment reads are 32 consecutive floats of one k row whatever the pitch
@@ -372,6 +476,98 @@ k_eval_scores_mfma(const float *__restrict__ Q, const float *__restrict__ M, int
   // row m = wm + mt*32 + 8*(e/4) + 4*(l/32) + e%4, question n = wn + nt*32 + l%32; a lane walks its rows in
   // increasing order, so "strictly greater" keeps the lowest row among equal scores (the reference's first-wins).
   const int r0 = m0 + wm;
+  if constexpr (TOPK) {
+    // unit = this wavefront's 64 rows: the lane pair (l, l ^ 32) holds a question's 2 x 32 scores.  `seen` is the
+    // question's bound.  Usual case: no lane maximum reaches it (15 v_max3, as above).  Otherwise the lanes mark
+    // their candidates in a 32-bit mask; if there are any, the wavefront parks this half of its accumulators in
+    // its quarter of the operand tiles (dead by now), [accumulator][lane]: no bank conflicts, and the rest can
+    // index them.
+    __syncthreads();                    // every wavefront has read its last fragment
+    float *park = (wave < 2 ? &As[0][0][0] : &Bs[0][0][0]) + (wave & 1) * (32 * 64);
+    static_assert(2 * 32 * 64 <= 2 * MK * MLD, "two wavefronts park 32 x 64 floats in one operand buffer");
+    const int unit = ct * 2 + (wave & 1);
+    const unsigned lo0 = 0xFFFFFFFFu - (unsigned)(r0 + 4 * lk2);
+    auto key_at = [&](int i) {          // accumulator i = mt * 16 + e of the parked half
+      const unsigned off = (unsigned)((i >> 4) * 32 + 8 * ((i & 15) >> 2) + (i & 3));
+      return ((unsigned long long)__float_as_uint(park[i * 64 + lane]) << 32) | (unsigned long long)(lo0 - off);
+    };
+    auto lane_max = [&](unsigned rem, unsigned long long &mk, int &mi) {
+      mk = 0ull;
+      mi = 0;
+      for (unsigned t = rem; t; t &= t - 1) {
+        const int i = __builtin_ctz(t);
+        const unsigned long long k2 = key_at(i);
+        if (k2 > mk) { mk = k2; mi = i; }
+      }
+    };
+#pragma unroll
+    for (int nt = 0; nt < 2; nt++) {
+      const int q = n0 + wn + nt * 32 + l32;
+      const bool live = q < nq;
+      const int e1 = qw[nt][0], e2 = qw[nt][1], e3 = qw[nt][2];
+      const unsigned long long bnd = seen[nt];
+      float m = acc[0][nt][0];
+#pragma unroll
+      for (int e = 1; e < 15; e += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, acc[0][nt][e]), acc[0][nt][e + 1]);
+      m = __builtin_fmaxf(m, acc[0][nt][15]);
+#pragma unroll
+      for (int e = 0; e < 16; e += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, acc[1][nt][e]), acc[1][nt][e + 1]);
+      const bool may = live && m > 0.f && __float_as_uint(m) >= (unsigned)(bnd >> 32);          // (NaN: m > 0 fails)
+      if (!__any(may)) continue;
+      unsigned cm = 0u;
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+          const int off = mt * 32 + 8 * (e >> 2) + (e & 3), c = r0 + 4 * lk2 + off;
+          const float d = acc[mt][nt][e];
+          const unsigned long long k2 =
+              ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(lo0 - (unsigned)off);
+          const bool ok = may && c < words && c != e1 && c != e2 && c != e3 && d > 0.f && k2 > bnd;
+          cm |= ok ? 1u << (mt * 16 + e) : 0u;
+        }
+      if (!__any(cm != 0u)) continue;
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) park[(mt * 16 + e) * 64 + lane] = acc[mt][nt][e];
+      int n_me = __builtin_popcount(cm), n_ot = __shfl_xor(n_me, 32, 64);
+      const int tot = n_me + n_ot;
+      unsigned long long mk;
+      int mi;
+      lane_max(cm, mk, mi);
+      unsigned long long pm = __shfl_xor(mk, 32, 64);
+      pm = mk > pm ? mk : pm;           // the pair's largest candidate
+      unsigned long long kth = 0ull;
+      if (tot > tk.cap) {               // (same for both lanes of a pair) keep the cap largest: cap rounds of
+        unsigned rem = cm, keep = 0u;   // "the larger of the two lane maxima leaves"; keys are unique
+        for (int j = 0; j < tk.cap; j++) {
+          const unsigned long long o = __shfl_xor(mk, 32, 64);
+          if (mk > o) {
+            keep |= 1u << mi;
+            rem &= ~(1u << mi);
+            kth = mk;
+            lane_max(rem, mk, mi);
+          } else {
+            kth = o;
+          }
+        }
+        cm = keep;
+        n_me = __builtin_popcount(cm);
+        n_ot = tk.cap - n_me;
+      }
+      if (cm) {
+        unsigned long long *slot = tk.keys + ((long long)q * tk.nunits + unit) * tk.cap + (lk2 ? n_ot : 0);
+        for (unsigned t = cm; t; t &= t - 1) *slot++ = key_at(__builtin_ctz(t));
+      }
+      if (lk2 == 0 && pm) {
+        tk.cnt[(long long)q * tk.nunits + unit] = (unsigned char)(n_me + n_ot);
+        if (kth && tk.cap == tk.k) atomicMax(&best[q], kth);     // k keys of this unit are >= kth
+        topk_note_max(tk.bkt, tk.k, best, q, unit, pm);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int nt = 0; nt < 2; nt++) {
     const int nl = wn + nt * 32 + l32, q = n0 + nl;
@@ -429,6 +625,58 @@ k_eval_scores_mfma(const float *__restrict__ Q, const float *__restrict__ M, int
   if (tid < EBN && skey[tid] && n0 + tid < nq) atomicMax(&best[n0 + tid], skey[tid]);
 }
 
+__global__ void __launch_bounds__(ETHREADS, 3)
+k_eval_scores_mfma(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int nh,
+                   int q_tiles, int c_tiles, int c_per_xcd, int q_group, const int *__restrict__ b1,
+                   const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ best) {
+  eval_scores_mfma_body<false>(Q, M, nq, words, ld, nh, q_tiles, c_tiles, c_per_xcd, q_group, b1, b2, b3, best,
+                               TopkArgs{});
+}
+
+__global__ void __launch_bounds__(ETHREADS, 3)
+k_eval_topk_mfma(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int nh,
+                 int q_tiles, int c_tiles, int c_per_xcd, int q_group, const int *__restrict__ b1,
+                 const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ bound,
+                 const TopkArgs tk) {
+  eval_scores_mfma_body<true>(Q, M, nq, words, ld, nh, q_tiles, c_tiles, c_per_xcd, q_group, b1, b2, b3, bound, tk);
+}
+
+// One workgroup per question: the k largest keys among its slots, in descending order (= the reference's order).
+// Round j finds the largest key below the one of round j - 1; the slots of a question are few and mostly empty.
+__global__ void __launch_bounds__(256)
+k_eval_topk_merge(const TopkArgs tk, unsigned long long *__restrict__ out) {
+  __shared__ unsigned long long red[4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const unsigned char *cnt = tk.cnt + (long long)q * tk.nunits;
+  const unsigned long long *keys = tk.keys + (long long)q * tk.nunits * tk.cap;
+  unsigned long long prev = ~0ull;
+  for (int j = 0; j < tk.k; j++) {
+    unsigned long long best = 0ull;
+    if (prev) {
+      for (int u = tid; u < tk.nunits; u += 256) {
+        const int n = cnt[u];
+        for (int i = 0; i < n; i++) {
+          const unsigned long long v = keys[(long long)u * tk.cap + i];
+          best = (v < prev && v > best) ? v : best;
+        }
+      }
+#pragma unroll
+      for (int d = 32; d; d >>= 1) {
+        const unsigned long long o = __shfl_xor(best, d, 64);
+        best = o > best ? o : best;
+      }
+    }
+    __syncthreads();                   // red[] of the previous round has been read
+    if ((tid & 63) == 0) red[tid >> 6] = best;
+    __syncthreads();
+    best = red[0];
+#pragma unroll
+    for (int w = 1; w < 4; w++) best = red[w] > best ? red[w] : best;
+    if (tid == 0) out[(long long)q * tk.k + j] = best;       // 0: fewer than k rows qualify
+    prev = best;
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------ launchers
@@ -477,5 +725,44 @@ hipError_t w2b_launch_eval_scores(const float *Q, const float *M, int nq, int wo
   else
     hipLaunchKernelGGL((k_eval_scores<false>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
                        q_tiles, c_tiles, c_per_xcd, b1, b2, b3, best);
+  return hipGetLastError();
+}
+
+void w2b_eval_topk_layout(long long words, int k, bool mfma, int *nunits, int *cap) {
+  const int c_tiles = (int)((words + EBN - 1) / EBN);
+  const int rows = mfma ? 64 : 8;             // rows per unit
+  *nunits = c_tiles * (EBN / rows);
+  *cap = k < rows ? k : rows;
+}
+
+hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
+                                const int *b1, const int *b2, const int *b3, int k, unsigned long long *bound,
+                                unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
+                                unsigned long long *out, int variant, hipStream_t s) {
+  if (nq <= 0 || words <= 0) return hipSuccess;
+  const int q_tiles = (nq + EBM - 1) / EBM, c_tiles = (words + EBN - 1) / EBN;
+  const int c_per_xcd = (c_tiles + 7) / 8;
+  const long long grid = 8ll * c_per_xcd * q_tiles;
+  const bool mfma = fused && variant != 0;
+  TopkArgs tk;
+  tk.keys = keys;
+  tk.cnt = cnt;
+  tk.bkt = bkt;
+  tk.k = k;
+  w2b_eval_topk_layout(words, k, mfma, &tk.nunits, &tk.cap);
+  if (mfma) {
+    int g = variant > 1 ? variant : 8;
+    if (g > q_tiles) g = q_tiles;
+    const long long grid2 = 8ll * c_per_xcd * ((q_tiles + g - 1) / g * g);
+    hipLaunchKernelGGL(k_eval_topk_mfma, dim3((unsigned)grid2), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
+                       (size + 7) / 8, q_tiles, c_tiles, c_per_xcd, g, b1, b2, b3, bound, tk);
+  }
+  else if (fused)
+    hipLaunchKernelGGL((k_eval_topk<true>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
+                       q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
+  else
+    hipLaunchKernelGGL((k_eval_topk<false>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
+                       q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
+  hipLaunchKernelGGL(k_eval_topk_merge, dim3((unsigned)nq), dim3(256), 0, s, tk, out);
   return hipGetLastError();
 }

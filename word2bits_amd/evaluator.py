@@ -66,6 +66,39 @@ class Evaluator:
         _lib.check(self._L.w2b_eval_top1(self._h, n, p(b1), p(b2), p(b3), p(best), bestd.ctypes.data_as(_lib.f32p)))
         return best, bestd
 
+    def topk(self, b1, b2, b3, k):
+        """ref :155-177 with N = k: (rows int32 [nq, k], scores float32 [nq, k]) in the reference's order (score down,
+        equal scores by ascending row); a list of fewer than k rows ends in row -1 / score 0.  1 <= k <= 64."""
+        b1, b2, b3 = (np.ascontiguousarray(x, np.int32) for x in (b1, b2, b3))
+        n, k = len(b1), int(k)
+        best, bestd = np.empty((n, max(k, 0)), np.int32), np.empty((n, max(k, 0)), np.float32)
+        p = lambda a: a.ctypes.data_as(_lib.i32p)
+        _lib.check(self._L.w2b_eval_topk(self._h, n, p(b1), p(b2), p(b3), k, p(best), bestd.ctypes.data_as(_lib.f32p)))
+        return best, bestd
+
+    def neighbors(self, rows, k):
+        """The k nearest rows of each row in `rows` (the row itself excluded): topk(rows, rows, rows, k)."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        n, k = len(rows), int(k)
+        best, bestd = np.empty((n, max(k, 0)), np.int32), np.empty((n, max(k, 0)), np.float32)
+        p = lambda a: a.ctypes.data_as(_lib.i32p)
+        _lib.check(self._L.w2b_eval_neighbors(self._h, n, p(rows), k, p(best), bestd.ctypes.data_as(_lib.f32p)))
+        return best, bestd
+
+    def nearest_text(self, queries, k):
+        """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
+        queries = bytes(queries)
+        out, n = C.c_void_p(), C.c_int64()
+        _lib.check(self._L.w2b_eval_nearest_text(self._h, queries, len(queries), int(k), C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            self._L.w2b_eval_free_text(out)
+
+    def set_topk_scratch(self, nbytes):
+        """Upper bound for the device scratch of one top-k launch (0 = default); results never depend on it."""
+        _lib.check(self._L.w2b_eval_set_topk_scratch(self._h, int(nbytes)))
+
     def transcript(self, questions):
         """stdout of `compute_accuracy FILE bitlevel threshold < questions` as bytes."""
         questions = bytes(questions)
