@@ -47,7 +47,7 @@ def flat(t):
 
 
 def saturated_rows(counts, words, window, negative):
-    """the library's rule for mode 2 restated (w2b_trainer.cpp xchg_saturated): per table, rows 1..n with n the result of
+    """the library's rule for mode 2 restated (w2b_trainer.cpp xchg_saturated_prefix): per table, rows 1..n with n the result of
     the same binary search over `rate x words >= 32` (the vocabulary is meant to be sorted by count)"""
     c = counts.astype(np.float64)
     pw, tot = (c ** 0.75).sum(), c.sum()

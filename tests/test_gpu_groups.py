@@ -96,7 +96,7 @@ def test_row_group_kernel_falls_back_where_it_does_not_fit(gpu):
         t.set_vocab_counts(np.full(V, 50, np.int64), 0)
         assert t.worker_kernel_name() == "plain", kw
         t.close()
-    # automatic: short rows run the row groups -- unless the fidelity budget is thin already (w2b_trainer.cpp groups_plan):
+    # automatic: short rows run the row groups -- unless the fidelity budget is thin already (w2b_plan.cpp groups_run):
     # shards shorter than 50 000 words per worker, or a vocabulary so small and flat that every row collides
     Vz = 60000
     zipf = np.maximum(5, (3e7 / (np.arange(Vz) + 1.0))).astype(np.int64)

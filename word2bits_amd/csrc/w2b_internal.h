@@ -1,5 +1,5 @@
 // w2b_internal.h -- structures shared by the HIP kernels (w2b_kernels.hip) and the host side of the
-// C ABI (w2b_trainer.cpp).  Not part of the public interface (include/word2bits_hip.h).
+// C ABI (w2b_trainer.cpp, w2b_plan.cpp).  Not part of the public interface (include/word2bits_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -89,6 +89,12 @@ struct W2bParams {
                                   // w2b_tuning.concurrent_workers)
   float starting_alpha, sample, reg;
 };
+
+// the fields above that follow from the configuration and the tuning knobs alone (w2b_plan.cpp): what the shape predicates
+// below read.  The launch policy and the trainer's make_params both start from it.
+struct w2b_config;
+struct w2b_tuning;
+void w2b_shape_params(W2bParams &p, const w2b_config &cfg, const w2b_tuning &tune);
 
 // launchers implemented in w2b_kernels.hip --------------------------------------------------------
 // block size chosen from dim: one thread per 16-byte (or 4-byte) column of a row

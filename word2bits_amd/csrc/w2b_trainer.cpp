@@ -4,6 +4,7 @@
 #include "../../include/word2bits_hip.h"
 #include "../../include/word2bits_corpus.h"
 #include "w2b_internal.h"
+#include "w2b_plan.h"
 
 #include <rccl/rccl.h>
 
@@ -35,9 +36,8 @@ int w2b_internal_fail(int code, const char *msg) { return fail(code, msg ? msg :
   } while (0)
 
 struct w2b_trainer {
-  w2b_config cfg{};
+  W2bPlanInputs in;             // configuration, tuning knobs, compute units, word-count statistics: what the launch policy reads (w2b_plan.h)
   int device = 0;
-  int num_cus = 0;
   hipStream_t stream = nullptr;
   float *uv = nullptr;          // u followed by v (one allocation: one all-reduce)
   float *base = nullptr;        // snapshot for the delta-sum replica sync
@@ -48,15 +48,9 @@ struct w2b_trainer {
   float *keep = nullptr;
   float *entry = nullptr;       // scratch rows of the sentence-resident kernel
   size_t entry_floats = 0;
-  // XCD-shared copies of the hottest rows (XHot in w2b_device.hpp)
-  w2b_tuning tune{};            // knobs of include/word2bits_hip.h (defaults set in w2b_trainer_create)
-  std::vector<double> rate_v, rate_u;   // [k]: uses of row k + 1 of v (as a target) / of u (as a context row) per centre word
-  std::vector<double> ctx_share;        // [k]: share of the KEPT (sub-sampled) context positions that rows 1..k+1 hold
-  std::vector<int64_t> counts;          // vocab[].cn as given to w2b_set_vocab_counts (sorted by count behind row 0)
-  double counts_pw = 0, counts_tot = 0; // sum cn^0.75, sum cn
-  double counts_tot_kept = 0;           // sum of the expected KEPT occurrences (sub-sampling, ref :403-406)
   float *wide_scratch = nullptr;        // process_word_wide: [workgroups][2][dim]
   size_t wide_floats = 0;
+  // XCD-shared copies of the hottest rows (XHot in w2b_device.hpp)
   float *xhot = nullptr;        // [W2B_NXCD]{copies [nu + nv][dim], entries [nu + nv][dim], merge locks [nu + nv][W2B_MAXW]}
   size_t xhot_floats = 0;
   float *rc = nullptr;          // row-group kernel: 64 ints of flags + refreshed per-XCD copies of the hottest context rows
@@ -194,14 +188,16 @@ extern "C" float w2b_quantize(float x, int32_t bitlevel) {
 }
 
 // --------------------------------------------------------------------------------- lifetime
-static W2bParams make_params(const w2b_trainer *t) {
+// Everything a training launch passes to its kernel: the shape (w2b_shape_params), the trainer's device memory, the plan's numbers.
+static W2bParams make_params(const w2b_trainer *t, const W2bLaunchPlan &lp) {
   W2bParams p{};
+  w2b_shape_params(p, t->in.cfg, t->in.tune);
   p.u = t->uv;
   p.v = t->uv + t->table_elems;
   p.exp_table = t->exp_table;
   p.table = t->table;
   p.table_size = t->table_size;
-  p.keep = (t->cfg.sample > 0) ? t->keep : nullptr;
+  p.keep = (t->in.cfg.sample > 0) ? t->keep : nullptr;
   p.corpus = t->corpus;
   p.n_tokens = t->n_tokens;
   p.corpus_more = t->corpus_more ? 1 : 0;
@@ -210,64 +206,37 @@ static W2bParams make_params(const w2b_trainer *t) {
   p.jump_a = t->jump_a;
   p.jump_c = t->jump_c;
   p.table_magic = t->table_size > 1 ? (unsigned long long)((((unsigned __int128)1) << 64) / (unsigned __int128)t->table_size) : 0;
-  p.window_magic = t->cfg.window > 1 ? (unsigned long long)((((unsigned __int128)1) << 64) / (unsigned __int128)t->cfg.window) : 0;
-  {
-    const unsigned long long bytes = (unsigned long long)t->table_elems * sizeof(float);
-    p.tab_bytes = bytes < 0x7fffffffull ? (unsigned)bytes : 0u;   // signed 32-bit scalar offsets
-    // w2b_tuning.force_row_desc: run the large-table form (per-row buffer descriptors, what tables >= 2 GiB use) on any size
-    if (t->tune.force_row_desc) p.tab_bytes = 0u;
-  }
-  p.vocab_size = t->cfg.vocab_size;
-  p.train_words = t->cfg.train_words;
-  p.iter = t->cfg.iter;
-  p.dim = t->cfg.layer1_size;
-  p.window = t->cfg.window;
-  p.negative = t->cfg.negative;
-  p.bitlevel = t->cfg.bitlevel;
-  p.num_threads = t->cfg.num_threads;
-  p.total_threads = t->cfg.total_threads > 0 ? t->cfg.total_threads : t->cfg.num_threads;
-  p.mem_mode = t->cfg.relaxed_coherence;   // 0 coherent (sc1), 1 relaxed (plain); >1 experimental builds only
-  if (t->tune.mem_mode >= 0) p.mem_mode = t->tune.mem_mode;
-  p.exact = t->cfg.exact_reduction != 0;
-  if (p.exact) p.mem_mode = 0;             // the exact mode exists for coherent rows only
   p.entry = t->entry;
-  p.hot_period = t->tune.hot_period > 0 ? t->tune.hot_period : 8;   // centre words between two merge events of a worker
-                                       // (power of two; 0 = automatic: set per launch in xhot_prepare)
-  p.xhot = nullptr;                    // set by xhot_prepare() for the launch that uses the copies
-  p.xhot_u = p.xhot_v = 0;
-  p.xhot_m = 1;
-  p.xhot_w = (float)t->tune.hot_weight_permille / 1000.f;
-  p.uavg_rank = 0;
-  p.win_refresh = t->tune.window_refresh;
-  p.atomic_rank = 0;
-  p.atomic_rank_u = 0;
-  p.fresh_rank_u = 0;
-  (void)w2b_block_threads(t->cfg.layer1_size, nullptr, &p.wide);   // rows longer than a workgroup has columns
   p.wide_scratch = t->wide_scratch;
-  p.rc_rows = 0;
+  p.xhot = nullptr;                    // set by xhot_prepare() for the launch that uses the copies
+  p.xhot_u = lp.copies_u;
+  p.xhot_v = lp.copies_v;
+  p.hot_period = lp.merge_period;
+  p.xhot_m = lp.xhot_m;
+  p.uavg_rank = lp.uavg_rank;
+  p.atomic_rank = lp.atomic_rank_v;
+  p.atomic_rank_u = lp.atomic_rank_u;
+  p.fresh_rank_u = lp.fresh_rank_u;
+  p.rc_rows = 0;                       // set by rc_prepare() for a launch of the row-group kernel
   p.rc = nullptr;
   p.rc_flags = nullptr;
   p.worker_base = 0;
-  p.starting_alpha = t->cfg.alpha;
-  p.sample = t->cfg.sample;
-  p.reg = t->cfg.reg;
   return p;
 }
 
-static w2b_tuning default_tuning() {
-  w2b_tuning tn{};
-  tn.struct_size = (int32_t)sizeof(w2b_tuning);
-  tn.hot_rows_v = tn.hot_rows_u = -1;
-  tn.hot_period = 0;         // automatic
-  tn.hot_cap = 128;
-  tn.force_row_desc = 0;
-  tn.grid_per_cu = 0;
-  tn.mem_mode = -1;
-  tn.atomic_rank = -1;
-  tn.atomic_cap = 0;         // 0 = no cap
-  tn.hot_weight_permille = 1000 / W2B_NXCD;
-  tn.window_refresh = 16;
-  return tn;
+// Device buffer of at least `need` elements, grown on demand: the stream drains before the old buffer is freed (a launch in
+// flight may still use it).  *grown is set when the buffer is a new one (its contents are undefined).
+template <class T>
+static int grow(w2b_trainer *t, T **buf, size_t *cap, size_t need, bool *grown = nullptr) {
+  if (need <= *cap) return W2B_OK;
+  HIPCHK(hipStreamSynchronize(t->stream));
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = nullptr;
+  *cap = 0;
+  HIPCHK(hipMalloc(buf, sizeof(T) * need));
+  *cap = need;
+  if (grown) *grown = true;
+  return W2B_OK;
 }
 
 extern "C" int w2b_trainer_create(const w2b_config *cfg, w2b_trainer **out) {
@@ -286,13 +255,13 @@ extern "C" int w2b_trainer_create(const w2b_config *cfg, w2b_trainer **out) {
   w2b_trainer *t = new w2b_trainer();
   // every HIPCHK below returns on failure: the guard releases what was allocated so far
   struct Guard { w2b_trainer *t; ~Guard() { if (t) w2b_trainer_destroy(t); } } guard{t};
-  t->cfg = *cfg;
+  t->in.cfg = *cfg;
   t->device = cfg->device;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-  t->num_cus = prop.multiProcessorCount;
+  t->in.num_cus = prop.multiProcessorCount;
   t->debug = getenv("W2B_DEBUG") != nullptr;
-  t->tune = default_tuning();
+  t->in.tune = w2b_default_tuning();
   HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
   t->table_elems = (long long)cfg->vocab_size * cfg->layer1_size;
   HIPCHK(hipMalloc(&t->uv, sizeof(float) * 2 * t->table_elems));
@@ -370,7 +339,7 @@ extern "C" void w2b_trainer_destroy(w2b_trainer *t) {
 // --------------------------------------------------------------------------------- tuning knobs
 extern "C" int w2b_get_tuning(w2b_trainer *t, w2b_tuning *out) {
   if (!t || !out) return fail(W2B_EINVAL, "w2b_get_tuning: null argument");
-  *out = t->tune;
+  *out = t->in.tune;
   return W2B_OK;
 }
 
@@ -399,7 +368,7 @@ extern "C" int w2b_set_tuning(w2b_trainer *t, const w2b_tuning *in) {
   if (in->refresh_rows_u < -1 || in->refresh_rows_u > W2B_RC_MAX) return fail(W2B_EINVAL, "w2b_set_tuning: refresh_rows_u must be -1 .. 64");
   if (in->exchange_rule < 0 || in->exchange_rule > 2 || in->exchange_tau_u < 0 || in->exchange_tau_v < 0 || in->concurrent_workers < 0)
     return fail(W2B_EINVAL, "w2b_set_tuning: exchange_rule must be 0, 1 or 2, exchange_tau_* >= 0, concurrent_workers >= 0");
-  t->tune = *in;
+  t->in.tune = *in;
   return W2B_OK;
 }
 
@@ -472,9 +441,9 @@ void w2b_internal_trainer_view(w2b_trainer *t, float **u, float **v, long long *
   (void)xchg_fence(t);
   *u = t->uv;
   *v = t->uv + t->table_elems;
-  *V = t->cfg.vocab_size;
-  *D = t->cfg.layer1_size;
-  *bitlevel = t->cfg.bitlevel;
+  *V = t->in.cfg.vocab_size;
+  *D = t->in.cfg.layer1_size;
+  *bitlevel = t->in.cfg.bitlevel;
   *device = t->device;
   *stream = t->stream;
 }
@@ -490,7 +459,7 @@ extern "C" int w2b_export_quantized(w2b_trainer *t, float *out) {
   HIPCHK(hipMalloc(&tmp, sizeof(float) * (n < slab ? n : slab)));
   for (long long o = 0; o < n; o += slab) {
     const long long m = (n - o < slab) ? n - o : slab;
-    hipError_t e = w2b_launch_export(t->uv + o, t->uv + t->table_elems + o, tmp, m, t->cfg.bitlevel, t->stream);
+    hipError_t e = w2b_launch_export(t->uv + o, t->uv + t->table_elems + o, tmp, m, t->in.cfg.bitlevel, t->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out + o, tmp, sizeof(float) * m, hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
     if (e != hipSuccess) {
@@ -506,17 +475,17 @@ extern "C" int w2b_export_quantized(w2b_trainer *t, float *out) {
 extern "C" int w2b_export_packed(w2b_trainer *t, uint64_t *out) {
   NEED(t);
   if (!out) return fail(W2B_EINVAL, "w2b_export_packed: null output");
-  const int64_t wpr = w2b_packed_words_per_row(t->cfg.layer1_size, t->cfg.bitlevel);
+  const int64_t wpr = w2b_packed_words_per_row(t->in.cfg.layer1_size, t->in.cfg.bitlevel);
   if (wpr < 0) return fail(W2B_EUNSUPPORTED, "w2b_export_packed: bit-packed output exists for -bitlevel 1 and 2");
   if (int rc = xchg_fence(t)) return rc;
-  const long long V = t->cfg.vocab_size, slab_rows = (32ll << 20) / wpr > 0 ? (32ll << 20) / wpr : 1;   // <= 256 MB of words
+  const long long V = t->in.cfg.vocab_size, slab_rows = (32ll << 20) / wpr > 0 ? (32ll << 20) / wpr : 1;   // <= 256 MB of words
   unsigned long long *tmp = nullptr;
   HIPCHK(hipMalloc(&tmp, sizeof(unsigned long long) * (size_t)((V < slab_rows ? V : slab_rows) * wpr)));
   for (long long r = 0; r < V; r += slab_rows) {
     const long long m = (V - r < slab_rows) ? V - r : slab_rows;
-    const long long o = r * t->cfg.layer1_size;
-    hipError_t e = w2b_launch_export_packed(t->uv + o, t->uv + t->table_elems + o, tmp, m, t->cfg.layer1_size,
-                                            t->cfg.bitlevel, t->stream);
+    const long long o = r * t->in.cfg.layer1_size;
+    hipError_t e = w2b_launch_export_packed(t->uv + o, t->uv + t->table_elems + o, tmp, m, t->in.cfg.layer1_size,
+                                            t->in.cfg.bitlevel, t->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out + r * wpr, tmp, sizeof(uint64_t) * (size_t)(m * wpr), hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
     if (e != hipSuccess) {
@@ -541,53 +510,15 @@ extern "C" int w2b_set_unigram_table(w2b_trainer *t, const int32_t *table, int64
   return W2B_OK;
 }
 
-// How often is row i of v a target (ref :450-460)?  Per centre word: negative * cn_i^0.75 / sum cn^0.75 (the unigram
-// table) + cn_i / train_words (as the centre word itself); and row i of u a context row: (window + 1 on average,
-// SURVEY A.3) * cn_i / train_words.  The vocabulary is sorted by count, so the rows worth per-XCD copies / lossless adds
-// are a prefix; how long a prefix is decided per launch from these rates and the number of workers (xhot_plan,
-// atomic_plan, atomic_plan_u).  Host arithmetic only (w2b_plan_rows runs it without a device).
-// (a token is a centre / context word only if it survives sub-sampling, ref :403-406: the counts that matter for
-// those two roles are the expected KEPT occurrences; the negative draws use the raw counts, ref :112-128)
-static void word_rates(w2b_trainer *t, const int64_t *cn, const std::vector<float> &keep) {
-  const int64_t V = t->cfg.vocab_size;
-  double pw = 0, tot = 0, tot_kept = 0;
-  auto kept = [&](int64_t a) -> double {
-    if (a == 0) return 0.0;                                  // "</s>" is never a centre or context word (ref :400)
-    const double k = t->cfg.sample > 0 ? (double)keep[(size_t)a] : 1.0;
-    return (double)cn[a] * (k < 1.0 ? k : 1.0);
-  };
-  for (int64_t a = 0; a < V; a++) { pw += pow((double)cn[a], 0.75); tot += (double)cn[a]; tot_kept += kept(a); }
-  t->counts.assign(cn, cn + V);
-  t->counts_pw = pw;
-  t->counts_tot = tot;
-  t->counts_tot_kept = tot_kept;
-  const int n = (int)(V - 1 < W2B_XHOT_MAX ? V - 1 : W2B_XHOT_MAX);
-  t->rate_v.assign((size_t)(n > 0 ? n : 0), 0.0);
-  t->rate_u.assign((size_t)(n > 0 ? n : 0), 0.0);
-  t->ctx_share.assign((size_t)(n > 0 ? n : 0), 0.0);
-  {
-    double acc = 0;
-    for (int k = 0; k < n; k++) { acc += tot_kept > 0 ? kept(k + 1) / tot_kept : 0; t->ctx_share[(size_t)k] = acc; }
-  }
-  for (int k = 0; k < n; k++) {
-    const double c = (double)cn[k + 1];
-    // (raw counts for the choice of the rows with copies: measured in round 3 on the text8-sized corpus at 256 workers)
-    t->rate_v[k] = (pw > 0 ? t->cfg.negative * pow(c, 0.75) / pw : 0) + (tot > 0 ? c / tot : 0);
-    t->rate_u[k] = tot > 0 ? (t->cfg.window + 1) * c / tot : 0;
-  }
-}
-
 static int xchg_upload_rates(w2b_trainer *t);   // per-row update rates for the replica exchange's combination rule (below)
 
 extern "C" int w2b_set_vocab_counts(w2b_trainer *t, const int64_t *cn, int64_t table_size) {
   NEED(t);
   if (!cn) return fail(W2B_EINVAL, "w2b_set_vocab_counts: null counts");
-  const int64_t V = t->cfg.vocab_size;
-  std::vector<float> keep((size_t)V, 1.f);
-  if (t->cfg.sample > 0) w2b_build_keep_prob(cn, V, t->cfg.sample, t->cfg.train_words, keep.data());
+  const int64_t V = t->in.cfg.vocab_size;
+  const std::vector<float> keep = w2b_plan_set_counts(t->in, cn);
   if (!t->keep) HIPCHK(hipMalloc(&t->keep, sizeof(float) * V));
   HIPCHK(hipMemcpy(t->keep, keep.data(), sizeof(float) * V, hipMemcpyHostToDevice));
-  word_rates(t, cn, keep);
   if (int rc = xchg_upload_rates(t)) return rc;
   if (table_size > 0) {
     std::vector<int32_t> tab((size_t)table_size);
@@ -683,7 +614,7 @@ extern "C" int w2b_set_corpus(w2b_trainer *t, const int32_t *ids, int64_t n) {
   if (!ids || n < 0) return fail(W2B_EINVAL, "w2b_set_corpus: bad argument");
   t->corpus_more = false;
   for (int64_t i = 0; i < n; i++)       // a bad id would be an out-of-bounds row access on the device
-    if (ids[i] < 0 || ids[i] >= t->cfg.vocab_size) return fail(W2B_EINVAL, "w2b_set_corpus: token id out of range");
+    if (ids[i] < 0 || ids[i] >= t->in.cfg.vocab_size) return fail(W2B_EINVAL, "w2b_set_corpus: token id out of range");
   HIPCHK(hipStreamSynchronize(t->stream));
   if (t->corpus_owned) HIPCHK(hipFree(t->corpus_owned));
   t->corpus_owned = nullptr;
@@ -708,11 +639,11 @@ extern "C" int w2b_set_corpus_device(w2b_trainer *t, const void *ids_dev, int64_
 
 extern "C" int w2b_set_shards(w2b_trainer *t, const int64_t *starts, const int32_t *ov) {
   if (!t || !starts) return fail(W2B_EINVAL, "w2b_set_shards: bad argument");
-  const int nw = t->cfg.num_threads;
+  const int nw = t->in.cfg.num_threads;
   for (int i = 0; i < nw; i++) {
     if (starts[i] < 0 || (t->corpus && starts[i] > t->n_tokens))
       return fail(W2B_EINVAL, "w2b_set_shards: shard start outside the token stream");
-    if (ov && ov[i] != -2 && ov[i] != -1 && (ov[i] < 0 || ov[i] >= t->cfg.vocab_size))
+    if (ov && ov[i] != -2 && ov[i] != -1 && (ov[i] < 0 || ov[i] >= t->in.cfg.vocab_size))
       return fail(W2B_EINVAL, "w2b_set_shards: first_override is neither -2, -1 nor a word id");
   }
   t->shard_start.assign(starts, starts + nw);
@@ -727,13 +658,13 @@ extern "C" int w2b_epoch_begin(w2b_trainer *t) {
   if (!t->corpus || !t->shards_set) return fail(W2B_ESTATE, "w2b_epoch_begin: corpus/shards not set");
   for (long long st : t->shard_start)
     if (st > t->n_tokens) return fail(W2B_EINVAL, "w2b_epoch_begin: shard start outside the token stream");
-  if (t->cfg.negative > 0 && !t->table) return fail(W2B_ESTATE, "w2b_epoch_begin: unigram table not set");
-  if (t->cfg.sample > 0 && !t->keep) return fail(W2B_ESTATE, "w2b_epoch_begin: vocab counts not set");
-  const int nw = t->cfg.num_threads;
+  if (t->in.cfg.negative > 0 && !t->table) return fail(W2B_ESTATE, "w2b_epoch_begin: unigram table not set");
+  if (t->in.cfg.sample > 0 && !t->keep) return fail(W2B_ESTATE, "w2b_epoch_begin: vocab counts not set");
+  const int nw = t->in.cfg.num_threads;
   std::vector<W2bWorker> w((size_t)nw);
   memset(w.data(), 0, sizeof(W2bWorker) * nw);
   for (int i = 0; i < nw; i++) {
-    w[i].rng = (unsigned long long)(t->cfg.worker_offset + i);   // global worker id, ref :368
+    w[i].rng = (unsigned long long)(t->in.cfg.worker_offset + i);   // global worker id, ref :368
     w[i].cursor = t->shard_start[i];           // ref :377
     w[i].first_override = t->shard_override[i];
   }
@@ -747,262 +678,11 @@ extern "C" int w2b_epoch_begin(w2b_trainer *t) {
   return W2B_OK;
 }
 
-static void xhot_plan(const w2b_trainer *t, long long workers, bool with_u, int *nu, int *nv, bool legacy_u);
-
-// Which worker kernel runs: plain_worker_kernel 0 = automatic (sentence-resident kernel for coherent rows when
-// the window fits in LDS; plain kernel for relaxed rows, where caching in L2 already absorbs the re-reads and
-// four workgroups per CU win), 1 = plain, 2 = sentence-resident whenever it fits -- coherent rows only: relaxed rows and
-// the parity mode always run the plain kernel.  Returns the radius (-1 = plain kernel).
-static int worker_plan(const w2b_trainer *t) {
-  const int mode = t->cfg.plain_worker_kernel;
-  if (mode == 1 || mode == 3 || t->cfg.exact_reduction) return -1;   // the serial reduction lives in the plain kernel
-  if (t->cfg.relaxed_coherence) return -1;              // the sentence-resident kernel exists for coherent rows only
-  if (t->tune.mem_mode > 0) return -1;
-  if (mode == 0) {
-    // Automatic = the plain kernel (round 4).  The sentence-resident kernel keeps every context row PRIVATE to a worker
-    // for as long as the row is in its window -- up to 2 x window + 1 positions, where the reference's thread holds a
-    // context row for one -- and publishes the worker's accumulated progress when the row leaves.  With hundreds of
-    // workers every frequent word is in dozens of windows at once, and the sum of those private progresses over-shoots.
-    // Rounds 2-3 chose it wherever it was faster and kept it inside the fidelity gates of the regimes they measured
-    // (text8-sized corpus: -1 ... -2.5 %) with a consensus rule for the most frequent context rows; on the first
-    // held-out regime (Zipf exponent 1.2 at the configs[2] shape, tests/w2b_testlib.py HELDOUT) that same default is
-    // 13 % off the reference's first-epoch loss at 256 workers (28 % without the consensus rule), the plain kernel
-    // 0.1-2 %.  It stays available as an explicit choice (plain_worker_kernel = 2, ./word2bits -window-cache 1): the
-    // faster kernel at short rows, with this caveat.
-    return -1;
-  }
-  return w2b_resident_plan(t->cfg.layer1_size, t->cfg.window, t->cfg.negative);
-}
-
-static int atomic_plan(const w2b_trainer *t, long long workers);
-// worker_plan() + what w2b_train_step additionally has to respect: atomic row updates (small flat vocabularies) exist in
-// only some forms of the sentence-resident kernel; the others run the plain kernel.  ONE decision for w2b_train_step,
-// w2b_worker_kernel_info and w2b_suggested_threads (round 3 decided it in w2b_train_step alone, so the other two could
-// report the sentence-resident kernel while the plain one ran).
-static int effective_radius(const w2b_trainer *t, long long workers) {
-  int radius = worker_plan(t);
-  if (radius >= 0) {
-    W2bParams probe = make_params(t);
-    probe.atomic_rank = atomic_plan(t, workers);
-    if (probe.atomic_rank > 0 && !w2b_resident_atomic_ok(probe, radius)) radius = -1;
-  }
-  return radius;
-}
-
-// How many leading rows of u / v get per-XCD copies for a launch with `workers` concurrent workers / workgroups.
-// Explicit numbers (w2b_tuning.hot_rows_*) win; otherwise a row is taken when its expected load -- uses per centre word
-// x workers x row length -- reaches W2B_HOT_LOAD: a coherent row queues at its memory line (~7 M read-modify-writes per
-// second for a 3200-byte row), workers deliver ~50 K words/s each at 800 floats, and the load should stay well below a
-// tenth of that: rate x workers x floats >= 6400 is rate >= 0.016 for 512 workers of 800 floats (about 45 rows of a
-// 400 K-word Zipf vocabulary), none for 8 workers and none on flat distributions.  Only for 16-byte columns, coherent
-// rows, and not in the parity mode.
-static const double W2B_HOT_LOAD = 6400.0;
-// legacy_u: the load rule of round 3 whatever the number of workers, which the sentence-resident kernel still uses to pick
-// its consensus rows (uavg_rank).
-// Round 4: per-XCD copies are a FULL-DEVICE mechanism.  Measured on the benchmarked regime (profiles/r04_sessions/): with
-// up to a few hundred workers the copies cost fidelity whatever their number and merge period (64 workers: 3-5 copies -2.5 %,
-// none +0.3 %; 256 workers: 16 copies -3.8 %, none +0.9 %) and buy nothing (the rows do not queue yet); on a full device
-// (1024 workers) the picture turns: without copies the hottest rows queue at their memory lines (13.4 M words/s against
-// 28.0 M) and 113 + 113 copies with the consensus rule are within 0.1-0.4 % of the reference's epoch loss.  So the automatic
-// choice gives copies only when the launch has at least W2B_FULL_DEVICE_WG_PER_CU workgroups per CU; below that every row
-// is shared by all workers as in the reference, and the context rows are updated by lossless adds (atomic_plan_u).
-static const int W2B_FULL_DEVICE_WG_PER_CU = 3;
-static const int W2B_HOT_PERIOD = 16;            // centre words between two merge events of a worker (xhot_prepare)
-static bool full_device(const w2b_trainer *t, long long workers) { return workers >= (long long)W2B_FULL_DEVICE_WG_PER_CU * t->num_cus; }
-// Round 5: BETWEEN the reference's own scale (256 threads: the most its bands exist for, and what -threads 0 stays at) and a full
-// device, explicit worker counts drifted on the benchmarked regime: +1.0 / +1.3 / +1.6 / +1.5 % of the reference's epoch loss
-// at 320 / 440 / 512 / 640 workers with every row shared.  Round 4 had measured "4 copies of v, merged every word" at -0.1 % for
-// 440 workers and not adopted it; round 5 measured the range (profiles/r05_sessions/r05q_mid_range.txt): -0.25 / -0.09 / -0.05 /
-// -0.45 % at 320 / 440 / 512 / 640, and on the held-out 60 M-token regime +0.18 -> -0.05 % (440) and +0.29 -> +0.03 % (600).  At
-// 767 workers it over-shoots (-1.5 % against +0.7 % shared), so the range ends at 2.5 workgroups per CU.  8 copies: -0.7 ... -1.2 %.
-static const int W2B_REFERENCE_SCALE = 256, W2B_MID_RANGE_COPIES_V = 4;
-static bool mid_range(const w2b_trainer *t, long long workers) { return workers > W2B_REFERENCE_SCALE && 2 * workers <= 5ll * t->num_cus; }
-
-static void xhot_plan(const w2b_trainer *t, long long workers, bool with_u, int *nu, int *nv, bool legacy_u) {
-  *nu = *nv = 0;
-  const int mem_mode = t->tune.mem_mode >= 0 ? t->tune.mem_mode : t->cfg.relaxed_coherence;
-  int wide = 0;
-  (void)w2b_block_threads(t->cfg.layer1_size, nullptr, &wide);
-  if (t->cfg.layer1_size % 4 != 0 || wide || mem_mode != 0 || t->cfg.exact_reduction) return;
-  const long long vmax = t->cfg.vocab_size - 1 < W2B_XHOT_MAX ? t->cfg.vocab_size - 1 : W2B_XHOT_MAX;
-  auto pick = [&](int explicit_n, const std::vector<double> &rate) -> int {
-    long long n = 0;
-    if (explicit_n >= 0) n = explicit_n;
-    else {
-      const int cap = t->tune.hot_cap < W2B_XHOT_MAX ? t->tune.hot_cap : W2B_XHOT_MAX;
-      while (n < (long long)rate.size() && n < cap && rate[(size_t)n] * (double)workers * t->cfg.layer1_size >= W2B_HOT_LOAD) n++;
-    }
-    return (int)(n < vmax ? n : (vmax > 0 ? vmax : 0));
-  };
-  // (legacy_u / !with_u: the sentence-resident kernel, an explicit choice, keeps the rule it was measured with)
-  const bool gated = with_u && !legacy_u && !full_device(t, workers);
-  *nv = (t->tune.hot_rows_v < 0 && gated) ? 0 : pick(t->tune.hot_rows_v, t->rate_v);
-  if (with_u) *nu = (t->tune.hot_rows_u < 0 && gated) ? 0 : pick(t->tune.hot_rows_u, t->rate_u);
-  if (gated && t->tune.hot_rows_v < 0 && t->tune.hot_rows_u < 0 && mid_range(t, workers)) {   // (see mid_range above)
-    const int n = pick(-1, t->rate_v);                   // never more rows than the load rule would take
-    *nv = n < W2B_MID_RANGE_COPIES_V ? n : W2B_MID_RANGE_COPIES_V;
-  }
-}
-
-// Rows 1..n (by count) whose updates are atomic adds at their master address (w2b_tuning.atomic_rank).  A load / modify /
-// store of a row is open for about 10 us on this machine (the rows of a chunk are loaded together and written after
-// their dot products), during which every other worker's update of the same row is lost; a row that is a target of
-// `rate` centre words is hit about 0.6 x workers x rate times per window.  Measured: on small
-// flat vocabularies, where that number is between a fraction and a few for EVERY row, atomic adds bring the epoch
-// losses of 64 ... 512 workers back to the reference's (planted corpus, 512 workers, first epoch: -1.1 % instead of
-// -31 %); on Zipf vocabularies they change nothing that matters (the rows that collide are the hot rows, which have
-// their own scheme, and summing the hundreds of stale gradients a hot row collects per window over-shoots) and cost
-// 20-30 % of the throughput.  Automatic therefore means: all rows when even the least frequent row collides
-// (0.6 x workers x rate >= W2B_ATOMIC_LOAD) and the tables are cache-sized, none otherwise; atomic_cap > 0 limits the
-// number of rows.
-static const double W2B_ATOMIC_LOAD = 0.25;
-// Is there a kernel that honours atomic ranks for this trainer?  Coherent rows, fast reduction, one thread per column; with
-// 16-byte columns only the workgroups of at most 256 threads have the ATOM instantiations (-size <= 1024; the row-group
-// kernel covers the same range).  Everywhere else the plans below return 0 -- for explicit ranks too -- so that
-// w2b_plan_rows / w2b_worker_kernel_info describe what runs (round 4 reported ranks that the kernels silently ignored).
-static bool atomics_supported(const w2b_trainer *t) {
-  int wide = 0, vec = 0;
-  const int threads = w2b_block_threads(t->cfg.layer1_size, &vec, &wide);
-  const int mem_mode = t->tune.mem_mode >= 0 ? t->tune.mem_mode : t->cfg.relaxed_coherence;
-  if (t->cfg.exact_reduction || wide || mem_mode != 0) return false;
-  if (vec == 4 && threads > 256) return false;
-  return true;
-}
-static int atomic_plan(const w2b_trainer *t, long long workers) {
-  if (!atomics_supported(t)) return 0;
-  const long long V = t->cfg.vocab_size;
-  long long n = 0;
-  if (t->tune.atomic_rank >= 0) n = t->tune.atomic_rank;
-  else if (!t->counts.empty() && t->counts_pw > 0 && t->counts_tot > 0) {
-    const double c = (double)t->counts[(size_t)(V - 1)];           // the least frequent row (counts are sorted)
-    const double rate = t->cfg.negative * pow(c, 0.75) / t->counts_pw + c / t->counts_tot;
-    // ... and the tables are small enough to live in the caches: atomic adds are executed by the memory system, and on
-    // tables that do not fit they cost a multiple of a store (uniform ids over 60 K words x 200 floats: 15 M words/s
-    // instead of 100 M).  8 MB per table covers the corpora where a flat small vocabulary occurs (planted: 1.7 MB).
-    const bool cacheable = (double)V * t->cfg.layer1_size * sizeof(float) <= 8.0e6;
-    if (cacheable && 0.6 * (double)workers * rate >= W2B_ATOMIC_LOAD) n = V - 1;
-    if (t->tune.atomic_cap > 0 && n > t->tune.atomic_cap) n = t->tune.atomic_cap;
-  }
-  return (int)(n < V - 1 ? n : V - 1);
-}
-
-// Context rows (u) updated with atomic adds.  The reference adds a centre word's accumulated error to every context row
-// with `u[c] += e[c]` on the row's CURRENT value (ref :500-502): nothing another thread added since the row was read for
-// the window average (ref :439) is lost -- the gradient is a whole centre word old, its application is not.  A GPU worker
-// that stores `value read in phase A + e` instead erases whatever the other workers added to the row during that centre
-// word.  How many others hold the row at that moment: workers x (uses of the row per centre word) -- a row is in a window
-// for the whole centre word, on the CPU as here, so this number is the reference's own at the same thread count.  Rows
-// for which it reaches W2B_ATOMIC_LOAD (a quarter of a worker) get the add; the vocabulary is sorted by count, so they
-// are a prefix.  Measured (profiles/r04_sessions/): the benchmarked regime at 64 / 256 / 1024 workers within 0.9 % of the
-// reference's epoch loss with lossless context rows and NO per-XCD copies, against +1.6 / +2.8 / +5.3 % with plain stores;
-// cost 1-2 % of the throughput in the transposed 16-byte-column form (add_col_contig).
-static int atomic_plan_u(const w2b_trainer *t, long long workers, int atomic_rank_v) {
-  const long long V = t->cfg.vocab_size;
-  if (!atomics_supported(t)) return 0;                             // (before an explicit rank: relaxed rows + agent-scope adds do not mix)
-  if (t->tune.atomic_rank_u > 0) return (int)(t->tune.atomic_rank_u < V - 1 ? t->tune.atomic_rank_u : V - 1);
-  if (t->tune.atomic_rank_u < 0) return 0;
-  if (t->tune.atomic_rank >= 0) return atomic_rank_v;            // an explicit atomic_rank speaks for both tables (round-3 meaning)
-  // full device with per-XCD copies: the rows that matter are at their copies, and adds for the rows below them cost 7 % of
-  // the throughput for nothing measurable (+0.37 % against -0.09 % of the reference's loss)
-  if (full_device(t, workers) && t->tune.hot_rows_u != 0) return atomic_rank_v;
-  long long n = atomic_rank_v;
-  if (!t->counts.empty() && t->counts_tot_kept > 0) {
-    const double st = (double)t->cfg.sample * (double)t->cfg.train_words;
-    auto kept = [&](double c) { return (t->cfg.sample > 0 && st > 0) ? (c < sqrt(c * st) + st ? c : sqrt(c * st) + st) : c; };
-    long long lo = 0, hi = V - 1;                                 // largest row whose rate still reaches the threshold
-    while (lo < hi) {
-      const long long mid = (lo + hi + 1) / 2;
-      const double rate = (t->cfg.window + 1) * kept((double)t->counts[(size_t)mid]) / t->counts_tot_kept;
-      if ((double)workers * rate >= W2B_ATOMIC_LOAD) lo = mid; else hi = mid - 1;
-    }
-    if (lo > n) n = lo;
-  }
-  return (int)(n < V - 1 ? n : V - 1);
-}
-
-// The row-group kernel (w2b_kernels_groups.hip; round 5) runs a worker as G row groups + a producer + an adder wavefront:
-// all targets of a centre word in flight at once, the scalar side one word ahead, the lossless adds to the frequent context
-// rows off the data wavefronts' path.  It implements the SHARED-ROW rules only (every row at its master address, context
-// rows 1..atomic_rank_u by lossless adds) -- what the library runs below a full device (xhot_plan) -- for 16-byte
-// columns up to -size 1024, window <= 16, negative + 1 <= 27/28, tables below 2 GiB.  plain_worker_kernel: 3 = wherever it
-// fits, 1 / 2 = never; 0 = automatic:
-//   * rows of at most W2B_GROUPS_AUTO_DIM floats (at -size 800 a row already fills four wavefronts, a worker is a 14-wavefront
-//     workgroup and its own latency, not the rows, bounds it: 14.7 M words/s at 256 workers where the plain kernel does 10 and
-//     a full device 26);
-//   * and only where the fidelity budget is not already thin.  With Hogwild rows what a kernel costs in epoch loss grows
-//     with its THROUGHPUT x the time a row is open (measured, profiles/r05_sessions/: at equal words/s the two kernels are
-//     equally far from the reference; the row-group kernel at equal worker counts is about twice as fast and 0.3 ... 0.8 %
-//     further off).  Two regimes sit at the 1.5 % floor with the plain kernel already: vocabularies so small and flat that
-//     every row collides (the quantity atomic_plan uses: 0.6 x workers x rate of the least frequent row, an eighth of
-//     W2B_ATOMIC_LOAD and more -- the planted corpus from 5 workers on), and shards shorter than the library's own guideline
-//     of W2B_WORDS_PER_WORKER_MIN words per worker and epoch (explicit -threads 256 on a 6-8 M-token corpus; the CLI warns
-//     there).  Both keep the plain kernel.
-static const int W2B_GROUPS_AUTO_DIM = 512;
-static const long long W2B_WORDS_PER_WORKER_MIN = 50000;
-static bool groups_plan(const w2b_trainer *t, long long workers) {
-  const int mode = t->cfg.plain_worker_kernel;
-  if (mode == 1 || mode == 2) return false;
-  if (mode == 0) {
-    if (t->cfg.layer1_size > W2B_GROUPS_AUTO_DIM) return false;
-    if (t->counts.empty() || t->counts_pw <= 0 || t->counts_tot <= 0) return false;      // (the rules below need the word counts)
-    const long long total = t->cfg.total_threads > 0 ? t->cfg.total_threads : workers;
-    if (t->cfg.train_words > 0 && t->cfg.train_words / (total > 0 ? total : 1) < W2B_WORDS_PER_WORKER_MIN) return false;
-    const double c = (double)t->counts[(size_t)(t->cfg.vocab_size - 1)];                   // the least frequent row (counts are sorted)
-    const double rate = t->cfg.negative * pow(c, 0.75) / t->counts_pw + c / t->counts_tot;
-    if (0.6 * (double)workers * rate >= W2B_ATOMIC_LOAD / 8) return false;
-  }
-  W2bParams probe = make_params(t);
-  int nu = 0, nv = 0;
-  xhot_plan(t, workers, true, &nu, &nv, false);
-  if (nu + nv > 0) return false;                       // per-XCD copies live in the plain kernel
-  probe.fresh_rank_u = t->tune.fresh_rank_u > 0 ? t->tune.fresh_rank_u : 0;
-  return w2b_groups_ok(probe);
-}
-
-// Rows 1..n of u that the row-group kernel reads at refreshed per-XCD copies (w2b_tuning.refresh_rows_u).  Measured
-// (profiles/r05_sessions/): what bounds the shared-row mode on a Zipf stream is neither the adds to the hottest context rows
-// nor their reads, but the two ON THE SAME LINES -- a read of a line that the memory side is adding to waits for the adds in
-// front of it (about 50 ns per operation on the hottest line, whatever the row length: 13-15 M words/s at -size 200 ... 1000).
-// With the reads of the 4 hottest rows moved to copies the -size 200 stream runs at 22 M words/s instead of 14 M at 256
-// workers.  The price is freshness: a copy lags its master row by a refresher sweep (a few us), which adds to the staleness
-// of exactly the rows that are updated most often -- heldout_zipf12 at 256 workers: -1.1 % of the reference's epoch loss
-// without copies, -1.35 % with 4, -2.7 % with 16, -3.9 ... -5.6 % with ~25.  So only the very hottest rows are taken: a row
-// whose load `workers x uses per centre word` reaches W2B_RC_LOAD -- 4-5 rows of a Zipf(1) vocabulary at 256 workers, 1 at
-// 64, none below 40 workers and none on flat vocabularies -- and only among the rows whose updates are lossless adds (a
-// stored `copy value + e` would lose every update since the last refresh).
-static const double W2B_RC_LOAD = 40.0;
-static int rc_plan(const w2b_trainer *t, long long workers, int atomic_rank_u) {
-  const long long V = t->cfg.vocab_size;
-  long long n = 0;
-  if (t->tune.refresh_rows_u < 0) return 0;
-  if (t->tune.refresh_rows_u > 0) n = t->tune.refresh_rows_u;
-  else if (!t->counts.empty() && t->counts_tot_kept > 0) {
-    const double st = (double)t->cfg.sample * (double)t->cfg.train_words;
-    auto kept = [&](double c) { return (t->cfg.sample > 0 && st > 0) ? (c < sqrt(c * st) + st ? c : sqrt(c * st) + st) : c; };
-    while (n < W2B_RC_MAX && n + 1 < V &&
-           (double)workers * (t->cfg.window + 1) * kept((double)t->counts[(size_t)(n + 1)]) / t->counts_tot_kept >= W2B_RC_LOAD) n++;
-  }
-  if (n > W2B_RC_MAX) n = W2B_RC_MAX;
-  if (n > atomic_rank_u) n = atomic_rank_u;
-  if (n > V - 1) n = V - 1;
-  return (int)(n > 0 ? n : 0);
-}
-
-// buffer, flags and counters of the refreshed copies for one launch of the row-group kernel
-static int rc_prepare(w2b_trainer *t, W2bParams &p, long long workers) {
-  p.rc_rows = rc_plan(t, workers, p.atomic_rank_u);
-  p.rc = nullptr;
-  p.rc_flags = nullptr;
-  if (p.rc_rows <= 0) { p.rc_rows = 0; return W2B_OK; }
-  const size_t need = 64 + (size_t)W2B_NXCD * W2B_RC_MAX * t->cfg.layer1_size;     // 64 ints of flags, then the copies
-  if (need > t->rc_floats) {
-    HIPCHK(hipStreamSynchronize(t->stream));
-    if (t->rc) HIPCHK(hipFree(t->rc));
-    t->rc = nullptr;
-    t->rc_floats = 0;
-    HIPCHK(hipMalloc(&t->rc, sizeof(float) * need));
-    t->rc_floats = need;
-  }
+// ---- applying a launch plan (w2b_plan.h decides; nothing below does): buffers large enough, cleared / folded as the launch needs
+// buffer, flags and counters of the refreshed copies (W2bLaunchPlan::refresh_rows_u) for one launch of the row-group kernel
+static int rc_prepare(w2b_trainer *t, W2bParams &p, const W2bLaunchPlan &lp) {
+  if (lp.refresh_rows_u <= 0) return W2B_OK;
+  if (int rc = grow(t, &t->rc, &t->rc_floats, 64 + (size_t)W2B_NXCD * W2B_RC_MAX * t->in.cfg.layer1_size)) return rc;   // 64 ints of flags, then the copies
   if (!t->rc_stream) {
     HIPCHK(hipStreamCreateWithFlags(&t->rc_stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&t->rc_go, hipEventDisableTiming));
@@ -1010,73 +690,29 @@ static int rc_prepare(w2b_trainer *t, W2bParams &p, long long workers) {
   }
   HIPCHK(hipMemsetAsync(t->rc, 0, 64 * sizeof(int), t->stream));                    // claims and alive flags of this launch
   HIPCHK(hipMemsetAsync(&t->shared->launch_done, 0, sizeof(int), t->stream));
+  p.rc_rows = lp.refresh_rows_u;
   p.rc_flags = reinterpret_cast<int *>(t->rc);
   p.rc = t->rc + 64;
   return W2B_OK;
 }
 
-// scratch rows of process_word_wide for `workgroups` workgroups (grown on demand)
+// scratch rows of process_word_wide for `workgroups` workgroups
 static int wide_prepare(w2b_trainer *t, W2bParams &p, long long workgroups) {
   if (!p.wide) return W2B_OK;
-  const size_t need = (size_t)workgroups * 2 * t->cfg.layer1_size;
-  if (need > t->wide_floats) {
-    HIPCHK(hipStreamSynchronize(t->stream));
-    if (t->wide_scratch) HIPCHK(hipFree(t->wide_scratch));
-    t->wide_scratch = nullptr;
-    t->wide_floats = 0;
-    HIPCHK(hipMalloc(&t->wide_scratch, sizeof(float) * need));
-    t->wide_floats = need;
-  }
+  if (int rc = grow(t, &t->wide_scratch, &t->wide_floats, (size_t)workgroups * 2 * t->in.cfg.layer1_size)) return rc;
   p.wide_scratch = t->wide_scratch;
   return W2B_OK;
 }
 
-// Buffer + parameters of the XCD-shared hot rows for one launch; folds the copies into the masters first when the
-// layout changed or somebody wrote the master rows since the last launch.
-static int xhot_prepare(w2b_trainer *t, W2bParams &p, long long workers, bool with_u) {
-  int nu = 0, nv = 0;
-  xhot_plan(t, workers, with_u, &nu, &nv, false);
-  p.xhot = nullptr;
-  p.xhot_u = nu;
-  p.xhot_v = nv;
-  p.atomic_rank = atomic_plan(t, workers);
-  p.atomic_rank_u = with_u ? atomic_plan_u(t, workers, p.atomic_rank) : 0;   // (the sentence-resident kernel keeps its context rows in LDS)
-  p.fresh_rank_u = t->tune.fresh_rank_u > 0 ? t->tune.fresh_rank_u : 0;
-  if (!with_u) {          // sentence-resident kernel: its context rows live in LDS; the most frequent ones (the rows that
-    int un = 0, vn = 0;   // would be hot rows of u) are merged by consensus and refreshed (w2b_kernels_resident.hip)
-    xhot_plan(t, workers, true, &un, &vn, true);
-    p.uavg_rank = un;
-  }
+// Buffer of the XCD-shared hot rows for one launch; folds the copies into the masters first when the layout changed or
+// somebody wrote the master rows since the last launch.
+static int xhot_prepare(w2b_trainer *t, W2bParams &p) {
+  const int nu = p.xhot_u, nv = p.xhot_v;
   if (nu + nv == 0) return W2B_OK;
-  const size_t need = (size_t)W2B_NXCD * ((size_t)2 * (nu + nv) * t->cfg.layer1_size + (size_t)(nu + nv) * W2B_MAXW);
+  const size_t need = (size_t)W2B_NXCD * ((size_t)2 * (nu + nv) * t->in.cfg.layer1_size + (size_t)(nu + nv) * W2B_MAXW);
   bool fresh = (nu != t->xhot_nu || nv != t->xhot_nv);
-  if (need > t->xhot_floats) {
-    HIPCHK(hipStreamSynchronize(t->stream));
-    if (t->xhot) HIPCHK(hipFree(t->xhot));
-    t->xhot = nullptr;
-    t->xhot_floats = 0;
-    HIPCHK(hipMalloc(&t->xhot, sizeof(float) * need));
-    t->xhot_floats = need;
-    fresh = true;
-  }
+  if (int rc = grow(t, &t->xhot, &t->xhot_floats, need, &fresh)) return rc;
   p.xhot = t->xhot;
-  const long long per_xcd = workers / W2B_NXCD > 0 ? workers / W2B_NXCD : 1;
-  const int most = nu > nv ? nu : nv;
-  p.xhot_m = (int)((most + per_xcd - 1) / per_xcd);       // every copy of an XCD is merged about once per hot_period steps
-  // Merge period: a worker merges every W2B_HOT_PERIOD = 16 centre words.  Round 4 chose 32 on the 22 M-token proxy of the
-  // benchmarked regime (+0.06 % of the reference's epoch loss at 1024 workers, against +0.9 % at 8).  Round 5 recorded the
-  // reference on BASELINE configs[1] literally (100 M tokens) and measured both files (profiles/r05_sessions/r05n_balance.txt):
-  // period 32: -1.16 ... -1.38 % (literal) / +0.27 % (proxy); 16: -0.70 % / +0.67 %; 8: +0.32 % / +1.11 %; 64: -1.10 % / +0.47 %.
-  // The longer the stream the further stale copies pull the epoch loss down, so the period that centres BOTH is the default;
-  // it costs ~2 % of the headline throughput against 32.
-  if (t->tune.hot_period <= 0) p.hot_period = full_device(t, workers) ? W2B_HOT_PERIOD : 1;   // (mid range: every word)
-  // The sentence-resident kernel (an explicit choice; its context rows are private in LDS, only target rows have copies) keeps
-  // round 4's period of 32.  Round 5's line above gave it the mid-range value -- a resident launch has 2 workgroups per CU, never
-  // "a full device" by the 3-per-CU rule -- i.e. a merge after EVERY word: that, not the move from 32 to 16, is what took the
-  // cfg5 shape's sentence-resident leg from 0.889 to 0.776 of the roofline between the round-4 and round-5 driver runs (same-box
-  // A/B in round 6: 36.9-37.2 M words/s as shipped in round 5, 41.4 M with 32, 38.4 M for the round-4 library;
-  // profiles/r06_sessions/r06b_cfg5_ab.txt, r06c_cfg5_resident_period.txt).
-  if (t->tune.hot_period <= 0 && !with_u) p.hot_period = 2 * W2B_HOT_PERIOD;
   if (fresh) {         // copy == entry (== 0) everywhere: the fold below adopts the master rows
     HIPCHK(hipMemsetAsync(t->xhot, 0, sizeof(float) * need, t->stream));
     t->xhot_nu = nu;
@@ -1088,153 +724,57 @@ static int xhot_prepare(w2b_trainer *t, W2bParams &p, long long workers, bool wi
   return W2B_OK;
 }
 
-// Fewest words of an epoch a worker should have when the library picks the number of workers: alpha is re-computed per
-// worker only every 10000 of its own words (ref :379-393), so short shards coarsen the schedule.  20000 in rounds 2-3; the
-// text8-sized corpus then ran 850 workers and ended its later epochs 2 % off the reference whatever the row-update
-// scheme (256 workers: 0.5 %), i.e. the cap, not a race, was what the gate saw.
+// as many workers as the device holds at once (the occupancy of the kernel that would run -- sentence-resident or plain), capped
+// by what the corpus supports (w2b_plan_suggested_workers)
 extern "C" int w2b_suggested_threads(w2b_trainer *t, int32_t *out) {
   NEED(t);
   if (!out) return fail(W2B_EINVAL, "w2b_suggested_threads: null");
-  const W2bParams p = make_params(t);
-  // (judged for a full device: the atomic plan depends on the number of workers, which is what is being asked for)
-  const int radius = effective_radius(t, 2ll * t->num_cus > t->cfg.num_threads ? 2ll * t->num_cus : t->cfg.num_threads);
-  const int per_cu = radius >= 0 ? w2b_resident_per_cu(p, radius, t->cfg.compute_loss != 0)
-                                 : w2b_workers_per_cu(p, t->cfg.compute_loss != 0);
-  long long n = (long long)per_cu * t->num_cus;
-  // A worker adjusts alpha only after >10000 of its own words (ref :379-393): with shards shorter than that no worker
-  // ever does and the whole epoch runs at the starting alpha.  Never suggest more workers than leave every shard
-  // at least two such periods long (train_words here is the job's global number; 0 = unknown, no cap).
-  if (t->cfg.train_words > 0) {
-    const long long total = t->cfg.total_threads > 0 && t->cfg.num_threads > 0
-                                ? (long long)t->cfg.total_threads / t->cfg.num_threads : 1;   // replicas
-    const long long cap = t->cfg.train_words / (W2B_WORDS_PER_WORKER_MIN * (total > 0 ? total : 1));
-    if (n > cap) n = cap > 1 ? cap : 1;
-  }
-  // Not enough words for a full device.  Round 4 stopped at 256 workers here, the reference's own scale: beyond it the
-  // shared-row mode drifted (+1.3 ... +1.5 % at 440 workers on the benchmarked regime).  Round 5:
-  //   * rows of at most 512 floats stay at 256 workers -- the row-group kernel runs there (22 M words/s at -size 200; with the
-  //     mid-range copies the plain kernel would run instead, at half of that);
-  //   * longer rows go on to the mid range (257 .. 640 workers, four target rows with copies merged every word: within 0.5 %
-  //     of the reference on the benchmarked regime and 35-45 % faster than 256 workers: 13.5 M words/s at 440, 14.3 M at 512-640
-  //     on the 22 M-token headline-shape file, where 256 workers run 9.9 M).
-  if (radius < 0 && n < (long long)W2B_FULL_DEVICE_WG_PER_CU * t->num_cus && n > W2B_REFERENCE_SCALE) {
-    const long long mid_top = 5ll * t->num_cus / 2;                      // where mid_range() ends
-    const bool short_rows = t->cfg.plain_worker_kernel != 1 && t->cfg.layer1_size <= W2B_GROUPS_AUTO_DIM;
-    n = short_rows ? W2B_REFERENCE_SCALE : (n < mid_top ? n : mid_top);
-    int nu = 0, nv = 0;
-    xhot_plan(t, n, true, &nu, &nv, false);
-    if (nv == 0) n = W2B_REFERENCE_SCALE;                                 // (no copies for this trainer -- relaxed rows, flat counts, ...: the reference's scale)
-  }
-  *out = (int32_t)n;
+  const W2bLaunchPlan lp = w2b_plan_launch(t->in, w2b_plan_probe_workers(t->in));
+  W2bParams p{};
+  w2b_shape_params(p, t->in.cfg, t->in.tune);
+  const int per_cu = lp.radius >= 0 ? w2b_resident_per_cu(p, lp.radius, t->in.cfg.compute_loss != 0)
+                                    : w2b_workers_per_cu(p, t->in.cfg.compute_loss != 0);
+  *out = (int32_t)w2b_plan_suggested_workers(t->in, lp, (long long)per_cu * t->in.num_cus);
   return W2B_OK;
 }
 
 extern "C" int w2b_worker_kernel_info(w2b_trainer *t, int32_t *resident, int32_t *radius, int32_t *column_bytes,
                                       int32_t *workgroups_per_cu, int32_t *hot_rows) {
   NEED(t);
-  const W2bParams p = make_params(t);
-  const int r = effective_radius(t, t->cfg.num_threads);
-  int hu = 0, hot = 0;
-  xhot_plan(t, t->cfg.num_threads, r < 0, &hu, &hot, false);
-  const bool groups = r < 0 && groups_plan(t, t->cfg.num_threads);
-  if (resident) *resident = r >= 0 ? 1 : (groups ? 2 : 0);      // 0 plain, 1 sentence-resident, 2 row groups
-  if (radius) *radius = r;
-  if (hot_rows) *hot_rows = hot;
+  const W2bLaunchPlan lp = w2b_plan_launch(t->in, t->in.cfg.num_threads);
+  W2bParams p{};
+  w2b_shape_params(p, t->in.cfg, t->in.tune);
+  const bool loss = t->in.cfg.compute_loss != 0;
+  if (resident) *resident = lp.kernel;      // 0 plain, 1 sentence-resident, 2 row groups
+  if (radius) *radius = lp.radius;
+  if (hot_rows) *hot_rows = lp.copies_v;
   int vec = 0;
-  (void)w2b_block_threads(t->cfg.layer1_size, &vec);
-  if (column_bytes) *column_bytes = 4 * (r >= 0 ? 4 : vec);
+  (void)w2b_block_threads(t->in.cfg.layer1_size, &vec);
+  if (column_bytes) *column_bytes = 4 * (lp.radius >= 0 ? 4 : vec);
   if (workgroups_per_cu)
-    *workgroups_per_cu = r >= 0 ? w2b_resident_per_cu(p, r, t->cfg.compute_loss != 0)
-                                : (groups ? w2b_groups_per_cu(p, t->cfg.compute_loss != 0) : w2b_workers_per_cu(p, t->cfg.compute_loss != 0));
+    *workgroups_per_cu = lp.kernel == W2B_KERNEL_RESIDENT ? w2b_resident_per_cu(p, lp.radius, loss)
+                                                          : (lp.kernel == W2B_KERNEL_GROUPS ? w2b_groups_per_cu(p, loss) : w2b_workers_per_cu(p, loss));
   return W2B_OK;
-}
-
-// The row rules of a launch without a device (pure host arithmetic on the word counts): what w2b_train_step would decide for
-// `workers` concurrent workers of the plain kernel on a GPU with `num_cus` compute units.
-static int concurrency_plan(const w2b_trainer *t, int workers);
-
-extern "C" int w2b_plan_rows(const w2b_config *cfg, const w2b_tuning *tune, const int64_t *cn, int32_t num_cus, int32_t workers,
-                             w2b_row_plan *out) {
-  if (!cfg || !cn || !out || num_cus < 1 || workers < 1 || cfg->vocab_size < 2 || cfg->layer1_size < 1)
-    return fail(W2B_EINVAL, "w2b_plan_rows: bad argument");
-  if (tune && tune->struct_size != (int32_t)sizeof(w2b_tuning)) return fail(W2B_EINVAL, "w2b_plan_rows: struct_size of w2b_tuning");
-  w2b_trainer t;                               // a host-side stand-in: no device member is touched by the plan functions
-  t.cfg = *cfg;
-  t.num_cus = num_cus;
-  t.tune = tune ? *tune : default_tuning();
-  std::vector<float> keep((size_t)cfg->vocab_size, 1.f);
-  if (cfg->sample > 0) w2b_build_keep_prob(cn, cfg->vocab_size, cfg->sample, cfg->train_words, keep.data());
-  word_rates(&t, cn, keep);
-  int nu = 0, nv = 0;
-  xhot_plan(&t, workers, true, &nu, &nv, false);
-  out->copies_u = nu;
-  out->copies_v = nv;
-  out->atomic_rank_v = atomic_plan(&t, workers);
-  out->atomic_rank_u = atomic_plan_u(&t, workers, out->atomic_rank_v);
-  out->full_device = full_device(&t, workers) ? 1 : 0;
-  out->merge_period = t.tune.hot_period > 0 ? t.tune.hot_period : (full_device(&t, workers) ? W2B_HOT_PERIOD : 1);
-  t.cfg.num_threads = workers;
-  t.table_elems = (long long)cfg->vocab_size * cfg->layer1_size;
-  out->row_group_kernel = groups_plan(&t, workers) ? 1 : 0;
-  out->refresh_rows_u = out->row_group_kernel ? rc_plan(&t, workers, out->atomic_rank_u) : 0;
-  out->concurrent_workers = out->row_group_kernel ? workers : concurrency_plan(&t, workers);
-  return W2B_OK;
-}
-
-// How many workers of the plain kernel run AT ONCE (w2b_tuning.concurrent_workers; 0 = automatic).  A worker is a shard and an LCG
-// stream; how many of them are in flight together is an execution detail -- the reference's own threads are scheduled by the OS,
-// and a GPU launch with more workers than resident workgroups already runs them in rounds.  Automatic = all of them, except on
-// vocabularies so small and flat that every row collides (atomic_plan: every row gets lossless adds).  There what decides the
-// epoch loss is concurrency x the time a row is open, and a GPU workgroup has a chunk of 13 target rows open for ~10 us where the
-// reference's thread has one row open for ~1.5 us: 64 workers at once over-shoot (planted corpus at the configs[2] shape: -1.0 ...
-// -2.8 % over five epochs, the ONE stated exception of the 1.5 % floor until round 6), a part of them at a time do not.
-// Measured (planted corpus, configs[2] shape, 64 workers, five epochs; profiles/r06_sessions/r06h_planted_concurrency.txt, r06i):
-//   at once   epoch losses vs the reference's 64-thread band          accuracy (band 16.9-17.8)
-//      64     -0.7 / -1.2 / -1.4 / -2.0 / -2.5 %                       19.9      (rounds 3-5: the exception)
-//      32     -0.1 / +0.2 / -0.6 / -1.4 / -1.2 %                       15.5
-//      16     +0.3 / +0.4 / +0.1 / -0.3 / +0.1 %                       14.2
-//       8     +0.5 / +1.1 / +0.6 / +0.5 / +0.5 %                       14.1
-// The losses want few workers at once, the accuracy (which in the reference itself rises from 9.5 at 8 threads to 17.3 at 64) wants
-// many: 3/8 of the workers, at least 16, keeps both inside their gates.
-static const int W2B_FLAT_CONCURRENCY_NUM = 3, W2B_FLAT_CONCURRENCY_DEN = 8, W2B_FLAT_CONCURRENCY_MIN = 16;
-static int concurrency_plan(const w2b_trainer *t, int workers) {
-  int c = workers;
-  if (t->tune.concurrent_workers > 0) c = t->tune.concurrent_workers;
-  else if (workers > W2B_FLAT_CONCURRENCY_MIN && atomic_plan(t, workers) >= t->cfg.vocab_size - 1 && t->tune.atomic_rank < 0) {
-    c = workers * W2B_FLAT_CONCURRENCY_NUM / W2B_FLAT_CONCURRENCY_DEN;
-    if (c < W2B_FLAT_CONCURRENCY_MIN) c = W2B_FLAT_CONCURRENCY_MIN;
-  }
-  if (c > workers) c = workers;
-  return c > 0 ? c : 1;
 }
 
 extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
   NEED(t);
   if (!t->corpus || !t->shards_set) return fail(W2B_ESTATE, "w2b_train_step: corpus/shards not set");
   if (max_positions <= 0) return fail(W2B_EINVAL, "w2b_train_step: max_positions must be positive");
-  const int radius = effective_radius(t, t->cfg.num_threads);
-  if (radius >= 0) {                       // scratch rows of the sentence-resident kernel (grown on demand)
-    const size_t need = (size_t)t->cfg.num_threads * (size_t)w2b_resident_scratch_rows(radius) * t->cfg.layer1_size;
-    if (need > t->entry_floats) {
-      HIPCHK(hipStreamSynchronize(t->stream));
-      if (t->entry) HIPCHK(hipFree(t->entry));
-      t->entry = nullptr;
-      t->entry_floats = 0;
-      HIPCHK(hipMalloc(&t->entry, sizeof(float) * need));
-      t->entry_floats = need;
-    }
-  }
-  W2bParams p = make_params(t);
-  // per-XCD copies of the hottest rows: v only for the sentence-resident kernel (its context rows live in LDS)
-  if (int rc = xhot_prepare(t, p, t->cfg.num_threads, radius < 0)) return rc;
-  if (int rc = wide_prepare(t, p, t->cfg.num_threads)) return rc;
+  const W2bLaunchPlan lp = w2b_plan_launch(t->in, t->in.cfg.num_threads);
+  if (lp.kernel == W2B_KERNEL_RESIDENT)    // scratch rows of the sentence-resident kernel
+    if (int rc = grow(t, &t->entry, &t->entry_floats,
+                      (size_t)t->in.cfg.num_threads * (size_t)w2b_resident_scratch_rows(lp.radius) * t->in.cfg.layer1_size)) return rc;
+  W2bParams p = make_params(t, lp);
+  if (int rc = xhot_prepare(t, p)) return rc;
+  if (int rc = wide_prepare(t, p, t->in.cfg.num_threads)) return rc;
 
-  t->x_words += (long long)max_positions * t->cfg.num_threads;
-  t->x_words_full += (long long)max_positions * t->cfg.num_threads;
+  t->x_words += (long long)max_positions * t->in.cfg.num_threads;
+  t->x_words_full += (long long)max_positions * t->in.cfg.num_threads;
   HIPCHK(timing_begin(t));
-  if (radius >= 0) HIPCHK(w2b_launch_resident(p, max_positions, radius, t->cfg.compute_loss != 0, t->stream, t->debug));
-  else if (groups_plan(t, t->cfg.num_threads) && w2b_groups_ok(p)) {
-    if (int rc = rc_prepare(t, p, t->cfg.num_threads)) return rc;
+  if (lp.kernel == W2B_KERNEL_RESIDENT) HIPCHK(w2b_launch_resident(p, max_positions, lp.radius, t->in.cfg.compute_loss != 0, t->stream, t->debug));
+  else if (lp.kernel == W2B_KERNEL_GROUPS) {
+    if (int rc = rc_prepare(t, p, lp)) return rc;
     // The refresher runs beside the launch on a stream of its own and ends when the workers have.  Order (advisor, round 5):
     // rc_go (flags and counter of this launch cleared) -> the WORKERS on the training stream -> the refresher on its stream,
     // waiting for rc_go only.  Wherever the two kernels cannot run side by side (streams sharing a hardware queue, serialised
@@ -1242,7 +782,7 @@ extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
     // and exits -- round 5 launched it first, where it would have spun until its time-out with the workers queued behind it.
     // A failed worker launch returns before the refresher is enqueued.
     if (p.rc_rows > 0) HIPCHK(hipEventRecord(t->rc_go, t->stream));
-    HIPCHK(w2b_launch_groups(p, max_positions, t->cfg.compute_loss != 0, t->stream));
+    HIPCHK(w2b_launch_groups(p, max_positions, t->in.cfg.compute_loss != 0, t->stream));
     if (p.rc_rows > 0) {
       HIPCHK(hipStreamWaitEvent(t->rc_stream, t->rc_go, 0));
       HIPCHK(w2b_launch_refresher(p, t->rc_stream));
@@ -1250,14 +790,14 @@ extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
     }
   }
   else {
-    // plain kernel: all workers at once, or -- w2b_tuning.concurrent_workers / concurrency_plan -- in slices of that many, one
-    // slice after the other on the stream (every worker still advances by max_positions per call)
-    const int conc = concurrency_plan(t, t->cfg.num_threads);
+    // plain kernel: all workers at once, or -- W2bLaunchPlan::concurrent_workers -- in slices of that many, one slice after
+    // the other on the stream (every worker still advances by max_positions per call)
+    const int conc = lp.concurrent_workers;
     W2bParams q = p;
-    for (int base = 0; base < t->cfg.num_threads; base += conc) {
+    for (int base = 0; base < t->in.cfg.num_threads; base += conc) {
       q.worker_base = base;
-      q.num_threads = t->cfg.num_threads;
-      HIPCHK(w2b_launch_workers(q, max_positions, t->cfg.compute_loss != 0, t->stream, base + conc < t->cfg.num_threads ? conc : t->cfg.num_threads - base));
+      q.num_threads = t->in.cfg.num_threads;
+      HIPCHK(w2b_launch_workers(q, max_positions, t->in.cfg.compute_loss != 0, t->stream, base + conc < t->in.cfg.num_threads ? conc : t->in.cfg.num_threads - base));
     }
   }
   HIPCHK(timing_end(t));
@@ -1283,7 +823,7 @@ extern "C" int w2b_epoch_poll(w2b_trainer *t, int32_t lag, int32_t *finished, in
   if (t->launches - lag <= 0) {              // nothing launched that far back yet
     if (finished) *finished = 0;
     if (wca) *wca = 0;
-    if (alpha) *alpha = t->cfg.alpha;
+    if (alpha) *alpha = t->in.cfg.alpha;
     if (loss_sum) *loss_sum = 0;
     return W2B_OK;
   }
@@ -1292,7 +832,7 @@ extern "C" int w2b_epoch_poll(w2b_trainer *t, int32_t lag, int32_t *finished, in
   const W2bShared &sh = t->poll_host[slot];
   if (sh.corpus_overrun)
     return fail(W2B_ESTATE, "a worker reached the end of its corpus slice before its quota (w2b_set_corpus_slice: slice too short)");
-  if (finished) *finished = (sh.workers_done >= t->cfg.num_threads) ? 1 : 0;
+  if (finished) *finished = (sh.workers_done >= t->in.cfg.num_threads) ? 1 : 0;
   if (wca) *wca = (int64_t)sh.word_count_actual;
   if (alpha) *alpha = sh.alpha;
   if (loss_sum) *loss_sum = sh.loss_epoch;
@@ -1308,11 +848,11 @@ extern "C" int w2b_epoch_status(w2b_trainer *t, int32_t *finished, int64_t *wca,
   HIPCHK(hipMemcpy(&sh, t->shared, sizeof sh, hipMemcpyDeviceToHost));
   if (sh.corpus_overrun)
     return fail(W2B_ESTATE, "a worker reached the end of its corpus slice before its quota (w2b_set_corpus_slice: slice too short)");
-  if (finished) *finished = (sh.workers_done >= t->cfg.num_threads) ? 1 : 0;
+  if (finished) *finished = (sh.workers_done >= t->in.cfg.num_threads) ? 1 : 0;
   if (wca) *wca = (int64_t)sh.word_count_actual;
   if (alpha) *alpha = sh.alpha;
   if (loss_sum) {
-    const int nw = t->cfg.num_threads;
+    const int nw = t->in.cfg.num_threads;
     std::vector<double> w((size_t)nw);              // only the 8-byte loss field of every worker travels
     HIPCHK(hipMemcpy2D(w.data(), sizeof(double), &t->workers[0].loss, sizeof(W2bWorker), sizeof(double), nw,
                        hipMemcpyDeviceToHost));
@@ -1327,36 +867,27 @@ extern "C" int w2b_epoch_status(w2b_trainer *t, int32_t *finished, int64_t *wca,
 extern "C" int w2b_train_tuples_device(w2b_trainer *t, int64_t n, const void *center, const void *ctx_off,
                                        const void *ctx, const void *neg, float alpha, int32_t grid) {
   NEED(t);
-  if (n < 0 || !center || !ctx_off || !ctx || (!neg && t->cfg.negative > 0))
+  if (n < 0 || !center || !ctx_off || !ctx || (!neg && t->in.cfg.negative > 0))
     return fail(W2B_EINVAL, "w2b_train_tuples_device: bad argument");
   if (n == 0) return W2B_OK;
-  W2bParams p = make_params(t);
+  // the plain kernel's row rules (per-XCD copies of the hottest rows of both tables, ...); the load estimate uses the
+  // workgroups that will run
+  long long wgs = grid > 0 ? grid : (long long)(t->in.tune.grid_per_cu > 0 ? t->in.tune.grid_per_cu : 4) * t->in.num_cus;
+  if (wgs > n) wgs = n;
+  W2bParams p = make_params(t, w2b_plan_launch(t->in, wgs, true));
   {
-    // per-XCD copies of the hottest rows of both tables; the load estimate uses the workgroups that will run
-    long long wgs = grid > 0 ? grid : (long long)(t->tune.grid_per_cu > 0 ? t->tune.grid_per_cu : 4) * t->num_cus;
-    if (wgs > n) wgs = n;
-    if (int rc = xhot_prepare(t, p, wgs, true)) return rc;
+    if (int rc = xhot_prepare(t, p)) return rc;
     if (p.wide) {                          // (an explicit grid: the scratch rows are per workgroup)
-      if (grid <= 0) grid = (int32_t)(n < 2ll * t->num_cus ? n : 2ll * t->num_cus);
+      if (grid <= 0) grid = (int32_t)(n < 2ll * t->in.num_cus ? n : 2ll * t->in.num_cus);
       if (int rc = wide_prepare(t, p, grid)) return rc;
     }
   }
   HIPCHK(timing_begin(t));
   HIPCHK(w2b_launch_tuples(p, n, (const int32_t *)center, (const int32_t *)ctx_off, (const int32_t *)ctx,
-                           (const int32_t *)neg, alpha, grid > 0 ? grid : 0, t->num_cus, t->tune.grid_per_cu,
-                           t->cfg.compute_loss != 0, t->stream));
+                           (const int32_t *)neg, alpha, grid > 0 ? grid : 0, t->in.num_cus, t->in.tune.grid_per_cu,
+                           t->in.cfg.compute_loss != 0, t->stream));
   HIPCHK(timing_end(t));
   HIPCHK(w2b_launch_xhot_fold(p, t->stream));
-  return W2B_OK;
-}
-
-static int grow(int32_t **p, size_t *cap, size_t need) {
-  if (need <= *cap) return W2B_OK;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIPCHK(hipMalloc(p, sizeof(int32_t) * need));
-  *cap = need;
   return W2B_OK;
 }
 
@@ -1364,14 +895,14 @@ extern "C" int w2b_train_tuples(w2b_trainer *t, int64_t n, const int32_t *center
                                 const int32_t *ctx, const int32_t *neg, float alpha, int32_t serial,
                                 double *loss_out) {
   NEED(t);
-  if (n < 0 || !center || !ctx_off || !ctx || (!neg && t->cfg.negative > 0))
+  if (n < 0 || !center || !ctx_off || !ctx || (!neg && t->in.cfg.negative > 0))
     return fail(W2B_EINVAL, "w2b_train_tuples: bad argument");
-  const int K = t->cfg.negative;
-  const int64_t V = t->cfg.vocab_size;
+  const int K = t->in.cfg.negative;
+  const int64_t V = t->in.cfg.vocab_size;
   // validate ids on the host: a bad row index would be an out-of-bounds device access
   for (int64_t i = 0; i < n; i++) {
     if (center[i] < 0 || center[i] >= V) return fail(W2B_EINVAL, "w2b_train_tuples: centre id out of range");
-    if (ctx_off[i + 1] < ctx_off[i] || ctx_off[i + 1] - ctx_off[i] > 2 * t->cfg.window)
+    if (ctx_off[i + 1] < ctx_off[i] || ctx_off[i + 1] - ctx_off[i] > 2 * t->in.cfg.window)
       return fail(W2B_EINVAL, "w2b_train_tuples: context list longer than 2*window or CSR not monotone");
     for (int j = 0; j < K; j++)
       if (neg[i * K + j] >= V) return fail(W2B_EINVAL, "w2b_train_tuples: negative id out of range");
@@ -1385,23 +916,23 @@ extern "C" int w2b_train_tuples(w2b_trainer *t, int64_t n, const int32_t *center
     return W2B_OK;
   }
   int rc;
-  if ((rc = grow(&t->st_center, &t->cap_center, n))) return rc;
-  if ((rc = grow(&t->st_off, &t->cap_off, n + 1))) return rc;
-  if ((rc = grow(&t->st_ctx, &t->cap_ctx, nctx > 0 ? nctx : 1))) return rc;
-  if ((rc = grow(&t->st_neg, &t->cap_neg, (size_t)n * (K > 0 ? K : 1)))) return rc;
+  if ((rc = grow(t, &t->st_center, &t->cap_center, n))) return rc;
+  if ((rc = grow(t, &t->st_off, &t->cap_off, n + 1))) return rc;
+  if ((rc = grow(t, &t->st_ctx, &t->cap_ctx, nctx > 0 ? nctx : 1))) return rc;
+  if ((rc = grow(t, &t->st_neg, &t->cap_neg, (size_t)n * (K > 0 ? K : 1)))) return rc;
   HIPCHK(hipMemcpyAsync(t->st_center, center, sizeof(int32_t) * n, hipMemcpyHostToDevice, t->stream));
   HIPCHK(hipMemcpyAsync(t->st_off, ctx_off, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, t->stream));
   if (nctx) HIPCHK(hipMemcpyAsync(t->st_ctx, ctx, sizeof(int32_t) * nctx, hipMemcpyHostToDevice, t->stream));
   if (K) HIPCHK(hipMemcpyAsync(t->st_neg, neg, sizeof(int32_t) * n * K, hipMemcpyHostToDevice, t->stream));
   double zero = 0;
-  if (t->cfg.compute_loss)
+  if (t->in.cfg.compute_loss)
     HIPCHK(hipMemcpyAsync(&t->shared->loss_tuples, &zero, sizeof zero, hipMemcpyHostToDevice, t->stream));
   rc = w2b_train_tuples_device(t, n, t->st_center, t->st_off, t->st_ctx, t->st_neg, alpha, serial ? 1 : 0);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(t->stream));
   if (loss_out) {
     *loss_out = 0;
-    if (t->cfg.compute_loss)
+    if (t->in.cfg.compute_loss)
       HIPCHK(hipMemcpy(loss_out, &t->shared->loss_tuples, sizeof(double), hipMemcpyDeviceToHost));
   }
   return W2B_OK;
@@ -1447,20 +978,18 @@ static void xchg_teardown(w2b_trainer *t) {
   t->base = nullptr;
 }
 
-// Expected updates of every row of [u || v] per trained centre word, from the word counts (what word_rates computes for the
+// Expected updates of every row of [u || v] per trained centre word, from the word counts (what w2b_plan_set_counts computes for the
 // leading rows, for all of them): a context row (u) is updated once per window it is in -- window + 1 windows per kept
 // occurrence on average --, a target row (v) once per draw from the unigram table (ref :112-128, 455-458: raw
 // counts; row 0 is remapped, never drawn) and once as the centre word.  "Kept": what survives sub-sampling (ref :403-406).
 static int xchg_upload_rates(w2b_trainer *t) {
-  if (!t->xrate || t->counts.empty() || t->counts_tot_kept <= 0 || t->counts_pw <= 0) return W2B_OK;
-  const long long V = t->cfg.vocab_size;
-  const double st = (double)t->cfg.sample * (double)t->cfg.train_words;
-  auto kept = [&](double c) { return (t->cfg.sample > 0 && st > 0) ? (c < sqrt(c * st) + st ? c : sqrt(c * st) + st) : c; };
+  if (!t->xrate || t->in.counts.empty() || t->in.counts_tot_kept <= 0 || t->in.counts_pw <= 0) return W2B_OK;
+  const long long V = t->in.cfg.vocab_size;
   std::vector<float> r((size_t)(2 * V), 0.f);
   for (long long a = 1; a < V; a++) {
-    const double c = (double)t->counts[(size_t)a], k = kept(c) / t->counts_tot_kept;
-    r[(size_t)a] = (float)((t->cfg.window + 1) * k);
-    r[(size_t)(V + a)] = (float)(t->cfg.negative * pow(c, 0.75) / t->counts_pw + k);
+    const double c = (double)t->in.counts[(size_t)a], k = w2b_plan_kept(t->in, c) / t->in.counts_tot_kept;
+    r[(size_t)a] = (float)((t->in.cfg.window + 1) * k);
+    r[(size_t)(V + a)] = (float)(t->in.cfg.negative * pow(c, 0.75) / t->in.counts_pw + k);
   }
   HIPCHK(hipMemcpy(t->xrate, r.data(), sizeof(float) * 2 * V, hipMemcpyHostToDevice));
   t->xrate_host.swap(r);
@@ -1483,10 +1012,10 @@ static int xchg_setup(w2b_trainer *t) {
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_evs[k], hipEventDisableTiming);
   }
   if (e == hipSuccess && !t->wca_buf) e = hipMalloc(&t->wca_buf, 2 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&t->xcnt, sizeof(float) * 2 * t->cfg.vocab_size);
-  if (e == hipSuccess) e = hipMemsetAsync(t->xcnt, 0, sizeof(float) * 2 * t->cfg.vocab_size, t->stream);
-  if (e == hipSuccess) e = hipMalloc(&t->xrate, sizeof(float) * 2 * t->cfg.vocab_size);
-  if (e == hipSuccess) e = hipMemsetAsync(t->xrate, 0, sizeof(float) * 2 * t->cfg.vocab_size, t->stream);
+  if (e == hipSuccess) e = hipMalloc(&t->xcnt, sizeof(float) * 2 * t->in.cfg.vocab_size);
+  if (e == hipSuccess) e = hipMemsetAsync(t->xcnt, 0, sizeof(float) * 2 * t->in.cfg.vocab_size, t->stream);
+  if (e == hipSuccess) e = hipMalloc(&t->xrate, sizeof(float) * 2 * t->in.cfg.vocab_size);
+  if (e == hipSuccess) e = hipMemsetAsync(t->xrate, 0, sizeof(float) * 2 * t->in.cfg.vocab_size, t->stream);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_train, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_evc, hipEventDisableTiming);
   if (e == hipSuccess) e = hipMemcpyAsync(t->base, t->uv, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream);
@@ -1564,16 +1093,15 @@ extern "C" int w2b_exchange_init(w2b_trainer *t) {
 static const double W2B_SAT_UPDATES = 32.0;
 static void xchg_saturated_prefix(const w2b_trainer *t, long long words, int *sat_u, int *sat_v) {
   *sat_u = *sat_v = 0;
-  const long long V = t->cfg.vocab_size;
-  if (t->counts.empty() || t->counts_tot <= 0 || words <= 0) return;
-  const double sat = t->tune.exchange_sat_updates > 0 ? (double)t->tune.exchange_sat_updates : W2B_SAT_UPDATES;
+  const long long V = t->in.cfg.vocab_size;
+  if (t->in.counts.empty() || t->in.counts_tot <= 0 || words <= 0) return;
+  const double sat = t->in.tune.exchange_sat_updates > 0 ? (double)t->in.tune.exchange_sat_updates : W2B_SAT_UPDATES;
   auto prefix = [&](bool is_v) -> int {
     long long lo = 0, hi = V - 1;
     while (lo < hi) {
       const long long mid = (lo + hi + 1) / 2;
-      const double c = (double)t->counts[(size_t)mid];
-      const double rate = is_v ? t->cfg.negative * pow(c, 0.75) / t->counts_pw + c / t->counts_tot
-                               : (t->cfg.window + 1) * c / t->counts_tot;
+      const double c = (double)t->in.counts[(size_t)mid];
+      const double rate = is_v ? w2b_plan_rate_v(t->in, c) : (t->in.cfg.window + 1) * c / t->in.counts_tot;
       if (rate * (double)words >= sat) lo = mid; else hi = mid - 1;
     }
     return (int)lo;
@@ -1652,10 +1180,10 @@ static int xchg_delta(w2b_trainer *t, long long c) {
 static const double W2B_XCHG_TAU_U = 64.0, W2B_XCHG_TAU_V = 64.0;   // updates that move a row most of the way
 static int xchg_factor(w2b_trainer *t, hipStream_t q) {
   if (!t->x_fac_pending) return W2B_OK;
-  const int rule = t->tune.exchange_rule;
-  const float tau_u = t->tune.exchange_tau_u > 0 ? (float)t->tune.exchange_tau_u : (float)W2B_XCHG_TAU_U;
-  const float tau_v = t->tune.exchange_tau_v > 0 ? (float)t->tune.exchange_tau_v : (float)W2B_XCHG_TAU_V;
-  HIPCHK(w2b_launch_xchg_factor(t->xcnt, t->xrate_host.empty() ? nullptr : t->xrate, (float)t->x_words_sync, tau_u, tau_v, t->cfg.vocab_size,
+  const int rule = t->in.tune.exchange_rule;
+  const float tau_u = t->in.tune.exchange_tau_u > 0 ? (float)t->in.tune.exchange_tau_u : (float)W2B_XCHG_TAU_U;
+  const float tau_v = t->in.tune.exchange_tau_v > 0 ? (float)t->in.tune.exchange_tau_v : (float)W2B_XCHG_TAU_V;
+  HIPCHK(w2b_launch_xchg_factor(t->xcnt, t->xrate_host.empty() ? nullptr : t->xrate, (float)t->x_words_sync, tau_u, tau_v, t->in.cfg.vocab_size,
                                 rule, t->x_sat_u, t->x_sat_v, q));
   t->x_fac_pending = false;
   return W2B_OK;
@@ -1665,12 +1193,12 @@ static int xchg_apply(w2b_trainer *t, long long c, float scale) {
   const int k = (int)(c & 1);
   if (t->x_use_cnt) if (int rc = xchg_factor(t, t->xs[0])) return rc;
   HIPCHK(w2b_launch_xchg_apply(t->uv + r.off, t->base + r.off, t->xd[k], t->xsum[k], scale, r.len, t->x_use_cnt ? t->xcnt : nullptr,
-                               r.off, t->cfg.layer1_size, t->cfg.bitlevel, (t->tune.exchange_rule == 0 && t->cfg.bitlevel == 1) ? 1 : 0, t->xs[0]));
+                               r.off, t->in.cfg.layer1_size, t->in.cfg.bitlevel, (t->in.tune.exchange_rule == 0 && t->in.cfg.bitlevel == 1) ? 1 : 0, t->xs[0]));
   return W2B_OK;
 }
 // per row of [u || v]: has this replica changed it since the last exchange?
 static int xchg_touched(w2b_trainer *t, hipStream_t s) {
-  const long long V = t->cfg.vocab_size, D = t->cfg.layer1_size;
+  const long long V = t->in.cfg.vocab_size, D = t->in.cfg.layer1_size;
   return w2b_launch_xchg_touched(t->uv, t->base, t->xcnt, 2 * V, (int)D, s) == hipSuccess ? W2B_OK : fail(W2B_EHIP, "k_xchg_touched");
 }
 
@@ -1707,7 +1235,7 @@ static int xchg_run_rccl(w2b_trainer *t, int32_t mode) {
   t->x_use_cnt = mode == 2;
   if (mode == 2) {          // who has trained which row since the last exchange (2 V floats), before the first apply
     if (int rc = xchg_touched(t, Cs)) return rc;
-    NCCLCHK(ncclAllReduce(t->xcnt, t->xcnt, (size_t)(2 * t->cfg.vocab_size), ncclFloat, ncclSum, t->comm, Cs));
+    NCCLCHK(ncclAllReduce(t->xcnt, t->xcnt, (size_t)(2 * t->in.cfg.vocab_size), ncclFloat, ncclSum, t->comm, Cs));
     t->x_fac_pending = true;
     if (int rc = xchg_factor(t, Cs)) return rc;
     HIPCHK(hipEventRecord(t->x_evc, Cs));
@@ -1782,7 +1310,7 @@ extern "C" int w2b_exchange_counts(w2b_trainer *t, void **buf_dev, int64_t *elem
   t->x_use_cnt = true;
   t->x_fac_pending = true;                   // (the host sums the counts; the first w2b_exchange_apply turns them into factors)
   *buf_dev = t->xcnt;
-  *elems = 2 * t->cfg.vocab_size;
+  *elems = 2 * t->in.cfg.vocab_size;
   return W2B_OK;
 }
 
