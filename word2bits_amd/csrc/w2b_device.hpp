@@ -70,6 +70,13 @@ __device__ __forceinline__ float quant(float x, const QParam &q) {
   }
   return sgn * lvl;
 }
+__device__ __forceinline__ QParam make_qparam(const W2bParams &P) {
+  QParam qp;
+  qp.bitlevel = P.bitlevel;
+  qp.steps_i = (P.bitlevel >= 4) ? (1 << (P.bitlevel - 1)) : 1;
+  qp.steps_f = (float)qp.steps_i;
+  return qp;
+}
 
 // ------------------------------------------------------------------------------------ row access
 template <int VEC> struct Col { float e[VEC]; };
@@ -211,6 +218,36 @@ __device__ __forceinline__ double wave_sum_d(double x) {
 __device__ __forceinline__ unsigned long long lane_lt_mask(int lane) {
   return lane == 0 ? 0ull : (~0ull >> (64 - lane));
 }
+
+// Explicit LDS address space on every pointer of a kernel's LDS record: dereferences compile to ds_*
+// instructions.  (With generic pointers the two step buffers were selected through a struct reference and
+// address-space inference gave up: 250 flat_load/flat_store per step, each tied to vmcnt AND lgkmcnt, so
+// every window access also waited for the target rows in flight.)
+#define W2B_LDS __attribute__((address_space(3)))
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+// LDS accesses of a thread's own 16-byte column of a row kept in LDS
+__device__ __forceinline__ Col<4> lds_ld(const W2B_LDS float *p) {
+  const f32x4_t t = *(const W2B_LDS f32x4_t *)p;
+  Col<4> c;
+  c.e[0] = t.x; c.e[1] = t.y; c.e[2] = t.z; c.e[3] = t.w;
+  return c;
+}
+__device__ __forceinline__ void lds_st(W2B_LDS float *p, const Col<4> &c) {
+  f32x4_t t;
+  t.x = c.e[0]; t.y = c.e[1]; t.z = c.e[2]; t.w = c.e[3];
+  *(W2B_LDS f32x4_t *)p = t;
+}
+
+// Phase timers of the producer / consumer kernels (builds with -DW2B_PHASE_TIMERS; worker 0 only; shader clocks; printed by
+// w2b_trainer_destroy under W2B_DEBUG).  A kernel that uses them defines `timing_` and `tick_` and lists its dbg[] slots.
+#ifdef W2B_PHASE_TIMERS
+#define W2B_TICK(k) do { if (timing_) { const unsigned long long n_ = __builtin_readcyclecounter(); \
+    atomicAdd(&P.shared->dbg[k], n_ - tick_); tick_ = n_; } } while (0)
+#define W2B_COUNT(k) do { if (timing_) atomicAdd(&P.shared->dbg[k], 1ull); } while (0)
+#else
+#define W2B_TICK(k) do { } while (0)
+#define W2B_COUNT(k) do { } while (0)
+#endif
 
 // ------------------------------------------------------------------------------------ LDS carving
 // All regions are 4-byte typed; the carve keeps the float region 16-byte aligned.
@@ -456,6 +493,28 @@ __device__ __forceinline__ void xhot_merge_event(const W2bParams &P, const XHot 
   cursor += P.xhot_m;
 }
 
+// ------------------------------------------------------------------------------------ gradient scalar, loss term
+// g of one target from its dot product f (ref :473-475); `centre`: the target is the centre word (label 1).
+// TP: the sigmoid table in global memory or (row-group kernel) in LDS.
+template <typename TP>
+__device__ __forceinline__ float grad_scalar(const float f, const bool centre, const float alpha, TP exp_table) {
+  const float label = centre ? 1.f : 0.f;
+  float g;
+  if (f > 6.f) g = (label - 1.f) * alpha;
+  else if (f < -6.f) g = label * alpha;
+  else g = (label - exp_table[(int)((f + 6.f) * 83.f)]) * alpha;
+  return g;
+}
+// log(sigmoid(+-f)) of one target (ref :480-483)
+__device__ __forceinline__ float log_sigmoid_term(const float f, const bool centre) {
+  const float dp = centre ? f : -f;
+  float sg;
+  if (dp > 6.f) sg = 1.f;
+  else if (dp < -6.f) sg = 1e-9f;
+  else sg = 1.f / (1.f + expf(-dp));
+  return logf(sg);
+}
+
 // ------------------------------------------------------------------------------------ one centre word
 // Preconditions: L.ctx[0..cw), L.tgt[0..nt) and prep_lists() results published by a __syncthreads();
 // cw >= 1, nt >= 1.
@@ -621,12 +680,7 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
     if (lane < n) {
       float f = 0.f;
       for (int w = 0; w < nwaves; w++) f += red[lane * W2B_MAXW + w];
-      const float label = (start + lane == 0) ? 1.f : 0.f;      // target 0 is the centre word
-      float g;
-      if (f > 6.f) g = (label - 1.f) * alpha;
-      else if (f < -6.f) g = label * alpha;
-      else g = (label - P.exp_table[(int)((f + 6.f) * 83.f)]) * alpha;
-      gl = g;
+      gl = grad_scalar(f, start + lane == 0, alpha, P.exp_table);   // target 0 is the centre word
       if (LOSS && wave == 0) fsave[start + lane] = f;           // the log-sigmoid term of ref :480-483 is booked after phase C
     }
     // error accumulation + row update, in target order (ref :486-491)
@@ -736,15 +790,7 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
     // ref :480-483 for all targets of this centre word, now that the chunk registers are free: lane j of wavefront 0
     // takes target j (f parked in LDS by the same wavefront; in-order LDS + the barriers in between)
     if (wave == 0) {
-      for (int j = lane; j < nt; j += 64) {
-        const float f = fsave[j];
-        const float dp = (j == 0) ? f : -f;                     // target 0 is the centre word (label 1)
-        float sg;
-        if (dp > 6.f) sg = 1.f;
-        else if (dp < -6.f) sg = 1e-9f;
-        else sg = 1.f / (1.f + expf(-dp));
-        loss_acc += (double)logf(sg);
-      }
+      for (int j = lane; j < nt; j += 64) loss_acc += (double)log_sigmoid_term(fsave[j], j == 0);   // target 0 is the centre word
     }
     if (reg_on) {
       const float s = wave_sum(active ? regsq : 0.f);
@@ -817,19 +863,8 @@ __device__ __forceinline__ void process_word_wide(const W2bParams &P, const Word
     }
     __syncthreads();
     f = L.red[0];
-    const float label = (t == 0) ? 1.f : 0.f;
-    float g;
-    if (f > 6.f) g = (label - 1.f) * alpha;
-    else if (f < -6.f) g = label * alpha;
-    else g = (label - P.exp_table[(int)((f + 6.f) * 83.f)]) * alpha;
-    if (LOSS && tid == 0) {                                       // ref :480-483
-      const float dp = (label != 0.f) ? f : -f;
-      float sg;
-      if (dp > 6.f) sg = 1.f;
-      else if (dp < -6.f) sg = 1e-9f;
-      else sg = 1.f / (1.f + expf(-dp));
-      loss_acc += (double)logf(sg);
-    }
+    const float g = grad_scalar(f, t == 0, alpha, P.exp_table);
+    if (LOSS && tid == 0) loss_acc += (double)log_sigmoid_term(f, t == 0);
     float s2 = 0.f;
     for (int c = tid; c < dim; c += nthr) {
       const float xv = ld(P.v, row, c), q = quant<QM>(xv, qp);
@@ -943,6 +978,114 @@ struct WorkerLds {            // scalars of one worker, owned by wavefront 0
   int sen_len, sen_pos, override_, eof, done, cw, nt, pad;
   float alpha;
 };
+
+// ------------------------------------------------------------------------------------ the scalar walk of one worker
+// The scalar half of TrainModelThread (ref :379-460, :505-509), stated once for the three worker kernels.  Each piece is
+// executed by ONE wavefront (all 64 lanes, wave-uniform arguments).  SP / IP: pointers to the worker's LDS record and lists,
+// generic in the plain kernel and address-space-3 in the other two (as prep_lists<T, IP>).
+
+// The worker's unfinished sentence between W2bWorker::sen and LDS: thread t of the nthr threads that copy it
+template <typename DP, typename SP, typename NT>
+__device__ __forceinline__ void copy_sentence(DP dst, SP src, const int len, const int t, const NT nthr) {
+  for (int i = t; i < len; i += nthr) dst[i] = src[i];
+}
+// W2bWorker -> WorkerLds (one thread; followed by a __syncthreads() of the caller)
+template <typename SP>
+__device__ __forceinline__ void worker_restore(const W2bWorker *G, SP S) {
+  S->rng = G->rng; S->cursor = G->cursor; S->wc = G->word_count; S->last_wc = G->last_word_count;
+  S->sen_len = G->sen_len; S->sen_pos = G->sen_pos; S->override_ = G->first_override;
+  S->eof = 0; S->done = 0; S->cw = 0; S->nt = 0; S->alpha = 0.f;
+}
+// ... and back (one thread, behind a barrier of the caller); a worker that has finished its epoch is counted in workers_done,
+// after whatever the caller adds to the loss sums
+template <typename SP>
+__device__ __forceinline__ void worker_save(const W2bParams &P, W2bWorker *G, SP S) {
+  G->rng = S->rng; G->cursor = S->cursor; G->word_count = S->wc; G->last_word_count = S->last_wc;
+  G->sen_len = S->sen_len; G->sen_pos = S->sen_pos; G->first_override = S->override_;
+  if (S->done) { G->done = 1; atomicAdd(&P.shared->workers_done, 1); }
+}
+
+// The alpha schedule (ref :379-393): every 10000 words of this worker.  Returns whether this pass stored a new alpha.
+// `stored`: where a caller that goes on with its own value wants it, in every lane (the plain kernel loads alpha again
+// after its draws instead: its choice).
+__device__ __forceinline__ bool alpha_schedule_step(const W2bParams &P, const long long wc, long long &last_wc, const int lane,
+                                                    float *stored = nullptr) {
+  const bool due = wc - last_wc > 10000;
+  if (due) {
+    float a = 0.f;
+    if (lane == 0) {
+      const unsigned long long d = (unsigned long long)(wc - last_wc);
+      const unsigned long long wca = atomicAdd(&P.shared->word_count_actual, d) + d;
+      const long long wca_all = w2b_global_progress(P, (long long)wca);
+      a = P.starting_alpha * (1.f - (float)wca_all / (float)(P.iter * P.train_words + 1));
+      if ((double)a < (double)P.starting_alpha * 0.0001) a = (float)((double)P.starting_alpha * 0.0001);
+      __hip_atomic_store(&P.shared->alpha, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (stored) *stored = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a)));
+    last_wc = wc;
+  }
+  return due;
+}
+
+// The end of a worker's epoch (ref :414-423, local_iter == 1): its last words are booked.  The test itself,
+// `eof || wc > P.train_words / P.total_threads`, stays written out at the three callers: inside a helper, in every form
+// tried, the compiler treats the 64-bit division differently and the register allocation of all three kernels moves
+// (row-group kernel: one VGPR and half of the SGPR spills).
+__device__ __forceinline__ void epoch_end(const W2bParams &P, const long long wc, long long &last_wc, const int lane) {
+  if (lane == 0) atomicAdd(&P.shared->word_count_actual, (unsigned long long)(wc - last_wc));
+  last_wc = wc;
+}
+
+// The window draw b (ref :428-429)
+__device__ __forceinline__ int window_draw(const W2bParams &P, unsigned long long &rng) {
+  rng = rng * W2B_LCG_A + W2B_LCG_C;
+  return (int)fast_mod(rng, (unsigned long long)P.window, P.window_magic);
+}
+// ... and the step to the next position (ref :505-509)
+__device__ __forceinline__ void next_position(int &sen_pos, int &sen_len) {
+  sen_pos++;
+  if (sen_pos >= sen_len) sen_len = 0;
+}
+
+__device__ __forceinline__ int table_entry(const W2bParams &P, const unsigned long long x) {
+  return P.table[fast_mod(x >> 16, (unsigned long long)P.table_size, P.table_magic)];
+}
+// The targets of a centre word (ref :450-460): tgt[0] = word, then the negative draws that are not the word itself, 64 per
+// trip (lane l: draw d0 + l).  Returns nt; rng leaves advanced by the `negative` draws.
+// jump_d(x, d) = x_{n+d} and jump_all(x) = x_{n+negative}: where the LCG jump-ahead constants come from is the caller's.
+// pref_ok: t_pref holds the table entries of the first 64 draws (table_prefetch, requested by the previous step).
+// ONE_TRIP: negative <= 64 is known to the caller.
+template <bool ONE_TRIP, typename IP, typename JD, typename JA>
+__device__ __forceinline__ int draw_targets(const W2bParams &P, IP tgt, const int word, unsigned long long &rng, JD jump_d, JA jump_all,
+                                            const bool pref_ok, const int t_pref, const int lane) {
+  const int K = P.negative;
+  int cnt = 0;
+  for (int d0 = 1; ONE_TRIP ? d0 == 1 : d0 <= K; d0 += 64) {
+    const int d = d0 + lane;
+    bool keep = false;
+    int t = 0;
+    if (d <= K) {
+      const unsigned long long x = jump_d(rng, d);
+      t = (pref_ok && d0 == 1) ? t_pref : table_entry(P, x);
+      if (t == 0) t = (int)(x % (unsigned long long)(P.vocab_size - 1)) + 1;
+      keep = (t != word);
+    }
+    const unsigned long long m = __ballot(keep);
+    if (keep) tgt[1 + cnt + __popcll(m & lane_lt_mask(lane))] = t;
+    cnt += __popcll(m);
+  }
+  if (lane == 0) tgt[0] = word;
+  rng = jump_all(rng);
+  return 1 + cnt;
+}
+// The table entry of this lane's draw (d = lane + 1) of the NEXT step, requested a step early by the producer wavefronts.
+// Valid when the next step stays inside the sentence: then its LCG ledger is one window draw, then the negative draws
+// (ref :428,455) -- a sentence read in between (sub-sampling draws, ref :405) would move it.
+template <typename JD>
+__device__ __forceinline__ int table_prefetch(const W2bParams &P, const unsigned long long rng, JD jump_d, const int lane) {
+  const unsigned long long xb = rng * W2B_LCG_A + W2B_LCG_C;     // the next step's window draw
+  return table_entry(P, jump_d(xb, lane + 1));
+}
 
 template <typename F>
 hipError_t dispatch_q(int bitlevel, F &&f) {

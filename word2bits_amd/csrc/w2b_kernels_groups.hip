@@ -43,7 +43,6 @@
 #ifndef W2B_GROUPS_DRAIN
 #define W2B_GROUPS_DRAIN 1
 #endif
-#define W2G_LDS __attribute__((address_space(3)))
 #define W2G_CMAX 32      // context rows of a centre word (window <= 16)
 #define W2G_TMAX 32      // targets of a centre word (negative + 1 <= G * TC <= 32)
 
@@ -51,18 +50,8 @@
 //   producer: [0] produce(), [1] waiting at the barriers;  adder: [2] loss terms + adds issued, [3] barriers
 //   data wavefront 0: [4] B0 -> loads issued -> context rows arrived and staged, [5] B1 wait, [6] window average + dot
 //   products + g + row updates, [7] B3 wait, [8] error accumulation, [9] B4 wait, [10] phase C, [11] B0 wait, [12] words
-#ifdef W2B_PHASE_TIMERS
-#define W2G_TICK(k) do { if (timing_) { const unsigned long long n_ = __builtin_readcyclecounter(); \
-    atomicAdd(&P.shared->dbg[k], n_ - tick_); tick_ = n_; } } while (0)
-#define W2G_COUNT(k) do { if (timing_) atomicAdd(&P.shared->dbg[k], 1ull); } while (0)
-#else
-#define W2G_TICK(k) do { } while (0)
-#define W2G_COUNT(k) do { } while (0)
-#endif
 
 namespace {
-
-typedef float w2g_f4 __attribute__((ext_vector_type(4)));
 
 // what the producer wavefront hands over for ONE centre word (double buffered)
 struct GLists {
@@ -91,18 +80,6 @@ struct GFixed {                   // LDS record of a worker: compile-time offset
   float red[W2G_TMAX * 4];        // partial dot products of the RW wavefronts of a group
 };
 static_assert(sizeof(GFixed) % 16 == 0, "the row regions behind GFixed are accessed 16 bytes at a time");
-
-__device__ __forceinline__ Col<4> lds_ld4(const W2G_LDS float *p) {
-  const w2g_f4 t = *(const W2G_LDS w2g_f4 *)p;
-  Col<4> c;
-  c.e[0] = t.x; c.e[1] = t.y; c.e[2] = t.z; c.e[3] = t.w;
-  return c;
-}
-__device__ __forceinline__ void lds_st4(W2G_LDS float *p, const Col<4> &c) {
-  w2g_f4 t;
-  t.x = c.e[0]; t.y = c.e[1]; t.z = c.e[2]; t.w = c.e[3];
-  *(W2G_LDS w2g_f4 *)p = t;
-}
 
 // add_col_contig (w2b_device.hpp) for a wavefront that is number `wig` of its row group: tab[row][256 wig ...] += d,
 // transposed so that instruction e covers the dwords [64 e, 64 e + 64) of the wavefront's 1 KiB segment.  All 64 lanes
@@ -134,11 +111,11 @@ template <int QM, bool LOSS, int RW, int G, int TC>
 __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_groups(const W2bParams P, const long long max_positions) {
   static_assert(G * TC <= W2G_TMAX, "own[] capacity");
   extern __shared__ int smem[];
-  W2G_LDS GFixed *const F = (W2G_LDS GFixed *)smem;
+  W2B_LDS GFixed *const F = (W2B_LDS GFixed *)smem;
   const int dim = P.dim;
-  W2G_LDS float *const errbuf = (W2G_LDS float *)((W2G_LDS char *)smem + sizeof(GFixed));   // [dim] accumulated error (ref :486-488)
-  W2G_LDS float *const stash = errbuf + dim;                   // [2 window][dim] raw context rows, window order
-  W2G_LDS float *const xq = stash + 2 * P.window * dim;        // [negative + 1][dim] quantized target rows (pre-update), target order
+  W2B_LDS float *const errbuf = (W2B_LDS float *)((W2B_LDS char *)smem + sizeof(GFixed));   // [dim] accumulated error (ref :486-488)
+  W2B_LDS float *const stash = errbuf + dim;                   // [2 window][dim] raw context rows, window order
+  W2B_LDS float *const xq = stash + 2 * P.window * dim;        // [negative + 1][dim] quantized target rows (pre-update), target order
   constexpr int NDW = G * RW, NTHR = (NDW + 2) * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -153,20 +130,13 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
     if (rc_on && tid == 0 && wid < P.num_threads) atomicAdd(&P.shared->launch_done, 1);
     return;
   }
-  QParam qp;
-  qp.bitlevel = P.bitlevel;
-  qp.steps_i = (P.bitlevel >= 4) ? (1 << (P.bitlevel - 1)) : 1;
-  qp.steps_f = (float)qp.steps_i;
-  W2G_LDS WorkerLds *const S = &F->S;
-  W2G_LDS int *const s_sen = F->sen;
+  const QParam qp = make_qparam(P);
+  W2B_LDS WorkerLds *const S = &F->S;
+  W2B_LDS int *const s_sen = F->sen;
   // restore the worker, stage the sigmoid table
-  for (int i = tid; i < Gw->sen_len; i += NTHR) s_sen[i] = Gw->sen[i];
+  copy_sentence(s_sen, Gw->sen, Gw->sen_len, tid, NTHR);
   for (int i = tid; i < 1000; i += NTHR) F->exp_table[i] = P.exp_table[i];
-  if (tid == 0) {
-    S->rng = Gw->rng; S->cursor = Gw->cursor; S->wc = Gw->word_count; S->last_wc = Gw->last_word_count;
-    S->sen_len = Gw->sen_len; S->sen_pos = Gw->sen_pos; S->override_ = Gw->first_override;
-    S->eof = 0; S->done = 0; S->cw = 0; S->nt = 0; S->alpha = 0.f;
-  }
+  if (tid == 0) worker_restore(Gw, S);
   __syncthreads();
   const bool reg_on = P.reg != 0.f;
   const int atomic_rank_v = P.atomic_rank, atomic_rank_u = P.atomic_rank_u;
@@ -179,16 +149,16 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
   if (wave == NDW) {
     // ------------------------------------------------------------------------------------------ producer wavefront
     const int W = P.window, K = P.negative;
-    // unigram-table draws of the NEXT pass, requested at the end of a pass (lane l: draw l + 1).  Valid when the next pass
-    // stays inside the sentence: then its LCG ledger is one window draw, then the negative draws (ref :428,455) -- a sentence
-    // read in between (sub-sampling draws, ref :405) would move it.
+    // unigram-table draws of the NEXT pass, requested at the end of a pass (table_prefetch; lane l: draw l + 1)
     int t_pref = 0;
     bool pref_ok = false;
     // LCG jump-ahead constants of this lane's draw (x_{n+d} = ja x_n + jc, d = lane + 1) and of the whole word's negative draws
     const unsigned long long ja_l = P.jump_a[lane + 1 <= K ? lane + 1 : 0], jc_l = P.jump_c[lane + 1 <= K ? lane + 1 : 0];
     const unsigned long long ja_k = P.jump_a[K], jc_k = P.jump_c[K];
+    auto jump_l = [&](unsigned long long x, int) { return ja_l * x + jc_l; };     // (only ever asked for d == lane + 1: one trip)
+    auto jump_k = [&](unsigned long long x) { return ja_k * x + jc_k; };
     // one loop pass of TrainModelThread's scalar side (the wavefront-0 block of k_train_workers) into the lists O
-    auto produce = [&](W2G_LDS GLists *O, const bool last) {
+    auto produce = [&](W2B_LDS GLists *O, const bool last) {
       unsigned long long rng = S->rng;
       long long cursor = S->cursor, wc = S->wc, last_wc = S->last_wc;
       int sen_len = S->sen_len, sen_pos = S->sen_pos, ovr = S->override_, eof = S->eof;
@@ -196,24 +166,10 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
       // (requested first, used last: its round trip runs beside the unigram-table draws'.  The schedule below may store a new
       // alpha in this very pass -- only every 10000 words of this worker, and the other workers' stores land at any time anyway)
       const float alpha_now = __hip_atomic_load(&P.shared->alpha, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      float alpha = 0.f;
-      bool alpha_own = false;
-      float alpha_set = 0.f;
+      float alpha = 0.f, alpha_own = 0.f;
+      bool alpha_set = false;
       if (!last) {
-        if (wc - last_wc > 10000) {                                    // ref :379-393
-          if (lane == 0) {
-            const unsigned long long d = (unsigned long long)(wc - last_wc);
-            const unsigned long long wca = atomicAdd(&P.shared->word_count_actual, d) + d;
-            const long long wca_all = w2b_global_progress(P, (long long)wca);
-            float a = P.starting_alpha * (1.f - (float)wca_all / (float)(P.iter * P.train_words + 1));
-            if ((double)a < (double)P.starting_alpha * 0.0001) a = (float)((double)P.starting_alpha * 0.0001);
-            __hip_atomic_store(&P.shared->alpha, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            alpha_set = a;
-          }
-          alpha_own = true;
-          alpha_set = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(alpha_set)));
-          last_wc = wc;
-        }
+        alpha_set = alpha_schedule_step(P, wc, last_wc, lane, &alpha_own);   // ref :379-393
         if (sen_len == 0) {                                            // ref :394-413
           read_sentence(P, (int *)s_sen, rng, cursor, wc, ovr, eof, sen_len, lane);
           sen_pos = 0;
@@ -221,13 +177,11 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
           W2B_WAVE_SYNC();
         }
         if (eof || wc > P.train_words / P.total_threads) {            // ref :414-423 (local_iter == 1)
-          if (lane == 0) atomicAdd(&P.shared->word_count_actual, (unsigned long long)(wc - last_wc));
-          last_wc = wc;
+          epoch_end(P, wc, last_wc, lane);
           done = 1;
         } else {
           const int word = (sen_len > 0) ? s_sen[sen_pos] : 0;          // ref :424
-          rng = rng * W2B_LCG_A + W2B_LCG_C;                            // ref :428-429
-          const int b = (int)fast_mod(rng, (unsigned long long)W, P.window_magic);
+          const int b = window_draw(P, rng);                            // ref :428-429
           const int hi = 2 * W + 1 - b;
           {                                                             // ref :431-436 (2 window + 1 <= 33 positions: one trip)
             const int a = b + lane;
@@ -238,32 +192,14 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
             cw = __popcll(m);
           }
           if (cw > 0) {                                                 // ref :450-460 (negative <= 31: one trip)
-            bool keep = false;
-            int t = 0;
-            const int d = 1 + lane;
-            if (d <= K) {
-              const unsigned long long x = ja_l * rng + jc_l;
-              t = pref_ok ? t_pref : P.table[fast_mod(x >> 16, (unsigned long long)P.table_size, P.table_magic)];
-              if (t == 0) t = (int)(x % (unsigned long long)(P.vocab_size - 1)) + 1;
-              keep = (t != word);
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) O->tgt[1 + __popcll(m & lane_lt_mask(lane))] = t;
-            if (lane == 0) O->tgt[0] = word;
-            nt = 1 + __popcll(m);
-            rng = ja_k * rng + jc_k;
-            alpha = alpha_own ? alpha_set : alpha_now;                // (a worker sees the alpha it has just stored, as the plain kernel's load after the store does)
+            nt = draw_targets<true>(P, O->tgt, word, rng, jump_l, jump_k, pref_ok, t_pref, lane);
+            alpha = alpha_set ? alpha_own : alpha_now;                // (a worker sees the alpha it has just stored, as the plain kernel's load after the store does)
           }
-          sen_pos++;                                                    // ref :505-509
-          if (sen_pos >= sen_len) sen_len = 0;
+          next_position(sen_pos, sen_len);                              // ref :505-509
         }
         // the next pass's table draws (see t_pref); its window draw comes first
         pref_ok = !done && sen_len != 0;
-        if (pref_ok && lane < K) {
-          const unsigned long long xb = rng * W2B_LCG_A + W2B_LCG_C;
-          const unsigned long long x = ja_l * xb + jc_l;
-          t_pref = P.table[fast_mod(x >> 16, (unsigned long long)P.table_size, P.table_magic)];
-        }
+        if (pref_ok && lane < K) t_pref = table_prefetch(P, rng, jump_l, lane);
       } else pref_ok = false;
       if (lane == 0) {
         S->rng = rng; S->cursor = cursor; S->wc = wc; S->last_wc = last_wc;
@@ -278,7 +214,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
     // the repetitions, the context rows' multiplicities.  A pass of its own so that the producer's work spreads over two barrier
     // intervals of the data wavefronts (produce: under their wait for the target rows; prepare: under their error sum) instead
     // of holding one barrier up (phase timers: 3 K of 20 K cycles per word were spent waiting for the producer at B3).
-    auto prepare = [&](W2G_LDS GLists *O) {
+    auto prepare = [&](W2B_LDS GLists *O) {
       W2B_WAVE_SYNC();
       const int cw = __builtin_amdgcn_readfirstlane(O->cw), nt = __builtin_amdgcn_readfirstlane(O->nt);
       if (cw <= 0) return;
@@ -326,19 +262,19 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
     prepare(&F->lists[0]);
     __syncthreads();                                                    // B0
     for (long long it = 0;; ++it) {
-      const W2G_LDS GLists *const L = &F->lists[it & 1];
+      const W2B_LDS GLists *const L = &F->lists[it & 1];
       if (L->stop) break;
       const int cw = L->cw, npass = L->npass;
       if (cw > 0) __syncthreads();                                      // B1
-      W2G_TICK(1);
+      W2B_TICK(1);
       produce(&F->lists[(it + 1) & 1], it + 1 >= max_positions);        // (under the data wavefronts' wait for their target rows)
-      W2G_TICK(0);
+      W2B_TICK(0);
       if (cw > 0) {
         if (RW > 1) for (int ps = 0; ps < npass; ps++) __syncthreads();
         __syncthreads();                                                // B3
-        W2G_TICK(1);
+        W2B_TICK(1);
         prepare(&F->lists[(it + 1) & 1]);                               // (under the data wavefronts' error sum)
-        W2G_TICK(0);
+        W2B_TICK(0);
         __syncthreads();                                                // B4
       } else prepare(&F->lists[(it + 1) & 1]);
       __syncthreads();                                                  // B0
@@ -349,7 +285,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
     __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void *)P.u, 0, (int)P.tab_bytes, 0x27000);
     __syncthreads();                                                    // B0
     for (long long it = 0;; ++it) {
-      const W2G_LDS GLists *const L = &F->lists[it & 1];
+      const W2B_LDS GLists *const L = &F->lists[it & 1];
       if (L->stop) break;
       const int cw = L->cw;
       if (cw > 0) {
@@ -357,21 +293,13 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
         __syncthreads();                                                // B1
         if (RW > 1) for (int ps = 0; ps < npass; ps++) __syncthreads();
         __syncthreads();                                                // B3
-        W2G_TICK(3);
+        W2B_TICK(3);
         if (LOSS) {                                                     // ref :480-483: lane j books target j
-          for (int j = lane; j < nt; j += 64) {
-            const float f = F->fs[j];
-            const float dp = (j == 0) ? f : -f;                         // target 0 is the centre word (label 1)
-            float sg;
-            if (dp > 6.f) sg = 1.f;
-            else if (dp < -6.f) sg = 1e-9f;
-            else sg = 1.f / (1.f + expf(-dp));
-            loss_acc += (double)logf(sg);
-          }
+          for (int j = lane; j < nt; j += 64) loss_acc += (double)log_sigmoid_term(F->fs[j], j == 0);   // target 0 is the centre word
         }
-        W2G_TICK(2);
+        W2B_TICK(2);
         __syncthreads();                                                // B4
-        W2G_TICK(3);
+        W2B_TICK(3);
         if (!reg_on && atomic_rank_u > 0) {                             // u[c] += e[c] on the current value (ref :500-502)
           float ev[NE];
 #pragma unroll
@@ -394,7 +322,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
             }
           }
         }
-        W2G_TICK(2);
+        W2B_TICK(2);
       }
 #if W2B_GROUPS_DRAIN >= 2
       __builtin_amdgcn_s_waitcnt(0);                                    // ... and the adder's lossless adds have returned
@@ -412,7 +340,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
     const unsigned tab_bytes = P.tab_bytes;
     __syncthreads();                                                    // B0
     for (long long it = 0;; ++it) {
-      const W2G_LDS GLists *const L = &F->lists[it & 1];
+      const W2B_LDS GLists *const L = &F->lists[it & 1];
       if (L->stop) break;
       const int cw = L->cw;
       if (cw > 0) {
@@ -447,12 +375,12 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
 #pragma unroll
           for (int jj = 0; jj < CB; jj++) {
             const int j = g + (j0 + jj) * G;
-            if (j < cw && active) lds_st4(stash + j * dim + col0, r[jj]);
+            if (j < cw && active) lds_st(stash + j * dim + col0, r[jj]);
           }
         }
-        W2G_TICK(4);
+        W2B_TICK(4);
         __syncthreads();                                                // B1
-        W2G_TICK(5);
+        W2B_TICK(5);
         // ---- the target rows are requested only now: a target row is open (read -> dot product -> update -> store) for one
         // memory round trip + its own arithmetic, not for the context rows' round trip as well.  What a racy shared row costs
         // in epoch loss grows with throughput x the time it is open (measured: heldout_zipf12 at 256 workers -1.6 % with the
@@ -472,7 +400,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
           for (; j0 + LA <= cw; j0 += LA) {                            // whole trips: straight-line code
             Col<4> c[LA];
 #pragma unroll
-            for (int jj = 0; jj < LA; jj++) c[jj] = lds_ld4(stash + (j0 + jj) * dim + col0);
+            for (int jj = 0; jj < LA; jj++) c[jj] = lds_ld(stash + (j0 + jj) * dim + col0);
 #pragma unroll
             for (int jj = 0; jj < LA; jj++) {
 #pragma unroll
@@ -484,7 +412,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
             }
           }
           for (; j0 < cw; j0++) {
-            const Col<4> c = lds_ld4(stash + j0 * dim + col0);
+            const Col<4> c = lds_ld(stash + j0 * dim + col0);
 #pragma unroll
             for (int e = 0; e < 4; e++) {
               const float q = quant<QM>(c.e[e], qp);
@@ -517,7 +445,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
               dl.e[e] = gk * avg.e[e] - ar2 * xv;
               xr.e[e] = xv + dl.e[e];
             }
-            lds_st4(xq + i * dim + col0, q4);
+            lds_st(xq + i * dim + col0, q4);
             if (!by_add) store_col<4, 0, 0>(P.v, row, dim, col0, xr, tab_bytes);
           }
           if (by_add) add_cols_group(P.v, row, dim, dl, tab_bytes, wig, lane);
@@ -528,14 +456,6 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
           for (int e = 0; e < 4; e++) t[e] = avg.e[e] * quant<QM>(xr.e[e], qp);
           const float s = (t[0] + t[1]) + (t[2] + t[3]);
           return active ? s : 0.f;
-        };
-        auto grad = [&](const float f, const bool centre) -> float {   // ref :473-475
-          const float label = centre ? 1.f : 0.f;
-          float gq;
-          if (f > 6.f) gq = (label - 1.f) * alpha;
-          else if (f < -6.f) gq = label * alpha;
-          else gq = (label - F->exp_table[(int)((f + 6.f) * 83.f)]) * alpha;
-          return gq;
         };
         // ---- phase B, pass 0: the distinct target rows (ref :450-492)
         {
@@ -562,7 +482,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
           }
           float gl = 0.f;
           if (lane < TC && mine >= 0) {
-            gl = grad(fl, mine == 0);
+            gl = grad_scalar(fl, mine == 0, alpha, F->exp_table);
             if (wig == 0) {
               F->gs[mine] = gl;
               if (LOSS) F->fs[mine] = fl;
@@ -596,7 +516,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
             float f = 0.f;
             if (RW == 1) f = 0.f + pp;
             else for (int w = 0; w < RW; w++) f += F->red[i * 4 + w];
-            const float gk = grad(f, i == 0);
+            const float gk = grad_scalar(f, i == 0, alpha, F->exp_table);
             if (wig == 0 && lane == 0) {
               F->gs[i] = gk;
               if (LOSS) F->fs[i] = f;
@@ -604,9 +524,9 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
             finish_row(i, row, gk, xx);
           }
         }
-        W2G_TICK(6);
+        W2B_TICK(6);
         __syncthreads();                                                // B3
-        W2G_TICK(7);
+        W2B_TICK(7);
         // ---- error accumulation in target order (ref :486-488).  Round 5 let every row group sum all nt quantized target rows
         // for its own copy of the columns -- G times the same 25-row LDS sum (3.5 K of a word's 20 K cycles).  Round 6: the
         // columns are split over ALL data wavefronts of the worker, one thread per EC consecutive floats, every element still
@@ -650,13 +570,13 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
             for (int e = 0; e < EC; e++) errbuf[ecol + e] = er[e];
           }
         }
-        W2G_TICK(8);
+        W2B_TICK(8);
         __syncthreads();                                                // B4
-        W2G_TICK(9);
+        W2B_TICK(9);
         Col<4> err;
 #pragma unroll
         for (int e = 0; e < 4; e++) err.e[e] = 0.f;
-        if (active) err = lds_ld4(errbuf + col0);
+        if (active) err = lds_ld(errbuf + col0);
         // ---- phase C: u[ctx_j] += context_avge - 2*alpha*reg*u[ctx_j]   (ref :494-503); the adder wavefront takes the rows
         // that get lossless adds (reg == 0: their delta is the error vector itself)
 #pragma unroll
@@ -671,7 +591,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
                 Col<4> rr, dl;
 #pragma unroll
                 for (int e = 0; e < 4; e++) { rr.e[e] = 0.f; dl.e[e] = 0.f; }
-                if (active) rr = lds_ld4(stash + j * dim + col0);
+                if (active) rr = lds_ld(stash + j * dim + col0);
                 for (int k = 0; k < m; k++) {                           // a row that occurs m times in the window is updated m times
                   if (active) {
 #pragma unroll
@@ -691,20 +611,19 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
           const float s = wave_sum(active ? regsq : 0.f);
           if (lane == 0) loss_acc -= (double)(P.reg * s);               // ref :437-445 and :463-471
         }
-        W2G_TICK(10);
-        W2G_COUNT(12);
+        W2B_TICK(10);
+        W2B_COUNT(12);
       }
 #if W2B_GROUPS_DRAIN >= 1
       __builtin_amdgcn_s_waitcnt(0);                                    // this wavefront's row stores have been acknowledged (see W2B_GROUPS_DRAIN)
 #endif
       __syncthreads();                                                  // B0
-      W2G_TICK(11);
+      W2B_TICK(11);
     }
   }
   // save the worker
   __syncthreads();
-  const int sl = S->sen_len;
-  for (int i = tid; i < sl; i += NTHR) Gw->sen[i] = s_sen[i];
+  copy_sentence(Gw->sen, s_sen, S->sen_len, tid, NTHR);
   if (LOSS) {
     if (wave == NDW + 1) {                                              // the adder's lanes hold the log-sigmoid terms
       const double lsum = wave_sum_d(loss_acc);
@@ -715,11 +634,7 @@ __global__ void __launch_bounds__((G * RW + 2) * 64, (RW == 4 ? 4 : 3)) k_train_
     }
   }
   if (rc_on && tid == 0) atomicAdd(&P.shared->launch_done, 1);
-  if (tid == NDW * 64) {                                                // lane 0 of the producer
-    Gw->rng = S->rng; Gw->cursor = S->cursor; Gw->word_count = S->wc; Gw->last_word_count = S->last_wc;
-    Gw->sen_len = S->sen_len; Gw->sen_pos = S->sen_pos; Gw->first_override = S->override_;
-    if (S->done) { Gw->done = 1; atomicAdd(&P.shared->workers_done, 1); }
-  }
+  if (tid == NDW * 64) worker_save(P, Gw, S);                           // (lane 0 of the producer)
 }
 
 // The refresher of the hottest context rows' read copies: W2B_RC_BLOCKS small workgroups on a stream of their own, beside a

@@ -34,25 +34,16 @@
 #include <cstdio>
 #include <cstdlib>
 
-// Register budget and workgroup shape.  A worker is up to 4 data wavefronts + 1 producer wavefront.  The hardware
-// places wavefront i of a workgroup on SIMD i mod 4, so a worker that is a workgroup of its own puts TWO of its five
-// wavefronts on SIMD 0, and a second such workgroup fits on the CU only within 128 VGPRs (measured: at 168 VGPRs 256
-// and 512 one-worker workgroups run at the same speed although the occupancy API answers 2 per CU).  128 VGPRs hold
-// 13 target rows: two memory round trips per centre word at negative = 24.
-// Default: W2B_WPG = 1 worker per workgroup, W2B_RT = 13, 128 VGPRs, s_barrier.
-// Alternative (measured, kept selectable at build time): W2B_WPG = 2 INDEPENDENT workers per workgroup -- ten
-// wavefronts land 3/3/2/2 on the SIMDs, 168 VGPRs each, W2B_RT = 25: all target rows of a centre word in registers, one
-// round trip per word AND two workers per CU; the workers synchronise their own wavefronts through LDS counters
-// (worker_barrier) because s_barrier would couple them.  On MI355X it is +2 % at negative = 24 and -10 % at negative =
-// 12 (25-row code for 13-row chunks), and the counter barrier itself costs 2 % against s_barrier: not the default.
-#ifndef W2B_WPG
-#define W2B_WPG 1       // workers per workgroup
-#endif
+// Register budget and workgroup shape.  A worker is one workgroup: up to 4 data wavefronts + 1 producer wavefront.  The
+// hardware places wavefront i of a workgroup on SIMD i mod 4, so a worker puts TWO of its five wavefronts on SIMD 0, and a
+// second workgroup fits on the CU only within 128 VGPRs (measured: at 168 VGPRs 256 and 512 workgroups run at the same speed
+// although the occupancy API answers 2 per CU).  128 VGPRs hold 13 target rows: two memory round trips per centre word at
+// negative = 24.  (A build with two workers per workgroup and 25-row chunks was measured and dropped: DESIGN.md section 3.3.)
 #ifndef W2B_RT
-#define W2B_RT (W2B_WPG == 1 ? 13 : 25)       // target rows per chunk (x 4 VGPRs)
+#define W2B_RT 13       // target rows per chunk (x 4 VGPRs)
 #endif
 #ifndef W2B_RES_WAVES
-#define W2B_RES_WAVES (W2B_WPG == 1 ? 4 : 3)  // wavefronts per SIMD the kernel is register-allocated for
+#define W2B_RES_WAVES 4 // wavefronts per SIMD the kernel is register-allocated for
 #endif
 #define W2B_RB 5        // rows whose partial dot products are formed and reduced together (bounds the live temporaries)
 #define W2B_NDWMAX 4    // data wavefronts per worker (one thread per 16-byte column: D <= 1024) + 1 producer wavefront
@@ -60,51 +51,17 @@
 
 namespace {
 
-// Phase timers (builds with -DW2B_PHASE_TIMERS; worker 0 only; shader clocks; printed by w2b_trainer_destroy under
-// W2B_DEBUG):  producer wavefront: [0] prepare, [1] waiting at the end-of-step barrier, [2] loss bookkeeping
+// Phase timers (W2B_TICK / W2B_COUNT in w2b_device.hpp):  producer wavefront: [0] prepare, [1] waiting at the end-of-step
+//   barrier, [2] loss bookkeeping
 //   data wavefront 0  : [4] loads issued -> window exchange + phase A done, [5] partial dots (+ wait for the rows),
 //                       [6] chunk barrier wait, [7] g + updates + stores, [8] phase C + hot merge,
 //                       [9] end-of-step barrier wait, [10] steps
-#ifdef W2B_PHASE_TIMERS
-#define W2B_TICK(k) do { if (timing_) { const unsigned long long n_ = __builtin_readcyclecounter(); \
-    atomicAdd(&P.shared->dbg[k], n_ - tick_); tick_ = n_; } } while (0)
-#define W2B_COUNT(k) do { if (timing_) atomicAdd(&P.shared->dbg[k], 1ull); } while (0)
-#else
-#define W2B_TICK(k) do { } while (0)
-#define W2B_COUNT(k) do { } while (0)
-#endif
-
-// Explicit LDS address space on every pointer of the kernel's LDS record: dereferences compile to ds_*
-// instructions.  (With generic pointers the two step buffers were selected through a struct reference and
-// address-space inference gave up: 250 flat_load/flat_store per step, each tied to vmcnt AND lgkmcnt, so
-// every window access also waited for the target rows in flight.)
-#define W2B_LDS __attribute__((address_space(3)))
 
 struct Win2Lds {          // scalars owned by the producer wavefront (extends WorkerLds)
   WorkerLds w;
   int clo, chi;           // sentence positions currently resident (empty when chi < clo)
-  unsigned bar_step, bar_chunk;   // arrival counters of the worker's two barriers (monotonic within a launch)
   double loss_reg;                // regularisation terms of the loss booked by the data wavefronts (reg != 0 only)
 };
-
-// A barrier among the wavefronts of ONE worker (W2B_WPG > 1; with one worker per workgroup it is s_barrier).
-// Monotonic LDS counter: every arriving wavefront adds 1, everybody
-// polls until `target` arrivals have been counted.  LDS operations of a wavefront execute in order and the CU's LDS
-// serves all of them in arrival order, so what a wavefront wrote to LDS before its arrival is visible to whoever has
-// seen the count -- no s_waitcnt on outstanding GLOBAL memory operations is involved (the row stores of a step stay
-// in flight across the barrier; __syncthreads() would drain them).  The wavefront-scope fences only stop the compiler
-// from moving LDS accesses across the barrier.
-__device__ __forceinline__ void worker_barrier(W2B_LDS unsigned *cnt, unsigned target, int lane, bool arrive = true) {
-#if W2B_WPG == 1           // the workgroup IS the worker: the hardware barrier (the producer executes the chunk barriers too)
-  __syncthreads();
-  return;
-#endif
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  if (arrive && lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  while ((int)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - target) < 0)
-    __builtin_amdgcn_s_sleep(1);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // What the producer wavefront hands to the data wavefronts for ONE step (double buffered in LDS)
 struct Step2 {
@@ -181,20 +138,6 @@ __device__ __forceinline__ Col4 col_zero() {
 #pragma unroll
   for (int e = 0; e < 4; e++) c.e[e] = 0.f;
   return c;
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-// LDS accesses of a thread's own 16-byte column of a resident row
-__device__ __forceinline__ Col4 lds_ld(const W2B_LDS float *p) {
-  const f32x4_t t = *(const W2B_LDS f32x4_t *)p;
-  Col4 c;
-  c.e[0] = t.x; c.e[1] = t.y; c.e[2] = t.z; c.e[3] = t.w;
-  return c;
-}
-__device__ __forceinline__ void lds_st(W2B_LDS float *p, const Col4 &c) {
-  f32x4_t t;
-  t.x = c.e[0]; t.y = c.e[1]; t.z = c.e[2]; t.w = c.e[3];
-  *(W2B_LDS f32x4_t *)p = t;
 }
 
 // Everything a data thread needs to address the tables, its scratch rows and its columns
@@ -320,62 +263,49 @@ __device__ __forceinline__ void window_admit(const Rows<MM> &A, const Win2 &L, i
 // PRODUCER: it walks the sentence, the LCG ledger, the window bookkeeping and the negative draws ONE STEP
 // AHEAD and hands the lists over through a double-buffered LDS record.  The data wavefronts never wait for
 // the scalar work of a step (it was 25-30 % of the step time when wavefront 0 did both).
-// Barrier discipline (worker_barrier): per step the data wavefronts meet once per target chunk (the cross-wavefront
-// sum of the dot products; with s_barrier the producer has to execute those too, after its own work) and all
+// Barrier discipline: per step the data wavefronts meet once per target chunk (the cross-wavefront sum of the dot
+// products; s_barrier counts every wavefront, so the producer executes those too, after its own work) and all
 // wavefronts of the worker meet once at the end of the step.
 // UC: the radius is window-1 (the two outermost context rows of a step are register-held).
 template <int QM, bool LOSS, int MM, bool UC>
-__global__ void __launch_bounds__(W2B_WPG * 64 * (W2B_NDWMAX + 1), W2B_RES_WAVES)
-k_train_resident(const W2bParams P, const long long max_positions, const int R, const int NDW,
-                 const int lds_ints_per_worker) {
+__global__ void __launch_bounds__(64 * (W2B_NDWMAX + 1), W2B_RES_WAVES)
+k_train_resident(const W2bParams P, const long long max_positions, const int R, const int NDW) {
   extern __shared__ int smem[];
   const int WPT = (NDW + 1) * 64;                        // threads per worker
-  // which worker of this workgroup: the same for all lanes of a wavefront (WPT is a multiple of 64) -- said so with
-  // readfirstlane, or every LDS address and with it the whole control flow would count as divergent
-  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x / WPT);
-  W2B_LDS int *const smem_lds = (W2B_LDS int *)smem + half * lds_ints_per_worker;
+  W2B_LDS int *const smem_lds = (W2B_LDS int *)smem;
   const Win2 L0 = carve_win2(smem_lds, 0);
   const Win2 L1 = carve_win2(smem_lds, 1);
   const Win2 &L = L0;                                   // everything that is not double buffered
   W2B_LDS WorkerLds *S = &L.w->S.w;
   W2B_LDS int *s_sen = L.w->sen;
-  const int tid = (int)threadIdx.x - half * WPT, lane = tid & 63, wave = tid >> 6;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool producer = (wave == NDW);
-  const int wid = (int)blockIdx.x * W2B_WPG + half;
+  const int wid = (int)blockIdx.x;
   W2bWorker *G = P.workers + (wid < P.num_threads ? wid : 0);
   const bool valid = wid < P.num_threads && !G->done;
-  QParam qp;
-  qp.bitlevel = P.bitlevel;
-  qp.steps_i = (P.bitlevel >= 4) ? (1 << (P.bitlevel - 1)) : 1;
-  qp.steps_f = (float)qp.steps_i;
+  const QParam qp = make_qparam(P);
   const int NS = 2 * R + 1;
   const XHot XH = xhot_here(P);
   const int NH = XH.nv;                     // leading rows of v that live in this XCD's copies
   const Rows<MM> A{P, (long long)wid * 2 * NS, NS, P.dim, tid * 4, !producer && tid * 4 < P.dim, XH.cv, XH.ev, XH.lv, NH};
   const bool active = A.active;
   if (valid) {
-    for (int i = tid; i < G->sen_len; i += WPT) s_sen[i] = G->sen[i];
+    copy_sentence(s_sen, G->sen, G->sen_len, tid, WPT);
     for (int i = tid; i < NS; i += WPT) { L.w->slot_row[i] = -1; L.w->slot_ref[i] = 0; L.w->pos_slot[i] = 0; L.w->slot_gen[i] = 0; }
     for (int i = tid; i < W2B_NJ; i += WPT) { L.w->ja[i] = P.jump_a[i]; L.w->jc[i] = P.jump_c[i]; }
-    if (tid == 0) {
-      S->rng = G->rng; S->cursor = G->cursor; S->wc = G->word_count; S->last_wc = G->last_word_count;
-      S->sen_len = G->sen_len; S->sen_pos = G->sen_pos; S->override_ = G->first_override;
-      S->eof = 0; S->done = 0; S->cw = 0; S->nt = 0; S->alpha = 0.f;
-      L.w->S.clo = 0; L.w->S.chi = -1;
-      L.w->S.bar_step = 0u; L.w->S.bar_chunk = 0u;
-      L.w->S.loss_reg = 0.0;
-    }
+    if (tid == 0) { worker_restore(G, S); L.w->S.clo = 0; L.w->S.chi = -1; L.w->S.loss_reg = 0.0; }
   }
-  __syncthreads();            // the only workgroup-wide barrier: every wavefront of both workers is still here
+  __syncthreads();
   if (!valid) return;
-  W2B_LDS unsigned *const bar_step = &L.w->S.bar_step, *const bar_chunk = &L.w->S.bar_chunk;
-  unsigned n_step = 0u, n_chunk = 0u;       // barriers passed so far (identical in every wavefront of the worker)
 #ifdef W2B_PHASE_TIMERS
   const bool timing_ = (wid == 0) && (wave == 0 || wave == NDW) && lane == 0;
   unsigned long long tick_ = __builtin_readcyclecounter();
 #endif
   double loss_acc = 0.0;     // producer wavefront only: log-sigmoid terms (the data wavefronts carry nothing around their loop)
   const int W = P.window, K = P.negative;
+  // the LCG jump-ahead constants of the producer's draws come from the LDS copy of the table
+  auto jump_d = [&](unsigned long long x, int d) { return L.w->ja[d] * x + L.w->jc[d]; };
+  auto jump_all = [&](unsigned long long x) { return L.w->ja[K] * x + L.w->jc[K]; };
   // producer registers: the unigram-table gather and the alpha load of the NEXT step are issued at the end
   // of a preparation, so that their latency is not on the producer's critical path either
   int t_pref = 0;
@@ -407,36 +337,22 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
       int p = 0, b = 0, word = 0;
       bool train = false;
       if (!last) {
-        if (wc - last_wc > 10000) {                                    // ref :379-393
-          if (lane == 0) {
-            const unsigned long long d = (unsigned long long)(wc - last_wc);
-            const unsigned long long wca = atomicAdd(&P.shared->word_count_actual, d) + d;
-            const long long wca_all = w2b_global_progress(P, (long long)wca);
-            float a = P.starting_alpha * (1.f - (float)wca_all / (float)(P.iter * P.train_words + 1));
-            if ((double)a < (double)P.starting_alpha * 0.0001) a = (float)((double)P.starting_alpha * 0.0001);
-            __hip_atomic_store(&P.shared->alpha, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            alpha_own = a;
-          }
-          alpha_own = __shfl(alpha_own, 0, 64);
-          alpha_set = true;                              // this worker's own write is the newest value it may see
-          last_wc = wc;
-        }
+        // (this worker's own write is the newest value of alpha it may see)
+        alpha_set = alpha_schedule_step(P, wc, last_wc, lane, &alpha_own);   // ref :379-393
         if (sen_len == 0) {                                            // ref :394-413
           read_sentence(P, (int *)s_sen, rng, cursor, wc, ovr, eof, sen_len, lane);
           sen_pos = 0;
           new_sentence = true;
           W2B_WAVE_SYNC();
         }
-        if (eof || wc > P.train_words / P.total_threads) {            // ref :414-423
-          if (lane == 0) atomicAdd(&P.shared->word_count_actual, (unsigned long long)(wc - last_wc));
-          last_wc = wc;
+        if (eof || wc > P.train_words / P.total_threads) {            // ref :414-423 (local_iter == 1)
+          epoch_end(P, wc, last_wc, lane);
           done = 1;
         } else {
           train = true;
           p = sen_pos;
           word = (sen_len > 0) ? s_sen[p] : 0;                          // ref :424
-          rng = rng * W2B_LCG_A + W2B_LCG_C;                            // ref :428-429
-          b = (int)fast_mod(rng, (unsigned long long)W, P.window_magic);
+          b = window_draw(P, rng);                                      // ref :428-429
           if (sen_len > 0) { lo = max(0, p - R); hi = min(sen_len - 1, p + R); }
         }
       }
@@ -573,24 +489,7 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
           cdup = dupf;
         }
         if (cw > 0) {                                                    // ref :450-460
-          int cnt = 0;
-          for (int d0 = 1; d0 <= K; d0 += 64) {
-            const int d = d0 + lane;
-            bool keep = false;
-            int t = 0;
-            if (d <= K) {
-              const unsigned long long x = (L.w->ja[d] * rng + L.w->jc[d]);
-              t = (pref_ok && d0 == 1) ? t_pref : P.table[fast_mod(x >> 16, (unsigned long long)P.table_size, P.table_magic)];
-              if (t == 0) t = (int)(x % (unsigned long long)(P.vocab_size - 1)) + 1;
-              keep = (t != word);
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) O.s->tgt[1 + cnt + __popcll(m & lane_lt_mask(lane))] = t;
-            cnt += __popcll(m);
-          }
-          if (lane == 0) O.s->tgt[0] = word;
-          nt = 1 + cnt;
-          rng = (L.w->ja[K] * rng + L.w->jc[K]);
+          nt = draw_targets<false>(P, O.s->tgt, word, rng, jump_d, jump_all, pref_ok, t_pref, lane);
           alpha = alpha_set ? alpha_own
                             : (alpha_pref_ok ? alpha_pref
                                              : __hip_atomic_load(&P.shared->alpha, __ATOMIC_RELAXED,
@@ -599,15 +498,10 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
         }
         const int nq = p + 1 + R;                                        // enters the window at the next step
         next_row = (p + 1 < sen_len && nq < sen_len) ? s_sen[nq] : -1;
-        sen_pos++;                                                       // ref :505-509
-        if (sen_pos >= sen_len) sen_len = 0;
+        next_position(sen_pos, sen_len);                                 // ref :505-509
         // ---- prefetch for the next step (valid unless the next step starts with a sentence read, whose
         // sub-sampling draws come first in the LCG ledger)
-        if (sen_len != 0 && lane < K) {                                       // lane l serves draw d = l + 1
-          const unsigned long long xb = rng * W2B_LCG_A + W2B_LCG_C;     // the next step's window draw
-          const unsigned long long x = (L.w->ja[lane + 1] * xb + L.w->jc[lane + 1]);
-          t_pref = P.table[fast_mod(x >> 16, (unsigned long long)P.table_size, P.table_magic)];
-        }
+        if (sen_len != 0 && lane < K) t_pref = table_prefetch(P, rng, jump_d, lane);
         alpha_pref = __hip_atomic_load(&P.shared->alpha, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (lane == 0) {
@@ -629,7 +523,7 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
   // same s_barrier sequence per step.
   if (producer) {
     prepare(L0, max_positions == 0);
-    worker_barrier(bar_step, (unsigned)(NDW + 1) * ++n_step, lane);
+    __syncthreads();
     for (long long it = 0;; ++it) {
       const Win2 &I = (it & 1) ? L1 : L0;                 // this step's lists
       const bool stop = I.s->st.stop != 0;
@@ -640,27 +534,17 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
         // step buffer, which nobody writes again before this wavefront has passed the next end-of-step barrier.
         const Win2 &Q = (it & 1) ? L0 : L1;               // the previous step's lists
         const int ntp = Q.s->st.cw > 0 ? Q.s->st.nt : 0;
-        for (int i = lane; i < ntp; i += 64) {
-          const float f = Q.s->lossf[i];
-          const float dp = (i == 0) ? f : -f;                           // target 0 is the centre word (label 1)
-          float sg;
-          if (dp > 6.f) sg = 1.f;
-          else if (dp < -6.f) sg = 1e-9f;
-          else sg = 1.f / (1.f + expf(-dp));
-          loss_acc += (double)logf(sg);
-        }
+        for (int i = lane; i < ntp; i += 64) loss_acc += (double)log_sigmoid_term(Q.s->lossf[i], i == 0);   // target 0 is the centre word
       }
       W2B_TICK(2);
       if (!stop) prepare((it & 1) ? L0 : L1, it + 1 == max_positions);
       W2B_TICK(0);
-#if W2B_WPG == 1
       for (int i = 0; i < I.s->st.nck; i++) __syncthreads();               // s_barrier counts every wavefront: the chunk barriers too
-#endif
-      worker_barrier(bar_step, (unsigned)(NDW + 1) * ++n_step, lane);   // lists of the next step are published; this step is done
+      __syncthreads();                                    // lists of the next step are published; this step is done
       if (stop) break;                                    // (a stop pass trains nothing: no loss terms are left over)
     }
   } else {
-    worker_barrier(bar_step, (unsigned)(NDW + 1) * ++n_step, lane);
+    __syncthreads();
     for (long long it = 0;; ++it) {
       const Win2 &I = (it & 1) ? L1 : L0;                 // this step's lists
       const bool stop = I.s->st.stop != 0;
@@ -836,18 +720,13 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
 #pragma unroll
         for (int e = 0; e < 4; e++) asm volatile("" : "+v"(apre.e[e]));
         W2B_TICK(5);
-        worker_barrier(bar_chunk, (unsigned)NDW * ++n_chunk, lane);
+        __syncthreads();
         W2B_TICK(6);
         float gl = 0.f;
         if (lane < n) {
           float f = 0.f;
           for (int w = 0; w < NDW; w++) f += red[lane * W2B_NDWMAX + w];       // the plain kernel's order over wavefronts
-          const float label = (start + lane == 0) ? 1.f : 0.f;                 // target 0 is the centre word
-          float g;
-          if (f > 6.f) g = (label - 1.f) * alpha;
-          else if (f < -6.f) g = label * alpha;
-          else g = (label - P.exp_table[(int)((f + 6.f) * 83.f)]) * alpha;
-          gl = g;
+          gl = grad_scalar(f, start + lane == 0, alpha, P.exp_table);          // target 0 is the centre word
           if (LOSS && wave == 0) I.s->lossf[start + lane] = f;     // the producer wavefront books log(sigmoid) next step
         }
         if (LOSS && P.reg != 0.f) {            // reg * sum q^2 over the chunk's target rows (ref :469,481), re-derived
@@ -954,12 +833,11 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
         merge_cursor += P.xhot_m;
       }
       W2B_TICK(8);
-      worker_barrier(bar_step, (unsigned)(NDW + 1) * ++n_step, lane);   // lists of the next step are published; this step is done
+      __syncthreads();                                    // lists of the next step are published; this step is done
       if (stop) break;
     }
   }
-  const int sl = S->sen_len;
-  for (int i = tid; i < sl; i += WPT) G->sen[i] = s_sen[i];
+  copy_sentence(G->sen, s_sen, S->sen_len, tid, WPT);
   if (LOSS && producer) {       // producer lanes hold the log-sigmoid terms; the regularisation terms were summed in LDS
     const double lsum = wave_sum_d(loss_acc);
     if (lane == 0) {
@@ -967,11 +845,7 @@ k_train_resident(const W2bParams P, const long long max_positions, const int R, 
       atomicAdd(&P.shared->loss_epoch, lsum + L.w->S.loss_reg);       // what w2b_epoch_poll reports without a per-worker copy
     }
   }
-  if (tid == 0) {
-    G->rng = S->rng; G->cursor = S->cursor; G->word_count = S->wc; G->last_word_count = S->last_wc;
-    G->sen_len = S->sen_len; G->sen_pos = S->sen_pos; G->first_override = S->override_;
-    if (S->done) { G->done = 1; atomicAdd(&P.shared->workers_done, 1); }
-  }
+  if (tid == 0) worker_save(P, G, S);
 }
 
 }  // namespace
@@ -996,17 +870,15 @@ bool w2b_resident_atomic_ok(const W2bParams &p, int R) { return p.tab_bytes != 0
 // rows of scratch ("entry") memory per worker
 long long w2b_resident_scratch_rows(int R) { return 2ll * (2 * R + 1); }
 
-// workgroups of the sentence-resident kernel that are resident per CU (occupancy query of the instantiation
-// that would run)
 static size_t win2_lds_per_worker(const W2bParams &p, int R) {
   return (win2_lds_bytes(p.dim, p.window, p.negative, R) + 15) & ~(size_t)15;
 }
 
-// WORKERS of the sentence-resident kernel that are resident per CU (occupancy query of the instantiation that would
-// run: workgroups per CU x W2B_WPG workers per workgroup)
+// workers (= workgroups) of the sentence-resident kernel that are resident per CU (occupancy query of the instantiation
+// that would run)
 int w2b_resident_per_cu(const W2bParams &p, int R, bool loss) {
-  const size_t lds = W2B_WPG * win2_lds_per_worker(p, R);
-  const int threads = W2B_WPG * win2_threads(p.dim);
+  const size_t lds = win2_lds_per_worker(p, R);
+  const int threads = win2_threads(p.dim);
   int nb = 0;
   (void)dispatch_q(p.bitlevel, [&](auto qm) -> hipError_t {
     constexpr int QM = decltype(qm)::value;
@@ -1014,29 +886,26 @@ int w2b_resident_per_cu(const W2bParams &p, int R, bool loss) {
     if (loss) return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_train_resident<QM, true, 0, false>, threads, lds);
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_train_resident<QM, false, 0, false>, threads, lds);
   });
-  return (nb > 0 ? nb : 1) * W2B_WPG;
+  return nb > 0 ? nb : 1;
 }
 
 // Coherent rows only (memory mode 0): with relaxed rows the launcher of the trainer picks the plain kernel.
 hipError_t w2b_launch_resident(const W2bParams &p, long long max_positions, int R, bool loss, hipStream_t s, bool debug) {
-  const int wthreads = win2_threads(p.dim);  // data wavefronts (one thread per 16-byte column) + 1 producer wavefront
-  const int NDW = wthreads / 64 - 1;
-  const size_t wlds = win2_lds_per_worker(p, R);
-  const int threads = W2B_WPG * wthreads, grid = (p.num_threads + W2B_WPG - 1) / W2B_WPG;
-  const size_t lds = W2B_WPG * wlds;
-  const int lds_ints = (int)(wlds / 4);
+  const int threads = win2_threads(p.dim);  // data wavefronts (one thread per 16-byte column) + 1 producer wavefront
+  const int NDW = threads / 64 - 1, grid = p.num_threads;
+  const size_t lds = win2_lds_per_worker(p, R);
   static bool reported = false;
   if (!reported && debug) {
     reported = true;
     int nb = -1;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_train_resident<1, false, 0, false>, threads, lds);
-    fprintf(stderr, "w2b debug: sentence-resident kernel R=%d hot=%d lds=%zu B/worker threads=%d/worker, %d workers per workgroup, resident workgroups/CU=%d\n", R, p.xhot ? p.xhot_v : 0, wlds, wthreads, W2B_WPG, nb);
+    fprintf(stderr, "w2b debug: sentence-resident kernel R=%d hot=%d lds=%zu B/worker threads=%d/worker, resident workgroups/CU=%d\n", R, p.xhot ? p.xhot_v : 0, lds, threads, nb);
   }
   return dispatch_q(p.bitlevel, [&](auto qm) -> hipError_t {
     constexpr int QM = decltype(qm)::value;
     // template MM carries the memory mode in bits 0-2 (0: agent-scope rows), "tables >= 2 GiB" (per-row descriptors) in bit 3
     // and "atomic adds for rows 1..atomic_rank" in bit 4 (small-table form and radius == window only: w2b_resident_atomic_ok)
-#define W2B_LAUNCH_R(LOSS, MMV, UCV) hipLaunchKernelGGL((k_train_resident<QM, LOSS, MMV, UCV>), dim3(grid), dim3(threads), lds, s, p, max_positions, R, NDW, lds_ints)
+#define W2B_LAUNCH_R(LOSS, MMV, UCV) hipLaunchKernelGGL((k_train_resident<QM, LOSS, MMV, UCV>), dim3(grid), dim3(threads), lds, s, p, max_positions, R, NDW)
 #define W2B_LAUNCH_R2(MMV, UCV) do { if (loss) W2B_LAUNCH_R(true, MMV, UCV); else W2B_LAUNCH_R(false, MMV, UCV); } while (0)
     if (R < p.window) { if (p.tab_bytes) W2B_LAUNCH_R2(0, true); else W2B_LAUNCH_R2(8, true); }
     else if (p.atomic_rank > 0 && p.tab_bytes) W2B_LAUNCH_R2(16, false);

@@ -20,10 +20,7 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
   XHot XH = xhot_here(P);
   if (!hot) { XH.nu = 0; XH.nv = 0; }
   int since_merge = 0, merge_cursor = (int)(blockIdx.x >> 3) * P.xhot_m;   // (workgroup b runs on XCD b % 8: take turns)
-  QParam qp;
-  qp.bitlevel = P.bitlevel;
-  qp.steps_i = (P.bitlevel >= 4) ? (1 << (P.bitlevel - 1)) : 1;
-  qp.steps_f = (float)qp.steps_i;
+  const QParam qp = make_qparam(P);
   double loss_acc = 0.0;
   const int K = P.negative;
   for (long long i = blockIdx.x; i < n; i += gridDim.x) {

@@ -17,17 +17,9 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
   if (wid >= P.num_threads) return;
   W2bWorker *G = P.workers + wid;
   if (G->done) return;
-  QParam qp;
-  qp.bitlevel = P.bitlevel;
-  qp.steps_i = (P.bitlevel >= 4) ? (1 << (P.bitlevel - 1)) : 1;
-  qp.steps_f = (float)qp.steps_i;
-  // restore the worker
-  for (int i = tid; i < G->sen_len; i += blockDim.x) s_sen[i] = G->sen[i];
-  if (tid == 0) {
-    S->rng = G->rng; S->cursor = G->cursor; S->wc = G->word_count; S->last_wc = G->last_word_count;
-    S->sen_len = G->sen_len; S->sen_pos = G->sen_pos; S->override_ = G->first_override;
-    S->eof = 0; S->done = 0; S->cw = 0; S->nt = 0; S->alpha = 0.f;
-  }
+  const QParam qp = make_qparam(P);
+  copy_sentence(s_sen, G->sen, G->sen_len, tid, blockDim.x);
+  if (tid == 0) worker_restore(G, S);
   __syncthreads();
   double loss_acc = 0.0;
   // this XCD's copies of the hottest rows of u and v (16-byte columns, coherent rows, not in the parity mode)
@@ -35,7 +27,7 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
   XHot XH = xhot_here(P);
   if (!hot) { XH.nu = 0; XH.nv = 0; }
   int since_merge = 0, merge_cursor = (wid >> 3) * P.xhot_m;      // (workgroup b runs on XCD b % 8: take turns)
-  const int W = P.window, K = P.negative;
+  const int W = P.window;
   for (long long it = 0; it < max_positions; ++it) {
     if (wave == 0) {
       unsigned long long rng = S->rng;
@@ -43,31 +35,18 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
       int sen_len = S->sen_len, sen_pos = S->sen_pos, ovr = S->override_, eof = S->eof;
       int done = 0, cw = 0, nt = 0;
       float alpha = 0.f;
-      if (wc - last_wc > 10000) {                                    // ref :379-393
-        if (lane == 0) {
-          const unsigned long long d = (unsigned long long)(wc - last_wc);
-          const unsigned long long wca = atomicAdd(&P.shared->word_count_actual, d) + d;
-          const long long wca_all = w2b_global_progress(P, (long long)wca);
-          float a = P.starting_alpha * (1.f - (float)wca_all / (float)(P.iter * P.train_words + 1));
-          if ((double)a < (double)P.starting_alpha * 0.0001) a = (float)((double)P.starting_alpha * 0.0001);
-          __hip_atomic_store(&P.shared->alpha, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        last_wc = wc;
-      }
+      alpha_schedule_step(P, wc, last_wc, lane);                     // ref :379-393 (alpha is loaded again below, after the draws)
       if (sen_len == 0) {                                            // ref :394-413
         read_sentence(P, s_sen, rng, cursor, wc, ovr, eof, sen_len, lane);
         sen_pos = 0;
         W2B_WAVE_SYNC();
       }
       if (eof || wc > P.train_words / P.total_threads) {              // ref :414-423 (local_iter == 1)
-        if (lane == 0)
-          atomicAdd(&P.shared->word_count_actual, (unsigned long long)(wc - last_wc));
-        last_wc = wc;
+        epoch_end(P, wc, last_wc, lane);
         done = 1;
       } else {
         const int word = (sen_len > 0) ? s_sen[sen_pos] : 0;          // ref :424
-        rng = rng * W2B_LCG_A + W2B_LCG_C;                            // ref :428-429
-        const int b = (int)fast_mod(rng, (unsigned long long)W, P.window_magic);
+        const int b = window_draw(P, rng);                            // ref :428-429
         const int hi = 2 * W + 1 - b;
         for (int a0 = b; a0 < hi; a0 += 64) {                         // ref :431-436
           const int a = a0 + lane;
@@ -78,29 +57,12 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
           cw += __popcll(m);
         }
         if (cw > 0) {                                                 // ref :450-460
-          int cnt = 0;
-          for (int d0 = 1; d0 <= K; d0 += 64) {
-            const int d = d0 + lane;
-            bool keep = false;
-            int t = 0;
-            if (d <= K) {
-              const unsigned long long x = lcg_jump(P, rng, d);
-              t = P.table[fast_mod(x >> 16, (unsigned long long)P.table_size, P.table_magic)];
-              if (t == 0) t = (int)(x % (unsigned long long)(P.vocab_size - 1)) + 1;
-              keep = (t != word);
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) L.tgt[1 + cnt + __popcll(m & lane_lt_mask(lane))] = t;
-            cnt += __popcll(m);
-          }
-          if (lane == 0) L.tgt[0] = word;
-          nt = 1 + cnt;
-          rng = lcg_jump(P, rng, K);
+          nt = draw_targets<false>(P, L.tgt, word, rng, [&](unsigned long long x, int d) { return lcg_jump(P, x, d); },
+                                   [&](unsigned long long x) { return lcg_jump(P, x, P.negative); }, false, 0, lane);
           alpha = __hip_atomic_load(&P.shared->alpha, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           prep_lists<TFor<LOSS>::value, int *>(L.tgt, L.prev, L.cend, nt, L.ctx, L.umult, cw, lane);
         }
-        sen_pos++;                                                    // ref :505-509
-        if (sen_pos >= sen_len) sen_len = 0;
+        next_position(sen_pos, sen_len);                              // ref :505-509
       }
       if (lane == 0) {
         S->rng = rng; S->cursor = cursor; S->wc = wc; S->last_wc = last_wc;
@@ -125,8 +87,7 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
   }
   // save the worker
   __syncthreads();
-  const int sl = S->sen_len;
-  for (int i = tid; i < sl; i += blockDim.x) G->sen[i] = s_sen[i];
+  copy_sentence(G->sen, s_sen, S->sen_len, tid, blockDim.x);
   double lsum = 0.0;
   if (LOSS) {
     // wave 0 holds the log-sigmoid terms on its lanes; lane 0 of every wave holds reg terms
@@ -134,10 +95,8 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
     else if (lane == 0 && loss_acc != 0.0) { atomicAdd(&G->loss, loss_acc); atomicAdd(&P.shared->loss_epoch, loss_acc); }
   }
   if (tid == 0) {
-    G->rng = S->rng; G->cursor = S->cursor; G->word_count = S->wc; G->last_word_count = S->last_wc;
-    G->sen_len = S->sen_len; G->sen_pos = S->sen_pos; G->first_override = S->override_;
     if (LOSS) { atomicAdd(&G->loss, lsum); atomicAdd(&P.shared->loss_epoch, lsum); }
-    if (S->done) { G->done = 1; atomicAdd(&P.shared->workers_done, 1); }
+    worker_save(P, G, S);
   }
 }
 
