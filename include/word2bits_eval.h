@@ -96,6 +96,40 @@ int w2b_eval_set_kernel(w2b_eval *e, int32_t variant);
  * top-k time includes its merge kernel) since load or since the last call; `macs` = multiply-adds those launches performed (questions x padded rows x padded size). */
 int w2b_eval_timing_read(w2b_eval *e, double *kernel_ms, int64_t *launches, double *macs);
 
+/* ---- bits mode: the exact integer scan on bit-packed 1-bit vectors ------------------------------------------------
+ * A 1-bit model is one sign per value and is stored that way (include/word2bits_corpus.h).  The same opaque w2b_eval in
+ * a second mode keeps the rows packed on the device -- [words][ceil(size / 64)] 64-bit words, 1/32 of the float matrix
+ * -- and scans them with xor + popcount (word2bits_amd/csrc/w2b_kernels_evalbits.hip).  All 1-bit rows have the same
+ * length, so the cosine ranking is the ranking of the integer
+ *     I(c) = sum_a (s_b2[a] - s_b1[a] + s_b3[a]) * s_c[a] = size - 2 * (H(b2,c) - H(b1,c) + H(b3,c))
+ * where s_r[a] = -1 where the packed SIGN bit of row r, column a is set (quantize(x, 1) < 0) and +1 elsewhere, and H is
+ * the Hamming distance over the `size` columns.  The answer list of a question: the rows c other than b1, b2, b3 with
+ * I(c) > 0, by I descending, equal I in ascending row order, k of them, a short list ending in row -1 / score 0.  The
+ * reported score is (float)I / (float)size, one correctly rounded division.  The fp32 modes above agree with this
+ * ranking wherever I differs and order rows of equal I by rounding noise instead; a row with I == 0, which they
+ * sometimes score as a tiny positive number, is never an answer here.
+ * On a bits handle w2b_eval_top1 / _topk / _neighbors / _nearest_text / _transcript / _set_topk_scratch /
+ * _timing_read (macs = questions x rows x size) work with these semantics, w2b_eval_set_kernel does nothing and
+ * w2b_eval_get_matrix is W2B_EINVAL.
+ * Two-bit models are out of scope: their rows differ in length, so the ranking needs a per-row float scale. */
+
+/* FILE is a bit-packed .w2bp of bitlevel 1, read without expanding it (bitlevel 2: W2B_EINVAL), or a file of the
+ * reference's binary format, each value reduced to its sign by the bitlevel-1 rule of ref :26-61 (negative iff
+ * num < 0: +0, -0 and NaN are positive).  `threshold` caps the rows as in w2b_eval_load; W2B_EIO "Input file not
+ * found" when the file cannot be opened. */
+int w2b_eval_load_bits(const char *file, int64_t threshold, int32_t device, w2b_eval **out);
+/* The same on a live trainer at -bitlevel 1 (else W2B_EINVAL): the rows are packed on the device from u + v, no float
+ * leaves it.  What w2b_eval_load_bits holds after the trainer's vectors have been written with -packed. */
+int w2b_eval_bits_from_trainer(struct w2b_trainer *t, int64_t n_words, const char *const *words, int64_t threshold,
+                               w2b_eval **out);
+int32_t w2b_eval_is_bits(const w2b_eval *e);
+/* the packed rows, [words][ceil(size / 64)] in the file's layout; W2B_EINVAL on a float handle */
+int w2b_eval_get_bits(w2b_eval *e, uint64_t *out);
+/* Host twin of the bits kernels (pure C, no device; for tests, as w2b_quantize is for the device quantizer): I(c) of the
+ * question (b1, b2, b3) for EVERY row c of packed[words][ceil(dim / 64)], b1, b2, b3 included, into I_out[words]. */
+int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
+                         int32_t *I_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,11 @@ SIGNATURES = {
     "w2b_eval_free_text": (None, [vp]),
     "w2b_eval_set_kernel": (C.c_int, [vp, C.c_int32]),
     "w2b_eval_timing_read": (C.c_int, [vp, f64p, i64p, f64p]),
+    "w2b_eval_load_bits": (C.c_int, [C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp)]),
+    "w2b_eval_bits_from_trainer": (C.c_int, [vp, C.c_int64, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(vp)]),
+    "w2b_eval_is_bits": (C.c_int32, [vp]),
+    "w2b_eval_get_bits": (C.c_int, [vp, u64p]),
+    "w2b_bits_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p]),
 }
 
 _lib = None

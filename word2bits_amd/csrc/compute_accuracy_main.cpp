@@ -1,9 +1,11 @@
 // compute_accuracy_main.cpp -- drop-in for the reference's evaluator program (ref src/compute-accuracy.c:63-189):
-//   ./compute_accuracy <FILE> <bitlevel> <threshold> [fma|nofma] < questions-words.txt
+//   ./compute_accuracy <FILE> <bitlevel> <threshold> [fma|nofma|bits] < questions-words.txt
 // Same positional arguments, same stdout.  The scan runs on the MI355X through include/word2bits_eval.h.
 // The optional 4th argument (or W2B_EVAL_FUSED=0|1) selects which build of the reference the scores are
 // bit-identical to: "fma" (default; the reference's own Makefile flags on an FMA-capable host) or "nofma"
 // (-ffp-contract=off).  The reference ignores a 4th argument, so scripts can pass it to both.
+// "bits" (1-bit models only; <bitlevel> is ignored) keeps the rows bit-packed and answers by the exact integer score
+// with ties to the lowest row (include/word2bits_eval.h, "bits mode"); the transcript keeps the reference's format.
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 
@@ -17,6 +19,10 @@ int main(int argc, char **argv) {
     printf("Usage: ./compute-accuracy <FILE> <bitlevel> <threshold>\nwhere FILE contains word projections, and "
            "threshold is used to reduce vocabulary of the model for fast approximate evaluation (0 = off, "
            "otherwise typical value is 30000)\n");
+    // (stdout is the reference's, byte for byte; what this program adds goes to stderr)
+    fprintf(stderr, "Optional 4th argument: fma (default) | nofma = the build of the reference whose arithmetic is "
+                    "reproduced; bits = 1-bit models only: exact integer scores on the bit-packed rows, ties to the lowest "
+                    "row (<bitlevel> is ignored)\n");
     return 0;
   }
   const int bitlevel = argc > 2 ? atoi(argv[2]) : 0;          // ref :78
@@ -28,7 +34,9 @@ int main(int argc, char **argv) {
   if (const char *env = getenv("W2B_DEVICE")) device = atoi(env);
 
   w2b_eval *e = nullptr;
-  const int rc = w2b_eval_load(argv[1], bitlevel, threshold, fused, device, &e);
+  const bool bits = argc > 4 && !strcmp(argv[4], "bits");
+  const int rc = bits ? w2b_eval_load_bits(argv[1], threshold, device, &e)
+                      : w2b_eval_load(argv[1], bitlevel, threshold, fused, device, &e);
   if (rc == W2B_EIO && !strcmp(w2b_last_error(), "Input file not found")) {
     printf("Input file not found\n");                          // ref :81-84
     return -1;

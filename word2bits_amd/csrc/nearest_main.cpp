@@ -1,9 +1,10 @@
 // nearest_main.cpp -- what is near a word, and the best few answers to an analogy:
-//   ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma] < queries
+//   ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits] < queries
 // FILE is a vectors file in the reference's binary format or a bit-packed .w2bp file, loaded exactly like
 // ./compute_accuracy loads it (ref src/compute-accuracy.c:80-112).  One query per input line: one word = its k
 // nearest words, three words A B C = the k best answers to "A is to B as C is to ?" (ref :155-177 with N = k).
 // All lines are scored in one batch on the MI355X; the output format is that of w2b_eval_nearest_text.
+// "bits" (1-bit models only; bitlevel is ignored): exact integer scores on the bit-packed rows, ties to the lowest row.
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 
@@ -14,9 +15,10 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    printf("Usage: ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma] < queries\nwhere FILE contains word "
+    printf("Usage: ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits] < queries\nwhere FILE contains word "
            "projections and every input line is one word (its k nearest words) or three words A B C (the k best "
-           "answers to A : B = C : ?); 1 <= k <= %d\n", W2B_EVAL_MAX_K);
+           "answers to A : B = C : ?); 1 <= k <= %d; bits = 1-bit models only: exact integer scores on the bit-packed "
+           "rows, ties to the lowest row (bitlevel is ignored)\n", W2B_EVAL_MAX_K);
     return 0;
   }
   const int k = argc > 2 ? atoi(argv[2]) : 10;
@@ -33,7 +35,9 @@ int main(int argc, char **argv) {
   if (const char *env = getenv("W2B_DEVICE")) device = atoi(env);
 
   w2b_eval *e = nullptr;
-  const int rc = w2b_eval_load(argv[1], bitlevel, threshold, fused, device, &e);
+  const bool bits = argc > 5 && !strcmp(argv[5], "bits");
+  const int rc = bits ? w2b_eval_load_bits(argv[1], threshold, device, &e)
+                      : w2b_eval_load(argv[1], bitlevel, threshold, fused, device, &e);
   if (rc == W2B_EIO && !strcmp(w2b_last_error(), "Input file not found")) {
     printf("Input file not found\n");
     return -1;

@@ -498,8 +498,8 @@ extern "C" int w2b_save_vectors_packed(const char *path, const w2b_corpus *c, co
 
 // A packed file in memory -> its vocabulary and unpacked rows.  Shared with the evaluator's loader (w2b_eval.cpp).
 bool w2b_internal_is_packed(const unsigned char *d, size_t n) { return n >= 6 && !memcmp(d, "W2BP1 ", 6); }
-int w2b_internal_parse_packed(const unsigned char *d, size_t n, std::vector<std::string> &words, std::vector<float> &values,
-                              int64_t *dim_out) {
+int w2b_internal_parse_packed_head(const unsigned char *d, size_t n, std::vector<std::string> &words, int64_t *dim_out,
+                                   int *bitlevel_out, size_t *data_pos) {
   if (!w2b_internal_is_packed(d, n)) return W2B_EINVAL;
   const unsigned char *nl = (const unsigned char *)memchr(d, '\n', n);
   if (!nl || nl - d > 100) return W2B_EIO;
@@ -520,6 +520,18 @@ int w2b_internal_parse_packed(const unsigned char *d, size_t n, std::vector<std:
     pos = (size_t)(e - d) + 1;
   }
   if (n - pos < (size_t)(V * wpr) * sizeof(uint64_t)) return W2B_EIO;
+  *dim_out = D;
+  *bitlevel_out = bitlevel;
+  *data_pos = pos;
+  return W2B_OK;
+}
+int w2b_internal_parse_packed(const unsigned char *d, size_t n, std::vector<std::string> &words, std::vector<float> &values,
+                              int64_t *dim_out) {
+  int64_t D = 0;
+  int bitlevel = 0;
+  size_t pos = 0;
+  if (int rc = w2b_internal_parse_packed_head(d, n, words, &D, &bitlevel, &pos)) return rc;
+  const int64_t V = (int64_t)words.size(), wpr = w2b_packed_words_per_row(D, bitlevel);
   std::vector<uint64_t> packed((size_t)(V * wpr));
   if (!packed.empty()) memcpy(packed.data(), d + pos, packed.size() * sizeof(uint64_t));     // (unaligned in the file)
   values.assign((size_t)(V * D), 0.f);

@@ -39,6 +39,11 @@ struct w2b_eval {
   std::vector<char> vocab;                              // flat [words * max_w] (+ slack), as ref :88
   std::unordered_map<std::string, int64_t> first;       // upper-cased word -> first row (ref :140)
   float *M = nullptr;                                   // [rows_padded][ld], zero padded, normalised
+  // bits mode (w2b_eval_load_bits / w2b_eval_bits_from_trainer): the rows stay packed and M does not exist
+  int bits = 0;
+  int64_t wpr = 0;                                      // 64-bit words per row
+  uint64_t *B = nullptr;                                // [words][wpr], the file's layout
+  uint32_t *P = nullptr;                                // per-call: the questions' planes [2 * 2 * wpr][cap_q]
   // per-call scratch (grown on demand)
   float *Q = nullptr;
   int32_t *b123 = nullptr;
@@ -57,6 +62,8 @@ static void eval_release(w2b_eval *e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   if (e->M) (void)hipFree(e->M);
+  if (e->B) (void)hipFree(e->B);
+  if (e->P) (void)hipFree(e->P);
   if (e->Q) (void)hipFree(e->Q);
   if (e->b123) (void)hipFree(e->b123);
   if (e->best) (void)hipFree(e->best);
@@ -246,6 +253,169 @@ extern "C" int w2b_eval_from_trainer(w2b_trainer *t, int64_t n_words, const char
   return rc;
 }
 
+// ------------------------------------------------------------------------------------ bits mode: the constructors
+// device side of the two bits constructors: `host_bits` ([words][wpr], may be unaligned) is uploaded, or the rows are
+// produced on the device from the trainer's tables (u != null) on its stream
+static int eval_finish_bits(w2b_eval *e, const unsigned char *host_bits, const float *u, const float *v, hipStream_t ts,
+                            w2b_eval **out) {
+  const long long words = e->words;
+  char *vocab = e->vocab.data();
+  for (long long b = 0; b < words; b++) e->first.emplace(std::string(vocab + b * kMaxW), b);   // first wins
+  auto bail = [&](int rc) { eval_release(e); return rc; };
+  if (hipSetDevice(e->device) != hipSuccess) return bail(efail(W2B_EHIP, "hipSetDevice failed"));
+  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
+    return bail(efail(W2B_EHIP, "hipStreamCreate failed"));
+  const size_t bytes = (size_t)words * (size_t)e->wpr * 8;
+  if (hipMalloc(&e->B, bytes ? bytes : 8) != hipSuccess) return bail(efail(W2B_ENOMEM, "w2b_eval: device allocation failed"));
+  hipError_t he = hipSuccess;
+  if (words > 0 && host_bits) he = hipMemcpy(e->B, host_bits, bytes, hipMemcpyHostToDevice);
+  if (words > 0 && u) {
+    he = w2b_launch_export_packed(u, v, (unsigned long long *)e->B, words, (int)e->size, 1, ts);
+    if (he == hipSuccess) he = hipStreamSynchronize(ts);
+  }
+  if (he != hipSuccess) return bail(efail(W2B_EHIP, std::string("w2b_eval: ") + hipGetErrorString(he)));
+  *out = e;
+  return W2B_OK;
+}
+
+static w2b_eval *eval_new_bits(long long words, long long size, int32_t device) {
+  w2b_eval *e = eval_new(words, size, 1, device);
+  e->bits = 1;
+  e->wpr = (size + 63) / 64;
+  e->ld = 0;
+  return e;
+}
+
+extern "C" int w2b_eval_load_bits(const char *file, int64_t threshold, int32_t device, w2b_eval **out) {
+  if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load_bits: null argument");
+  *out = nullptr;
+  FILE *f = fopen(file, "rb");
+  if (!f) return efail(W2B_EIO, "Input file not found");           // ref :81-84
+  std::vector<unsigned char> d;
+  {
+    fseek(f, 0, SEEK_END);
+    const long long n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    d.resize(n > 0 ? (size_t)n : 0);
+    if (n > 0 && fread(d.data(), 1, (size_t)n, f) != (size_t)n) {
+      fclose(f);
+      return efail(W2B_EIO, "w2b_eval_load_bits: short read");
+    }
+    fclose(f);
+  }
+  const bool packed = w2b_internal_is_packed(d.data(), d.size());
+  std::vector<std::string> names;
+  size_t pos = 0;
+  long long words = 0, size = 0;
+  if (packed) {
+    int64_t dim = 0;
+    int bitlevel = 0;
+    if (w2b_internal_parse_packed_head(d.data(), d.size(), names, &dim, &bitlevel, &pos) != W2B_OK)
+      return efail(W2B_EIO, "w2b_eval_load_bits: damaged bit-packed file");
+    if (bitlevel != 1)
+      return efail(W2B_EINVAL, "w2b_eval_load_bits: a 2-bit model has no integer ranking (rows differ in length); use w2b_eval_load");
+    words = (long long)names.size();
+    size = dim;
+  } else {
+    if (!scan_ll(d, pos, &words)) return efail(W2B_EIO, "w2b_eval_load_bits: no <words> header");
+    if (!scan_ll(d, pos, &size)) return efail(W2B_EIO, "w2b_eval_load_bits: no <size> header");
+  }
+  if (threshold && words > threshold) words = threshold;            // ref :86
+  if (words < 0 || size <= 0 || words > 0x7FFFFF00ll || size > (1 << 24))
+    return efail(W2B_EINVAL, "w2b_eval_load_bits: unsupported <words> <size>");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return efail(W2B_ENOGPU, "w2b_eval_load_bits: no HIP device visible (the evaluator has no CPU fallback)");
+  if (device < 0 || device >= ndev) return efail(W2B_EINVAL, "w2b_eval_load_bits: bad device index");
+
+  w2b_eval *e = eval_new_bits(words, size, device);
+  char *vocab = e->vocab.data();
+  if (packed) {
+    // the names as the reader would see them in the float file of the same model ("word" + ' ' after the '\n' before it)
+    std::string rowbytes;
+    for (long long b = 0; b < words; b++) {
+      rowbytes.assign("\n");
+      rowbytes += names[(size_t)b];
+      rowbytes += ' ';
+      size_t p = 0;
+      read_name((const unsigned char *)rowbytes.data(), rowbytes.size(), p, vocab + b * kMaxW);
+    }
+    return eval_finish_bits(e, d.data() + pos, nullptr, nullptr, nullptr, out);   // the file's words, as they are
+  }
+  // a float file: each row reduced to its signs by the bitlevel-1 rule (ref :26-61: negative iff num < 0)
+  std::vector<uint64_t> hb((size_t)(words * e->wpr), 0ull);
+  for (long long b = 0; b < words; b++) {                           // ref :96-105
+    read_name(d.data(), d.size(), pos, vocab + b * kMaxW);
+    const size_t want = (size_t)size * 4, have = d.size() - pos;
+    const size_t take = (want < have ? want : have) / 4;
+    uint64_t *row = hb.data() + b * e->wpr;
+    for (size_t a = 0; a < take; a++) {
+      float x;
+      memcpy(&x, d.data() + pos + a * 4, 4);
+      if (x < 0.f) row[a >> 6] |= 1ull << (a & 63);
+    }
+    pos = want <= have ? pos + want : d.size();
+  }
+  return eval_finish_bits(e, (const unsigned char *)hb.data(), nullptr, nullptr, nullptr, out);
+}
+
+extern "C" int w2b_eval_bits_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int64_t threshold,
+                                          w2b_eval **out) {
+  if (!t || !out || (n_words > 0 && !words_in)) return efail(W2B_EINVAL, "w2b_eval_bits_from_trainer: null argument");
+  *out = nullptr;
+  float *u = nullptr, *v = nullptr;
+  long long V = 0, D = 0;
+  int tb = 0, dev = 0;
+  hipStream_t ts = nullptr;
+  w2b_internal_trainer_view(t, &u, &v, &V, &D, &tb, &dev, &ts);
+  if (tb != 1) return efail(W2B_EINVAL, "w2b_eval_bits_from_trainer: the trainer must be at -bitlevel 1");
+  if (n_words != V) return efail(W2B_EINVAL, "w2b_eval_bits_from_trainer: one word per vocabulary row is needed");
+  long long words = V;
+  if (threshold && words > threshold) words = threshold;            // ref :86
+  w2b_eval *e = eval_new_bits(words, D, dev);
+  char *vocab = e->vocab.data();
+  std::string rowbytes;
+  for (long long b = 0; b < words; b++) {
+    rowbytes.assign("\n");
+    rowbytes += words_in[b];
+    rowbytes += ' ';
+    size_t pos = 0;
+    read_name((const unsigned char *)rowbytes.data(), rowbytes.size(), pos, vocab + b * kMaxW);
+  }
+  return eval_finish_bits(e, nullptr, u, v, ts, out);
+}
+
+extern "C" int32_t w2b_eval_is_bits(const w2b_eval *e) { return e ? e->bits : 0; }
+
+extern "C" int w2b_eval_get_bits(w2b_eval *e, uint64_t *out) {
+  if (!e || !out) return efail(W2B_EINVAL, "w2b_eval_get_bits: null argument");
+  if (!e->bits) return efail(W2B_EINVAL, "w2b_eval_get_bits: not a bits handle");
+  EHIP(hipSetDevice(e->device));
+  if (e->words > 0) EHIP(hipMemcpy(out, e->B, (size_t)e->words * (size_t)e->wpr * 8, hipMemcpyDeviceToHost));
+  return W2B_OK;
+}
+
+// host twin of the bits kernels: I(c) of every row, from the three Hamming distances of the definition
+extern "C" int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
+                                    int32_t *I_out) {
+  if (!packed || !I_out || words < 0 || dim < 1 || b1 < 0 || b2 < 0 || b3 < 0 || b1 >= words || b2 >= words || b3 >= words)
+    return efail(W2B_EINVAL, "w2b_bits_scores_host: bad argument");
+  const int64_t wpr = (dim + 63) / 64;
+  const uint64_t *r1 = packed + b1 * wpr, *r2 = packed + b2 * wpr, *r3 = packed + b3 * wpr;
+  for (int64_t c = 0; c < words; c++) {
+    const uint64_t *rc = packed + c * wpr;
+    int64_t h1 = 0, h2 = 0, h3 = 0;
+    for (int64_t w = 0; w < wpr; w++) {
+      const uint64_t valid = (w + 1) * 64 <= dim ? ~0ull : (1ull << (dim - w * 64)) - 1;    // padding bits do not count
+      h1 += __builtin_popcountll((r1[w] ^ rc[w]) & valid);
+      h2 += __builtin_popcountll((r2[w] ^ rc[w]) & valid);
+      h3 += __builtin_popcountll((r3[w] ^ rc[w]) & valid);
+    }
+    I_out[c] = (int32_t)(dim - 2 * (h2 - h1 + h3));
+  }
+  return W2B_OK;
+}
+
 extern "C" void w2b_eval_free(w2b_eval *e) { eval_release(e); }
 extern "C" int64_t w2b_eval_words(const w2b_eval *e) { return e ? e->words : 0; }
 extern "C" int64_t w2b_eval_size(const w2b_eval *e) { return e ? e->size : 0; }
@@ -261,6 +431,7 @@ extern "C" int64_t w2b_eval_lookup(const w2b_eval *e, const char *upper_word) {
 
 extern "C" int w2b_eval_get_matrix(w2b_eval *e, float *out) {
   if (!e || !out) return efail(W2B_EINVAL, "w2b_eval_get_matrix: null argument");
+  if (e->bits) return efail(W2B_EINVAL, "w2b_eval_get_matrix: a bits handle holds no float matrix (w2b_eval_get_bits)");
   EHIP(hipSetDevice(e->device));
   if (e->words > 0)
     EHIP(hipMemcpy2D(out, (size_t)e->size * 4, e->M, (size_t)e->ld * 4, (size_t)e->size * 4, (size_t)e->words,
@@ -272,13 +443,96 @@ extern "C" int w2b_eval_get_matrix(w2b_eval *e, float *out) {
 static int eval_reserve_questions(w2b_eval *e, int64_t np) {
   if (np <= e->cap_q) return W2B_OK;
   if (e->Q) (void)hipFree(e->Q);
+  if (e->P) (void)hipFree(e->P);
   if (e->b123) (void)hipFree(e->b123);
   if (e->best) (void)hipFree(e->best);
-  e->Q = nullptr; e->b123 = nullptr; e->best = nullptr; e->cap_q = 0;
-  if (hipMalloc(&e->Q, (size_t)np * e->ld * 4) != hipSuccess || hipMalloc(&e->b123, (size_t)np * 12) != hipSuccess ||
+  e->Q = nullptr; e->P = nullptr; e->b123 = nullptr; e->best = nullptr; e->cap_q = 0;
+  const hipError_t qe = e->bits ? hipMalloc(&e->P, (size_t)np * (size_t)e->wpr * 16) : hipMalloc(&e->Q, (size_t)np * e->ld * 4);
+  if (qe != hipSuccess || hipMalloc(&e->b123, (size_t)np * 12) != hipSuccess ||
       hipMalloc(&e->best, (size_t)np * 8) != hipSuccess)
     return W2B_ENOMEM;
   e->cap_q = np;
+  return W2B_OK;
+}
+
+// ------------------------------------------------------------------------------------ bits mode: the scan
+// The integer scan of include/word2bits_eval.h ("bits mode") for questions whose rows have been checked; k = 0 is the
+// top-1 form (best[nq]), k >= 1 the top-k form (best[nq][k]).  Questions go in chunks; in the top-k form a chunk and
+// its row splits are sized so that the slot scratch (splits x k keys per question) stays within the budget, never below
+// 128 questions or one split.
+static int eval_bits_scan(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t k,
+                          int32_t *best, float *bestd, const char *who) {
+  const int64_t kk = k > 0 ? k : 1;
+  const int nw = (int)(2 * e->wpr);
+  const uint32_t *B32 = (const uint32_t *)e->B;
+  int64_t chunk = kChunkQ;
+  int splits = 1, rpb = 1;
+  if (k > 0) {
+    const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+    chunk = nq < kChunkQ ? (nq + 127) / 128 * 128 : kChunkQ;
+    if (chunk < 128) chunk = 128;
+    for (;;) {
+      w2b_bits_layout(e->words, chunk, 1, 0, &splits, &rpb);
+      if (chunk * 8 * kk * (splits + 1) <= budget || chunk <= 128) break;
+      chunk = chunk / 2 / 128 * 128;
+      if (chunk < 128) chunk = 128;
+    }
+    if (chunk * 8 * kk * (splits + 1) > budget) {
+      const int64_t cap = budget / (chunk * 8 * kk) - 1;
+      w2b_bits_layout(e->words, chunk, 1, cap > 1 ? (int)cap : 1, &splits, &rpb);
+    }
+  }
+  std::vector<unsigned long long> keys;
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int64_t n = (nq - q0 < chunk) ? nq - q0 : chunk;
+    const int64_t np = (n + kTile - 1) / kTile * kTile;
+    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
+    unsigned long long *merged = e->best, *slots = nullptr;
+    if (k > 0) {
+      const size_t need = (size_t)n * 8 * kk * (size_t)(splits + 1);
+      if (need > e->tk_bytes) {
+        if (e->tk_buf) (void)hipFree(e->tk_buf);
+        e->tk_buf = nullptr;
+        e->tk_bytes = 0;
+        if (hipMalloc(&e->tk_buf, need) != hipSuccess) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
+        e->tk_bytes = need;
+      }
+      merged = (unsigned long long *)e->tk_buf;
+      slots = merged + n * kk;
+    }
+    int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
+    EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    if (k == 0) EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
+    hipEvent_t t0, t1;
+    EHIP(hipEventCreate(&t0));
+    EHIP(hipEventCreate(&t1));
+    EHIP(hipEventRecord(t0, e->stream));
+    hipError_t le = w2b_launch_bits_planes(B32, nw, (int)e->size, (int)n, np, d1, d2, d3, e->P, e->stream);
+    if (le == hipSuccess)
+      le = k == 0 ? w2b_launch_bits_top1(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, e->best, e->stream)
+                  : w2b_launch_bits_topk(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, k, splits, rpb, slots,
+                                         merged, e->stream);
+    if (le == hipSuccess) le = hipEventRecord(t1, e->stream);
+    keys.assign((size_t)(n * kk), 0ull);   // (no rows: nothing is launched and every list is empty)
+    if (le == hipSuccess && e->words > 0)
+      le = hipMemcpyAsync(keys.data(), merged, (size_t)(n * kk) * 8, hipMemcpyDeviceToHost, e->stream);
+    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+    float ms = 0;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, t0, t1);
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    if (le != hipSuccess) return efail(W2B_EHIP, std::string(who) + ": " + hipGetErrorString(le));
+    e->kernel_ms += ms;
+    e->launches++;
+    e->macs += (double)n * (double)e->words * (double)e->size;
+    for (int64_t i = 0; i < n * kk; i++) {
+      const unsigned long long key = keys[(size_t)i];
+      best[q0 * kk + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
+      if (bestd) bestd[q0 * kk + i] = (float)(int32_t)(key >> 32) / (float)e->size;   // one correctly rounded division
+    }
+  }
   return W2B_OK;
 }
 
@@ -290,6 +544,7 @@ extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const i
     if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
       return efail(W2B_EINVAL, "w2b_eval_top1: question row out of range");
   EHIP(hipSetDevice(e->device));
+  if (e->bits) return eval_bits_scan(e, nq, b1, b2, b3, 0, best, bestd, "w2b_eval_top1");
   std::vector<unsigned long long> keys;
   for (int64_t q0 = 0; q0 < nq; q0 += kChunkQ) {
     const int64_t n = (nq - q0 < kChunkQ) ? nq - q0 : kChunkQ;
@@ -345,6 +600,7 @@ static int eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *
     if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
       return efail(W2B_EINVAL, std::string(who) + ": question row out of range");
   EHIP(hipSetDevice(e->device));
+  if (e->bits) return eval_bits_scan(e, nq, b1, b2, b3, k, best, bestd, who);
   int nunits = 0, cap = 0;
   w2b_eval_topk_layout(e->words, k, e->fused && e->variant != 0, &nunits, &cap);
   // per question: bound + k buckets + one byte per slot (zeroed together), k merged keys, nunits slots of cap keys
@@ -425,6 +681,7 @@ extern "C" int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes) {
 
 extern "C" int w2b_eval_set_kernel(w2b_eval *e, int32_t variant) {
   if (!e) return efail(W2B_EINVAL, "w2b_eval_set_kernel: null evaluator");
+  if (e->bits) return W2B_OK;                                         // one kernel: nothing to select
   if (variant < 0 || variant > 64) return efail(W2B_EINVAL, "w2b_eval_set_kernel: variant must be 0..64");
   e->variant = variant;
   return W2B_OK;

@@ -144,12 +144,27 @@ hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int word
                                 const int *b1, const int *b2, const int *b3, int k, unsigned long long *bound,
                                 unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
                                 unsigned long long *out, int variant, hipStream_t s);
+// the same scan on bit-packed 1-bit rows (w2b_kernels_evalbits.hip).  B = [words][nw] 32-bit halves of the packed rows
+// (nw = 2 * ceil(dim / 64)), P = the questions' planes [2 * nw][nqp].  Keys are (uint32)I << 32 | ~row, 0 = no row.
+hipError_t w2b_launch_bits_planes(const uint32_t *B, int nw, int dim, int nq, long long nqp, const int *b1, const int *b2,
+                                  const int *b3, uint32_t *P, hipStream_t s);
+void w2b_bits_layout(long long words, long long nq, int topk, int max_splits, int *splits, int *rows_per_split);
+hipError_t w2b_launch_bits_top1(const uint32_t *B, int words, int dim, const uint32_t *P, long long nqp, int nq,
+                                const int *b1, const int *b2, const int *b3, unsigned long long *best /* zeroed */,
+                                hipStream_t s);
+hipError_t w2b_launch_bits_topk(const uint32_t *B, int words, int dim, const uint32_t *P, long long nqp, int nq,
+                                const int *b1, const int *b2, const int *b3, int k, int splits, int rows_per_split,
+                                unsigned long long *slots /* [nq][splits][k] */, unsigned long long *out /* [nq][k] */,
+                                hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>
 bool w2b_internal_is_packed(const unsigned char *d, size_t n);
 int w2b_internal_parse_packed(const unsigned char *d, size_t n, std::vector<std::string> &words, std::vector<float> &values,
                               int64_t *dim_out);
+// header and vocabulary only: the rows stay packed at d + *data_pos (vocab_size x w2b_packed_words_per_row words, unaligned)
+int w2b_internal_parse_packed_head(const unsigned char *d, size_t n, std::vector<std::string> &words, int64_t *dim_out,
+                                   int *bitlevel_out, size_t *data_pos);
 int w2b_internal_fail(int code, const char *msg);   // sets w2b_last_error() (w2b_trainer.cpp)
 struct w2b_trainer;
 // what the evaluator needs from a live trainer (w2b_trainer.cpp): device tables, shape, bitlevel, device, stream

@@ -40,6 +40,7 @@ struct Options {                       // defaults: ref src/word2bits.cpp:48-54,
   int row_groups = -1;                 // -row-groups N: -1 automatic, 0 never, 1 the row-group worker kernel wherever it fits
   int exact = 0;                       // 1: serial dot product in the reference's order (bit parity at -threads 1)
   std::string eval_file;               // -eval FILE: questions to score on the GPU after the final save (-binary 1)
+  int eval_bits = 0;                   // -eval-bits 1: score them on the bit-packed rows (-bitlevel 1; word2bits_eval.h "bits mode")
   int hot_rows = -1;                   // -hot-rows N: leading rows of v (and u) with per-XCD copies; -1 = from the counts
   int hot_rows_u = -1, hot_rows_v = -1; // -hot-rows-u / -hot-rows-v N: the same for one table only
   int hot_cap = -1;                    // -hot-cap N: most rows the automatic choice takes (-1 = default)
@@ -196,6 +197,7 @@ int main(int argc, char **argv) {
   if ((i = arg_pos("-row-groups", argc, argv)) > 0) o.row_groups = atoi(argv[i + 1]);
   if ((i = arg_pos("-exact", argc, argv)) > 0) o.exact = atoi(argv[i + 1]);
   if ((i = arg_pos("-eval", argc, argv)) > 0) o.eval_file = argv[i + 1];
+  if ((i = arg_pos("-eval-bits", argc, argv)) > 0) o.eval_bits = atoi(argv[i + 1]);
   if ((i = arg_pos("-packed", argc, argv)) > 0) o.packed_file = argv[i + 1];
   if ((i = arg_pos("-hot-rows", argc, argv)) > 0) o.hot_rows = atoi(argv[i + 1]);
   if ((i = arg_pos("-hot-rows-u", argc, argv)) > 0) o.hot_rows_u = atoi(argv[i + 1]);
@@ -541,7 +543,9 @@ int main(int argc, char **argv) {
       w2b_eval *ev = nullptr;
       char *txt = nullptr;
       int64_t len = 0;
-      if (w2b_eval_from_trainer(reps[0].t, V, names.data(), 0, 0, 1, &ev) != W2B_OK ||
+      const int rc_ev = o.eval_bits ? w2b_eval_bits_from_trainer(reps[0].t, V, names.data(), 0, &ev)
+                                    : w2b_eval_from_trainer(reps[0].t, V, names.data(), 0, 0, 1, &ev);
+      if (rc_ev != W2B_OK ||
           w2b_eval_transcript(ev, qs.data(), (int64_t)qs.size(), &txt, &len) != W2B_OK) {
         fprintf(stderr, "word2bits: -eval failed: %s\n", w2b_last_error());
         rc_eval = 1;

@@ -3,7 +3,11 @@
     ev = Evaluator("vectors.bin", bitlevel=0, threshold=0)          # ref :77-112
     print(ev.transcript(open("questions-words.txt", "rb").read()).decode())   # ref :113-188, same bytes
 
-The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip); there is no CPU path in this module.
+    ev = Evaluator("vectors.w2bp", bits=True)                        # 1-bit model kept packed: the exact integer scan
+    rows, scores = ev.neighbors([ev.lookup(b"KING")], 10)
+
+The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip); there is no CPU path in this
+module.
 """
 import ctypes as C
 
@@ -14,28 +18,40 @@ from . import _lib
 
 class Evaluator:
     """`fused=True` reproduces the reference built with its own Makefile flags (FMA-contracted dot products),
-    `fused=False` the -ffp-contract=off build; answers are identical to that build's, ties included."""
+    `fused=False` the -ffp-contract=off build; answers are identical to that build's, ties included.
 
-    def __init__(self, path, bitlevel=0, threshold=0, fused=True, device=0, _handle=None):
+    `bits=True` (1-bit models: a bitlevel-1 .w2bp, or a float file reduced to its signs) keeps the rows packed on the
+    device and ranks by the exact integer score I (include/word2bits_eval.h, "bits mode"): rows with I > 0, I descending,
+    equal I by ascending row, score = float32(I) / float32(size).  `bitlevel` and `fused` are ignored."""
+
+    def __init__(self, path, bitlevel=0, threshold=0, fused=True, device=0, _handle=None, bits=False):
         self._h = C.c_void_p()
         self._L = _lib.lib()
         if _handle is not None:
             self._h = _handle
+        elif bits:
+            _lib.check(self._L.w2b_eval_load_bits(str(path).encode(), int(threshold), int(device), C.byref(self._h)))
         else:
             _lib.check(self._L.w2b_eval_load(str(path).encode(), int(bitlevel), int(threshold), int(bool(fused)),
                                              int(device), C.byref(self._h)))
         self.words = int(self._L.w2b_eval_words(self._h))
         self.size = int(self._L.w2b_eval_size(self._h))
+        self.is_bits = bool(self._L.w2b_eval_is_bits(self._h))
 
     @classmethod
-    def from_trainer(cls, trainer, words, bitlevel=0, threshold=0, fused=True):
+    def from_trainer(cls, trainer, words, bitlevel=0, threshold=0, fused=True, bits=False):
         """The evaluator on a live Trainer (no file round trip): what Evaluator(path) would hold after the trainer's
-        vectors had been saved to `path` with binary=1.  `words` = the vocabulary (Corpus.words())."""
+        vectors had been saved to `path` with binary=1.  `words` = the vocabulary (Corpus.words()).  `bits=True` (a
+        bitlevel-1 trainer): what Evaluator(path, bits=True) would hold after the packed save; the rows are packed on
+        the device."""
         L = _lib.lib()
         arr = (C.c_char_p * len(words))(*[w if isinstance(w, bytes) else w.encode("latin1") for w in words])
         h = C.c_void_p()
-        _lib.check(L.w2b_eval_from_trainer(trainer._h, len(words), arr, int(bitlevel), int(threshold), int(bool(fused)),
-                                           C.byref(h)))
+        if bits:
+            _lib.check(L.w2b_eval_bits_from_trainer(trainer._h, len(words), arr, int(threshold), C.byref(h)))
+        else:
+            _lib.check(L.w2b_eval_from_trainer(trainer._h, len(words), arr, int(bitlevel), int(threshold), int(bool(fused)),
+                                               C.byref(h)))
         return cls(None, _handle=h)
 
     def close(self):
@@ -55,6 +71,12 @@ class Evaluator:
     def matrix(self):
         out = np.empty((self.words, self.size), np.float32)
         _lib.check(self._L.w2b_eval_get_matrix(self._h, out.ctypes.data_as(_lib.f32p)))
+        return out
+
+    def bits(self):
+        """The packed rows of a bits handle: uint64 [words, ceil(size / 64)] in the .w2bp layout."""
+        out = np.empty((self.words, (self.size + 63) // 64), np.uint64)
+        _lib.check(self._L.w2b_eval_get_bits(self._h, out.ctypes.data_as(_lib.u64p)))
         return out
 
     def top1(self, b1, b2, b3):
