@@ -1,6 +1,7 @@
 // w2b_eval.cpp -- host side of include/word2bits_eval.h: the vector-file reader, the question-stream state
 // machine and the stdout transcript of the reference evaluator (ref src/compute-accuracy.c:80-188), around the
-// GPU scan in w2b_kernels_eval.hip.  No arithmetic on scores happens here and there is no CPU fallback.
+// GPU scans in w2b_kernels_eval.hip (fp32 rows) and w2b_kernels_evalbits.hip (bit-packed 1-bit rows).  No arithmetic
+// on scores happens here and there is no CPU fallback.
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
@@ -9,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -72,6 +74,18 @@ static void eval_release(w2b_eval *e) {
   delete e;
 }
 
+namespace {
+// a handle under construction: released on every exit that does not hand it to the caller
+struct EvalRelease { void operator()(w2b_eval *e) const { eval_release(e); } };
+using EvalPtr = std::unique_ptr<w2b_eval, EvalRelease>;
+// a device allocation that lives for one constructor call
+struct DeviceTemp {
+  float *p = nullptr;
+  ~DeviceTemp() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+
+// ------------------------------------------------------------------------------------ the file reader
 // fscanf(f, "%lld", &x): skip white space, optional sign, digits
 static bool scan_ll(const std::vector<unsigned char> &d, size_t &pos, long long *out) {
   while (pos < d.size() && is_space(d[pos])) pos++;
@@ -101,288 +115,261 @@ static void read_name(const unsigned char *d, size_t n, size_t &pos, char *row) 
   for (long long i = 0; i < kMaxW; i++) row[i] = c_upper(row[i]);
 }
 
-// common tail of the two constructors: device buffers, quantize(x, bitlevel) + normalisation of the rows (ref :106-110).
-// `host_rows` ([words][size], may be null) or `dev_rows` ([words][size] on the device, may be null) hold the raw values.
-static int eval_finish(w2b_eval *e, int32_t bitlevel, const float *host_rows, const float *dev_rows, w2b_eval **out) {
-  const long long words = e->words, size = e->size;
-  char *vocab = e->vocab.data();
-  for (long long b = 0; b < words; b++) e->first.emplace(std::string(vocab + b * kMaxW), b);   // first wins
-  auto bail = [&](int rc) { eval_release(e); return rc; };
-  if (hipSetDevice(e->device) != hipSuccess) return bail(efail(W2B_EHIP, "hipSetDevice failed"));
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(efail(W2B_EHIP, "hipStreamCreate failed"));
-  const size_t mbytes = (size_t)e->rows_padded * e->ld * 4;
-  float *len = nullptr;
-  if (hipMalloc(&e->M, mbytes) != hipSuccess || hipMalloc(&len, (size_t)(words + 1) * 4) != hipSuccess)
-    return bail(efail(W2B_ENOMEM, "w2b_eval: device allocation failed"));
-  hipError_t he = hipMemsetAsync(e->M, 0, mbytes, e->stream);
-  if (he == hipSuccess && words > 0 && host_rows)
-    he = hipMemcpy2DAsync(e->M, (size_t)e->ld * 4, host_rows, (size_t)size * 4, (size_t)size * 4, (size_t)words,
-                          hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess && words > 0 && dev_rows)
-    he = hipMemcpy2DAsync(e->M, (size_t)e->ld * 4, dev_rows, (size_t)size * 4, (size_t)size * 4, (size_t)words,
-                          hipMemcpyDeviceToDevice, e->stream);
-  if (he == hipSuccess) he = w2b_launch_eval_normalize(e->M, words, size, e->ld, bitlevel, e->fused, len, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  (void)hipFree(len);
-  if (he != hipSuccess) return bail(efail(W2B_EHIP, std::string("w2b_eval: ") + hipGetErrorString(he)));
-  *out = e;
+// One row of a float file (ref :96-105): its name into the vocabulary, then `size` floats.  Returns how many whole
+// floats of them the file still holds, at *values.
+static size_t read_row(const std::vector<unsigned char> &d, size_t &pos, long long size, char *name,
+                       const unsigned char **values) {
+  read_name(d.data(), d.size(), pos, name);
+  const size_t want = (size_t)size * 4, have = d.size() - pos;
+  *values = d.data() + pos;
+  pos = want <= have ? pos + want : d.size();   // a short fread also swallows the 1-3 bytes of a cut float
+  return (want < have ? want : have) / 4;
+}
+
+// The names of rows that come without a file, as the reader would see them in the float file of the same model: each
+// row of a binary file is "word" + ' ' + floats + '\n' (ref src/word2bits.cpp:565-574), so a name starts after the '\n'
+// that the previous row (or the header) left behind.
+template <class Get>
+static void names_from_words(w2b_eval *e, long long count, Get word) {
+  for (long long b = 0; b < count; b++) {
+    const std::string rowbytes = std::string("\n") + word(b) + ' ';
+    size_t pos = 0;
+    read_name((const unsigned char *)rowbytes.data(), rowbytes.size(), pos, e->vocab.data() + b * kMaxW);
+  }
+}
+
+static int read_whole_file(const char *path, const std::string &who, std::vector<unsigned char> &bytes) {
+  FILE *f = fopen(path, "rb");
+  if (!f) return efail(W2B_EIO, "Input file not found");           // ref :81-84
+  fseek(f, 0, SEEK_END);
+  const long long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  bytes.resize(n > 0 ? (size_t)n : 0);
+  const bool ok = n <= 0 || fread(bytes.data(), 1, (size_t)n, f) == (size_t)n;
+  fclose(f);
+  return ok ? W2B_OK : efail(W2B_EIO, who + ": short read");
+}
+
+namespace {
+struct VectorFile {
+  std::vector<unsigned char> d;
+  long long words = 0, size = 0;        // <words> after the threshold (ref :86), <size>
+  size_t pos = 0;                       // the first row
+  bool packed = false;                  // the rows at `pos` are the packed words of a .w2bp, their names are in `names`
+  std::vector<std::string> names;
+};
+}  // namespace
+
+// What both loaders do before they read rows.  A bit-packed model file (include/word2bits_corpus.h) keeps its rows
+// packed when `keep_packed`; otherwise it is rebuilt in memory as the bytes of the reference's binary file (ref
+// src/word2bits.cpp:560-576), which then go through the reader like any other file.  Everything that is wrong with the
+// file is reported before a device is asked for.
+static int open_vector_file(const char *file, bool keep_packed, int64_t threshold, int32_t device, const std::string &who,
+                            VectorFile &f) {
+  if (int rc = read_whole_file(file, who, f.d)) return rc;
+  f.packed = keep_packed && w2b_internal_is_packed(f.d.data(), f.d.size());
+  if (f.packed) {
+    int64_t dim = 0;
+    int bitlevel = 0;
+    if (w2b_internal_parse_packed_head(f.d.data(), f.d.size(), f.names, &dim, &bitlevel, &f.pos) != W2B_OK)
+      return efail(W2B_EIO, who + ": damaged bit-packed file");
+    if (bitlevel != 1)
+      return efail(W2B_EINVAL, who + ": a 2-bit model has no integer ranking (rows differ in length); use w2b_eval_load");
+    f.words = (long long)f.names.size();
+    f.size = dim;
+  } else {
+    if (w2b_internal_is_packed(f.d.data(), f.d.size())) {
+      std::vector<std::string> names;
+      std::vector<float> values;
+      int64_t dim = 0;
+      if (w2b_internal_parse_packed(f.d.data(), f.d.size(), names, values, &dim) != W2B_OK)
+        return efail(W2B_EIO, who + ": damaged bit-packed file");
+      std::vector<unsigned char> b;
+      char head[64];
+      const int hl = snprintf(head, sizeof head, "%lld %lld\n", (long long)names.size(), (long long)dim);
+      b.insert(b.end(), head, head + hl);
+      for (size_t a = 0; a < names.size(); a++) {
+        b.insert(b.end(), names[a].begin(), names[a].end());
+        b.push_back(' ');
+        const unsigned char *row = (const unsigned char *)(values.data() + a * (size_t)dim);
+        b.insert(b.end(), row, row + (size_t)dim * 4);
+        b.push_back('\n');
+      }
+      f.d.swap(b);
+    }
+    if (!scan_ll(f.d, f.pos, &f.words)) return efail(W2B_EIO, who + ": no <words> header");
+    if (!scan_ll(f.d, f.pos, &f.size)) return efail(W2B_EIO, who + ": no <size> header");
+  }
+  if (threshold && f.words > threshold) f.words = threshold;       // ref :86
+  if (f.words < 0 || f.size <= 0 || f.words > 0x7FFFFF00ll || f.size > (1 << 24))
+    return efail(W2B_EINVAL, who + ": unsupported <words> <size>");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return efail(W2B_ENOGPU, who + ": no HIP device visible (the evaluator has no CPU fallback)");
+  if (device < 0 || device >= ndev) return efail(W2B_EINVAL, who + ": bad device index");
   return W2B_OK;
 }
 
-static w2b_eval *eval_new(long long words, long long size, int32_t fused, int32_t device) {
-  w2b_eval *e = new w2b_eval;
+// ------------------------------------------------------------------------------------ the constructors
+static EvalPtr eval_new(long long words, long long size, int32_t fused, int32_t device, bool bits) {
+  EvalPtr e(new w2b_eval);
   e->device = device;
   e->words = words;
   e->size = size;
   e->fused = fused ? 1 : 0;
-  e->ld = (size + 15) / 16 * 16;
+  e->bits = bits ? 1 : 0;
+  e->wpr = bits ? (size + 63) / 64 : 0;
+  e->ld = bits ? 0 : (size + 15) / 16 * 16;
   e->rows_padded = (words + kTile - 1) / kTile * kTile;
   if (e->rows_padded == 0) e->rows_padded = kTile;
   e->vocab.assign((size_t)(words * kMaxW + kMaxW + 2), 0);
   return e;
 }
 
-extern "C" int w2b_eval_load(const char *file, int32_t bitlevel, int64_t threshold, int32_t fused, int32_t device,
-                             w2b_eval **out) {
-  if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load: null argument");
-  *out = nullptr;
-  FILE *f = fopen(file, "rb");
-  if (!f) return efail(W2B_EIO, "Input file not found");           // ref :81-84
-  std::vector<unsigned char> d;
-  {
-    fseek(f, 0, SEEK_END);
-    const long long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    d.resize(n > 0 ? (size_t)n : 0);
-    if (n > 0 && fread(d.data(), 1, (size_t)n, f) != (size_t)n) {
-      fclose(f);
-      return efail(W2B_EIO, "w2b_eval_load: short read");
-    }
-    fclose(f);
-  }
-  if (w2b_internal_is_packed(d.data(), d.size())) {
-    // a bit-packed model file (include/word2bits_corpus.h): rebuilt in memory as the bytes of the reference's binary file
-    // (ref src/word2bits.cpp:560-576), which then go through the reader below like any other file
-    std::vector<std::string> names;
-    std::vector<float> values;
-    int64_t dim = 0;
-    if (w2b_internal_parse_packed(d.data(), d.size(), names, values, &dim) != W2B_OK)
-      return efail(W2B_EIO, "w2b_eval_load: damaged bit-packed file");
-    std::vector<unsigned char> b;
-    char head[64];
-    const int hl = snprintf(head, sizeof head, "%lld %lld\n", (long long)names.size(), (long long)dim);
-    b.insert(b.end(), head, head + hl);
-    for (size_t a = 0; a < names.size(); a++) {
-      b.insert(b.end(), names[a].begin(), names[a].end());
-      b.push_back(' ');
-      const unsigned char *row = (const unsigned char *)(values.data() + a * (size_t)dim);
-      b.insert(b.end(), row, row + (size_t)dim * 4);
-      b.push_back('\n');
-    }
-    d.swap(b);
-  }
-  size_t pos = 0;
-  long long words = 0, size = 0;
-  if (!scan_ll(d, pos, &words)) return efail(W2B_EIO, "w2b_eval_load: no <words> header");
-  if (threshold && words > threshold) words = threshold;            // ref :86
-  if (!scan_ll(d, pos, &size)) return efail(W2B_EIO, "w2b_eval_load: no <size> header");
-  if (words < 0 || size <= 0 || words > 0x7FFFFF00ll || size > (1 << 24))
-    return efail(W2B_EINVAL, "w2b_eval_load: unsupported <words> <size>");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return efail(W2B_ENOGPU, "w2b_eval_load: no HIP device visible (the evaluator has no CPU fallback)");
-  if (device < 0 || device >= ndev) return efail(W2B_EINVAL, "w2b_eval_load: bad device index");
-
-  w2b_eval *e = eval_new(words, size, fused, device);
-  std::vector<float> raw((size_t)(words * size), 0.f);
-  char *vocab = e->vocab.data();
-  for (long long b = 0; b < words; b++) {                           // ref :96-105
-    read_name(d.data(), d.size(), pos, vocab + b * kMaxW);
-    const size_t want = (size_t)size * 4, have = d.size() - pos;
-    const size_t take = (want < have ? want : have) / 4 * 4;
-    memcpy(raw.data() + b * size, d.data() + pos, take);
-    pos = want <= have ? pos + want : d.size();   // a short fread also swallows the 1-3 bytes of a cut float
-  }
-  d.clear();
-  d.shrink_to_fit();
-  return eval_finish(e, bitlevel, raw.data(), nullptr, out);
-}
-
-// The evaluator on a LIVE trainer: what `compute_accuracy <file> <bitlevel> <threshold>` would load after
-// `./word2bits -binary 1` had written <file> from this trainer -- without the file: quantize(u+v) (ref src/word2bits.cpp
-// :568-569) is exported on the device straight into the evaluator's matrix, the names go through the same reader
-// logic as a file's would (each row of a binary file is "word" + ' ' + floats + '\n', ref :565-574).
-extern "C" int w2b_eval_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int32_t bitlevel,
-                                     int64_t threshold, int32_t fused, w2b_eval **out) {
-  if (!t || !out || (n_words > 0 && !words_in)) return efail(W2B_EINVAL, "w2b_eval_from_trainer: null argument");
-  *out = nullptr;
-  float *u = nullptr, *v = nullptr;
-  long long V = 0, D = 0;
-  int tb = 0, dev = 0;
-  hipStream_t ts = nullptr;
-  w2b_internal_trainer_view(t, &u, &v, &V, &D, &tb, &dev, &ts);
-  if (n_words != V) return efail(W2B_EINVAL, "w2b_eval_from_trainer: one word per vocabulary row is needed");
-  long long words = V;
-  if (threshold && words > threshold) words = threshold;            // ref :86
-  w2b_eval *e = eval_new(words, D, fused, dev);
-  char *vocab = e->vocab.data();
-  std::string rowbytes;
-  for (long long b = 0; b < words; b++) {
-    rowbytes.assign("\n");                                          // what the previous row (or the header) left behind
-    rowbytes += words_in[b];
-    rowbytes += ' ';
-    size_t pos = 0;
-    read_name((const unsigned char *)rowbytes.data(), rowbytes.size(), pos, vocab + b * kMaxW);
-  }
-  if (hipSetDevice(dev) != hipSuccess) { eval_release(e); return efail(W2B_EHIP, "hipSetDevice failed"); }
-  float *q = nullptr;
-  if (hipMalloc(&q, sizeof(float) * (size_t)(words > 0 ? words : 1) * D) != hipSuccess) {
-    eval_release(e);
-    return efail(W2B_ENOMEM, "w2b_eval_from_trainer: device allocation failed");
-  }
-  hipError_t he = w2b_launch_export(u, v, q, words * D, tb, ts);     // quantize(u+v) with the TRAINER's bitlevel
-  if (he == hipSuccess) he = hipStreamSynchronize(ts);
-  if (he != hipSuccess) {
-    (void)hipFree(q);
-    eval_release(e);
-    return efail(W2B_EHIP, std::string("w2b_eval_from_trainer: ") + hipGetErrorString(he));
-  }
-  const int rc = eval_finish(e, bitlevel, nullptr, q, out);
-  (void)hipFree(q);
-  return rc;
-}
-
-// ------------------------------------------------------------------------------------ bits mode: the constructors
-// device side of the two bits constructors: `host_bits` ([words][wpr], may be unaligned) is uploaded, or the rows are
-// produced on the device from the trainer's tables (u != null) on its stream
-static int eval_finish_bits(w2b_eval *e, const unsigned char *host_bits, const float *u, const float *v, hipStream_t ts,
-                            w2b_eval **out) {
-  const long long words = e->words;
-  char *vocab = e->vocab.data();
-  for (long long b = 0; b < words; b++) e->first.emplace(std::string(vocab + b * kMaxW), b);   // first wins
-  auto bail = [&](int rc) { eval_release(e); return rc; };
-  if (hipSetDevice(e->device) != hipSuccess) return bail(efail(W2B_EHIP, "hipSetDevice failed"));
+// once the names are in: the lookup table, the device and the handle's stream
+static int eval_open_device(w2b_eval *e) {
+  for (long long b = 0; b < e->words; b++) e->first.emplace(std::string(e->vocab.data() + b * kMaxW), b);   // first wins
+  if (hipSetDevice(e->device) != hipSuccess) return efail(W2B_EHIP, "hipSetDevice failed");
   if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(efail(W2B_EHIP, "hipStreamCreate failed"));
+    return efail(W2B_EHIP, "hipStreamCreate failed");
+  return W2B_OK;
+}
+
+// common tail of the two fp32 constructors: device buffers, quantize(x, bitlevel) + normalisation of the rows (ref
+// :106-110).  `rows` ([words][size], on the host or on the device as `kind` says) holds the raw values.
+static int eval_finish(EvalPtr e, int32_t bitlevel, const float *rows, hipMemcpyKind kind, w2b_eval **out) {
+  if (int rc = eval_open_device(e.get())) return rc;
+  const long long words = e->words, size = e->size;
+  const size_t mbytes = (size_t)e->rows_padded * e->ld * 4;
+  DeviceTemp len;
+  if (hipMalloc(&e->M, mbytes) != hipSuccess || hipMalloc(&len.p, (size_t)(words + 1) * 4) != hipSuccess)
+    return efail(W2B_ENOMEM, "w2b_eval: device allocation failed");
+  hipError_t he = hipMemsetAsync(e->M, 0, mbytes, e->stream);
+  if (he == hipSuccess && words > 0)
+    he = hipMemcpy2DAsync(e->M, (size_t)e->ld * 4, rows, (size_t)size * 4, (size_t)size * 4, (size_t)words, kind, e->stream);
+  if (he == hipSuccess) he = w2b_launch_eval_normalize(e->M, words, size, e->ld, bitlevel, e->fused, len.p, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return efail(W2B_EHIP, std::string("w2b_eval: ") + hipGetErrorString(he));
+  *out = e.release();
+  return W2B_OK;
+}
+
+// common tail of the two bits constructors: `host_bits` ([words][wpr], may be unaligned) is uploaded, or the rows are
+// produced on the device from the trainer's tables (u != null) on its stream
+static int eval_finish_bits(EvalPtr e, const unsigned char *host_bits, const float *u, const float *v, hipStream_t ts,
+                            w2b_eval **out) {
+  if (int rc = eval_open_device(e.get())) return rc;
+  const long long words = e->words;
   const size_t bytes = (size_t)words * (size_t)e->wpr * 8;
-  if (hipMalloc(&e->B, bytes ? bytes : 8) != hipSuccess) return bail(efail(W2B_ENOMEM, "w2b_eval: device allocation failed"));
+  if (hipMalloc(&e->B, bytes ? bytes : 8) != hipSuccess) return efail(W2B_ENOMEM, "w2b_eval: device allocation failed");
   hipError_t he = hipSuccess;
   if (words > 0 && host_bits) he = hipMemcpy(e->B, host_bits, bytes, hipMemcpyHostToDevice);
   if (words > 0 && u) {
     he = w2b_launch_export_packed(u, v, (unsigned long long *)e->B, words, (int)e->size, 1, ts);
     if (he == hipSuccess) he = hipStreamSynchronize(ts);
   }
-  if (he != hipSuccess) return bail(efail(W2B_EHIP, std::string("w2b_eval: ") + hipGetErrorString(he)));
-  *out = e;
+  if (he != hipSuccess) return efail(W2B_EHIP, std::string("w2b_eval: ") + hipGetErrorString(he));
+  *out = e.release();
   return W2B_OK;
 }
 
-static w2b_eval *eval_new_bits(long long words, long long size, int32_t device) {
-  w2b_eval *e = eval_new(words, size, 1, device);
-  e->bits = 1;
-  e->wpr = (size + 63) / 64;
-  e->ld = 0;
-  return e;
+extern "C" int w2b_eval_load(const char *file, int32_t bitlevel, int64_t threshold, int32_t fused, int32_t device,
+                             w2b_eval **out) {
+  if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load: null argument");
+  *out = nullptr;
+  VectorFile f;
+  if (int rc = open_vector_file(file, false, threshold, device, "w2b_eval_load", f)) return rc;
+  EvalPtr e = eval_new(f.words, f.size, fused, device, false);
+  std::vector<float> raw((size_t)(f.words * f.size), 0.f);
+  for (long long b = 0; b < f.words; b++) {
+    const unsigned char *values;
+    const size_t take = read_row(f.d, f.pos, f.size, e->vocab.data() + b * kMaxW, &values);
+    memcpy(raw.data() + b * f.size, values, take * 4);
+  }
+  f.d.clear();
+  f.d.shrink_to_fit();
+  return eval_finish(std::move(e), bitlevel, raw.data(), hipMemcpyHostToDevice, out);
 }
 
 extern "C" int w2b_eval_load_bits(const char *file, int64_t threshold, int32_t device, w2b_eval **out) {
   if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load_bits: null argument");
   *out = nullptr;
-  FILE *f = fopen(file, "rb");
-  if (!f) return efail(W2B_EIO, "Input file not found");           // ref :81-84
-  std::vector<unsigned char> d;
-  {
-    fseek(f, 0, SEEK_END);
-    const long long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    d.resize(n > 0 ? (size_t)n : 0);
-    if (n > 0 && fread(d.data(), 1, (size_t)n, f) != (size_t)n) {
-      fclose(f);
-      return efail(W2B_EIO, "w2b_eval_load_bits: short read");
-    }
-    fclose(f);
-  }
-  const bool packed = w2b_internal_is_packed(d.data(), d.size());
-  std::vector<std::string> names;
-  size_t pos = 0;
-  long long words = 0, size = 0;
-  if (packed) {
-    int64_t dim = 0;
-    int bitlevel = 0;
-    if (w2b_internal_parse_packed_head(d.data(), d.size(), names, &dim, &bitlevel, &pos) != W2B_OK)
-      return efail(W2B_EIO, "w2b_eval_load_bits: damaged bit-packed file");
-    if (bitlevel != 1)
-      return efail(W2B_EINVAL, "w2b_eval_load_bits: a 2-bit model has no integer ranking (rows differ in length); use w2b_eval_load");
-    words = (long long)names.size();
-    size = dim;
-  } else {
-    if (!scan_ll(d, pos, &words)) return efail(W2B_EIO, "w2b_eval_load_bits: no <words> header");
-    if (!scan_ll(d, pos, &size)) return efail(W2B_EIO, "w2b_eval_load_bits: no <size> header");
-  }
-  if (threshold && words > threshold) words = threshold;            // ref :86
-  if (words < 0 || size <= 0 || words > 0x7FFFFF00ll || size > (1 << 24))
-    return efail(W2B_EINVAL, "w2b_eval_load_bits: unsupported <words> <size>");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return efail(W2B_ENOGPU, "w2b_eval_load_bits: no HIP device visible (the evaluator has no CPU fallback)");
-  if (device < 0 || device >= ndev) return efail(W2B_EINVAL, "w2b_eval_load_bits: bad device index");
-
-  w2b_eval *e = eval_new_bits(words, size, device);
-  char *vocab = e->vocab.data();
-  if (packed) {
-    // the names as the reader would see them in the float file of the same model ("word" + ' ' after the '\n' before it)
-    std::string rowbytes;
-    for (long long b = 0; b < words; b++) {
-      rowbytes.assign("\n");
-      rowbytes += names[(size_t)b];
-      rowbytes += ' ';
-      size_t p = 0;
-      read_name((const unsigned char *)rowbytes.data(), rowbytes.size(), p, vocab + b * kMaxW);
-    }
-    return eval_finish_bits(e, d.data() + pos, nullptr, nullptr, nullptr, out);   // the file's words, as they are
+  VectorFile f;
+  if (int rc = open_vector_file(file, true, threshold, device, "w2b_eval_load_bits", f)) return rc;
+  EvalPtr e = eval_new(f.words, f.size, 1, device, true);
+  if (f.packed) {
+    names_from_words(e.get(), f.words, [&](long long b) -> const std::string & { return f.names[(size_t)b]; });
+    // the file's words, as they are
+    return eval_finish_bits(std::move(e), f.d.data() + f.pos, nullptr, nullptr, nullptr, out);
   }
   // a float file: each row reduced to its signs by the bitlevel-1 rule (ref :26-61: negative iff num < 0)
-  std::vector<uint64_t> hb((size_t)(words * e->wpr), 0ull);
-  for (long long b = 0; b < words; b++) {                           // ref :96-105
-    read_name(d.data(), d.size(), pos, vocab + b * kMaxW);
-    const size_t want = (size_t)size * 4, have = d.size() - pos;
-    const size_t take = (want < have ? want : have) / 4;
+  std::vector<uint64_t> hb((size_t)(f.words * e->wpr), 0ull);
+  for (long long b = 0; b < f.words; b++) {
+    const unsigned char *values;
+    const size_t take = read_row(f.d, f.pos, f.size, e->vocab.data() + b * kMaxW, &values);
     uint64_t *row = hb.data() + b * e->wpr;
     for (size_t a = 0; a < take; a++) {
       float x;
-      memcpy(&x, d.data() + pos + a * 4, 4);
+      memcpy(&x, values + a * 4, 4);
       if (x < 0.f) row[a >> 6] |= 1ull << (a & 63);
     }
-    pos = want <= have ? pos + want : d.size();
   }
-  return eval_finish_bits(e, (const unsigned char *)hb.data(), nullptr, nullptr, nullptr, out);
+  return eval_finish_bits(std::move(e), (const unsigned char *)hb.data(), nullptr, nullptr, nullptr, out);
+}
+
+namespace {
+struct TrainerView {
+  float *u = nullptr, *v = nullptr;
+  long long V = 0, D = 0;
+  int bitlevel = 0, device = 0;
+  hipStream_t stream = nullptr;
+};
+}  // namespace
+
+// The evaluator on a LIVE trainer: what `compute_accuracy <file> <bitlevel> <threshold>` would load after `./word2bits
+// -binary 1` (bits: the packed save) had written <file> from this trainer -- without the file.  This is what the two
+// forms share: the checks, the trainer's tables and the handle with its names, which go through the same reader logic
+// as a file's would.
+static int eval_new_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int64_t threshold,
+                                 int32_t fused, bool bits, const std::string &who, TrainerView &tv, EvalPtr &e,
+                                 w2b_eval **out) {
+  if (!t || !out || (n_words > 0 && !words_in)) return efail(W2B_EINVAL, who + ": null argument");
+  *out = nullptr;
+  w2b_internal_trainer_view(t, &tv.u, &tv.v, &tv.V, &tv.D, &tv.bitlevel, &tv.device, &tv.stream);
+  if (bits && tv.bitlevel != 1) return efail(W2B_EINVAL, who + ": the trainer must be at -bitlevel 1");
+  if (n_words != tv.V) return efail(W2B_EINVAL, who + ": one word per vocabulary row is needed");
+  const long long words = threshold && tv.V > threshold ? threshold : tv.V;   // ref :86
+  e = eval_new(words, tv.D, fused, tv.device, bits);
+  names_from_words(e.get(), words, [&](long long b) { return words_in[b]; });
+  return W2B_OK;
+}
+
+// fp32: quantize(u+v) (ref src/word2bits.cpp:568-569) is exported on the device straight into the evaluator's matrix
+extern "C" int w2b_eval_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int32_t bitlevel,
+                                     int64_t threshold, int32_t fused, w2b_eval **out) {
+  TrainerView tv;
+  EvalPtr e;
+  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, fused, false, "w2b_eval_from_trainer", tv, e, out))
+    return rc;
+  const long long words = e->words;
+  if (hipSetDevice(tv.device) != hipSuccess) return efail(W2B_EHIP, "hipSetDevice failed");
+  DeviceTemp q;
+  if (hipMalloc(&q.p, sizeof(float) * (size_t)(words > 0 ? words : 1) * tv.D) != hipSuccess)
+    return efail(W2B_ENOMEM, "w2b_eval_from_trainer: device allocation failed");
+  // quantize(u+v) with the TRAINER's bitlevel
+  hipError_t he = w2b_launch_export(tv.u, tv.v, q.p, words * tv.D, tv.bitlevel, tv.stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(tv.stream);
+  if (he != hipSuccess) return efail(W2B_EHIP, std::string("w2b_eval_from_trainer: ") + hipGetErrorString(he));
+  return eval_finish(std::move(e), bitlevel, q.p, hipMemcpyDeviceToDevice, out);
 }
 
 extern "C" int w2b_eval_bits_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int64_t threshold,
                                           w2b_eval **out) {
-  if (!t || !out || (n_words > 0 && !words_in)) return efail(W2B_EINVAL, "w2b_eval_bits_from_trainer: null argument");
-  *out = nullptr;
-  float *u = nullptr, *v = nullptr;
-  long long V = 0, D = 0;
-  int tb = 0, dev = 0;
-  hipStream_t ts = nullptr;
-  w2b_internal_trainer_view(t, &u, &v, &V, &D, &tb, &dev, &ts);
-  if (tb != 1) return efail(W2B_EINVAL, "w2b_eval_bits_from_trainer: the trainer must be at -bitlevel 1");
-  if (n_words != V) return efail(W2B_EINVAL, "w2b_eval_bits_from_trainer: one word per vocabulary row is needed");
-  long long words = V;
-  if (threshold && words > threshold) words = threshold;            // ref :86
-  w2b_eval *e = eval_new_bits(words, D, dev);
-  char *vocab = e->vocab.data();
-  std::string rowbytes;
-  for (long long b = 0; b < words; b++) {
-    rowbytes.assign("\n");
-    rowbytes += words_in[b];
-    rowbytes += ' ';
-    size_t pos = 0;
-    read_name((const unsigned char *)rowbytes.data(), rowbytes.size(), pos, vocab + b * kMaxW);
-  }
-  return eval_finish_bits(e, nullptr, u, v, ts, out);
+  TrainerView tv;
+  EvalPtr e;
+  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, 1, true, "w2b_eval_bits_from_trainer", tv, e, out))
+    return rc;
+  return eval_finish_bits(std::move(e), nullptr, tv.u, tv.v, tv.stream, out);
 }
 
 extern "C" int32_t w2b_eval_is_bits(const w2b_eval *e) { return e ? e->bits : 0; }
@@ -455,19 +442,104 @@ static int eval_reserve_questions(w2b_eval *e, int64_t np) {
   return W2B_OK;
 }
 
-// ------------------------------------------------------------------------------------ bits mode: the scan
-// The integer scan of include/word2bits_eval.h ("bits mode") for questions whose rows have been checked; k = 0 is the
-// top-1 form (best[nq]), k >= 1 the top-k form (best[nq][k]).  Questions go in chunks; in the top-k form a chunk and
-// its row splits are sized so that the slot scratch (splits x k keys per question) stays within the budget, never below
-// 128 questions or one split.
-static int eval_bits_scan(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t k,
-                          int32_t *best, float *bestd, const char *who) {
-  const int64_t kk = k > 0 ? k : 1;
-  const int nw = (int)(2 * e->wpr);
-  const uint32_t *B32 = (const uint32_t *)e->B;
-  int64_t chunk = kChunkQ;
+// the top-k scratch of one launch
+static int eval_reserve_topk(w2b_eval *e, size_t need) {
+  if (need <= e->tk_bytes) return W2B_OK;
+  if (e->tk_buf) (void)hipFree(e->tk_buf);
+  e->tk_buf = nullptr;
+  e->tk_bytes = 0;
+  if (hipMalloc(&e->tk_buf, need) != hipSuccess) return W2B_ENOMEM;
+  e->tk_bytes = need;
+  return W2B_OK;
+}
+
+// ------------------------------------------------------------------------------------ the scan (ref :155-177)
+// Every query goes through eval_scan_chunks in chunks of questions.  What differs between the forms is a Scan* struct:
+//   chunk, kk     questions per launch and keys per question, sized by the constructor
+//   scratch(n)    bytes of top-k scratch that a chunk of n questions needs
+//   before(...)   what is enqueued ahead of the timed window; leaves `keys` at the chunk's [n][kk] result keys
+//   timed(...)    the launches that the kernel time covers
+//   score(key)    the score in a key's high half
+namespace {
+inline float f32_score(unsigned long long key) {
+  const uint32_t bits = (uint32_t)(key >> 32);
+  float x;
+  memcpy(&x, &bits, 4);
+  return x;
+}
+
+struct ScanTop1 {   // fp32 rows, the best row
+  w2b_eval *e;
+  int64_t chunk = kChunkQ, kk = 1;
+  const unsigned long long *keys = nullptr;
+  size_t scratch(int64_t) const { return 0; }
+  int before(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+    EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
+    EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
+    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
+    keys = e->best;
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+    return w2b_launch_eval_scores(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3, e->best,
+                                  e->variant, e->stream);
+  }
+  float score(unsigned long long key) const { return f32_score(key); }
+};
+
+// fp32 rows, the k best (N = k).  A chunk is sized so that the slot scratch of one launch (w2b_internal.h) stays within
+// the budget; it is never smaller than one 128-question tile.
+struct ScanTopK {
+  w2b_eval *e;
+  int32_t k;
+  int nunits = 0, cap = 0;
+  int64_t zero_q, per_q, chunk, kk;
+  const unsigned long long *keys = nullptr;
+  unsigned long long *bound = nullptr, *bkt = nullptr, *merged = nullptr, *slots = nullptr;
+  unsigned char *cnt = nullptr;
+  ScanTopK(w2b_eval *e_, int32_t k_) : e(e_), k(k_), kk(k_) {
+    w2b_eval_topk_layout(e->words, k, e->fused && e->variant != 0, &nunits, &cap);
+    // per question: bound + k buckets + one byte per slot (zeroed together), k merged keys, nunits slots of cap keys
+    zero_q = 8 + 8 * (int64_t)k + nunits;
+    per_q = zero_q + 8 * (int64_t)k + 8 * (int64_t)nunits * cap;
+    const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+    chunk = budget / per_q / 128 * 128;
+    if (chunk < 128) chunk = 128;
+    if (chunk > kChunkQ) chunk = kChunkQ;
+  }
+  size_t scratch(int64_t n) const { return (size_t)n * per_q + 8; }
+  int before(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+    const size_t zero_bytes = ((size_t)n * zero_q + 7) / 8 * 8;
+    bound = (unsigned long long *)e->tk_buf;
+    bkt = bound + n;
+    cnt = (unsigned char *)(bkt + n * k);
+    merged = (unsigned long long *)((char *)e->tk_buf + zero_bytes);
+    slots = merged + n * k;
+    EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
+    EHIP(hipMemsetAsync(e->tk_buf, 0, zero_bytes, e->stream));
+    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
+    keys = merged;
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+    return w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3, k, bound, bkt,
+                                slots, cnt, merged, e->variant, e->stream);
+  }
+  float score(unsigned long long key) const { return f32_score(key); }
+};
+
+// The integer scan of include/word2bits_eval.h ("bits mode"); k = 0 is the top-1 form (best[nq]), k >= 1 the top-k form
+// (best[nq][k]).  In the top-k form a chunk and its row splits are sized so that the slot scratch (splits x k keys per
+// question) stays within the budget, never below 128 questions or one split.
+struct ScanBits {
+  w2b_eval *e;
+  int32_t k;
+  int64_t chunk = kChunkQ, kk;
   int splits = 1, rpb = 1;
-  if (k > 0) {
+  const unsigned long long *keys = nullptr;
+  unsigned long long *merged = nullptr, *slots = nullptr;
+  ScanBits(w2b_eval *e_, int64_t nq, int32_t k_) : e(e_), k(k_), kk(k_ > 0 ? k_ : 1) {
+    if (k == 0) return;
     const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
     chunk = nq < kChunkQ ? (nq + 127) / 128 * 128 : kChunkQ;
     if (chunk < 128) chunk = 128;
@@ -482,195 +554,105 @@ static int eval_bits_scan(w2b_eval *e, int64_t nq, const int32_t *b1, const int3
       w2b_bits_layout(e->words, chunk, 1, cap > 1 ? (int)cap : 1, &splits, &rpb);
     }
   }
+  size_t scratch(int64_t n) const { return k > 0 ? (size_t)n * 8 * kk * (size_t)(splits + 1) : 0; }
+  int before(int64_t n, int64_t np, const int32_t *, const int32_t *, const int32_t *) {
+    if (k == 0) EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
+    merged = k == 0 ? e->best : (unsigned long long *)e->tk_buf;
+    slots = k == 0 ? nullptr : merged + n * kk;
+    keys = merged;
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+    const uint32_t *B32 = (const uint32_t *)e->B;
+    hipError_t le = w2b_launch_bits_planes(B32, (int)(2 * e->wpr), (int)e->size, (int)n, np, d1, d2, d3, e->P, e->stream);
+    if (le != hipSuccess) return le;
+    return k == 0 ? w2b_launch_bits_top1(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, e->best, e->stream)
+                  : w2b_launch_bits_topk(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, k, splits, rpb, slots,
+                                         merged, e->stream);
+  }
+  float score(unsigned long long key) const { return (float)(int32_t)(key >> 32) / (float)e->size; }   // one correctly rounded division
+};
+
+struct EventPair {   // the two ends of a timed window
+  hipEvent_t t[2] = {nullptr, nullptr};
+  hipError_t create() {
+    hipError_t he = hipSuccess;
+    for (hipEvent_t &x : t)
+      if (he == hipSuccess) he = hipEventCreate(&x);
+    return he;
+  }
+  ~EventPair() {
+    for (hipEvent_t x : t)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+}  // namespace
+
+template <class Scan>
+static int eval_scan_chunks(w2b_eval *e, Scan &&m, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
+                            int32_t *best, float *bestd, const std::string &who) {
   std::vector<unsigned long long> keys;
-  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-    const int64_t n = (nq - q0 < chunk) ? nq - q0 : chunk;
+  for (int64_t q0 = 0; q0 < nq; q0 += m.chunk) {
+    const int64_t n = (nq - q0 < m.chunk) ? nq - q0 : m.chunk;
     const int64_t np = (n + kTile - 1) / kTile * kTile;
-    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
-    unsigned long long *merged = e->best, *slots = nullptr;
-    if (k > 0) {
-      const size_t need = (size_t)n * 8 * kk * (size_t)(splits + 1);
-      if (need > e->tk_bytes) {
-        if (e->tk_buf) (void)hipFree(e->tk_buf);
-        e->tk_buf = nullptr;
-        e->tk_bytes = 0;
-        if (hipMalloc(&e->tk_buf, need) != hipSuccess) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
-        e->tk_bytes = need;
-      }
-      merged = (unsigned long long *)e->tk_buf;
-      slots = merged + n * kk;
-    }
+    if (eval_reserve_questions(e, np) != W2B_OK || eval_reserve_topk(e, m.scratch(n)) != W2B_OK)
+      return efail(W2B_ENOMEM, who + ": device allocation failed");
     int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
     EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    if (k == 0) EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
-    hipEvent_t t0, t1;
-    EHIP(hipEventCreate(&t0));
-    EHIP(hipEventCreate(&t1));
-    EHIP(hipEventRecord(t0, e->stream));
-    hipError_t le = w2b_launch_bits_planes(B32, nw, (int)e->size, (int)n, np, d1, d2, d3, e->P, e->stream);
-    if (le == hipSuccess)
-      le = k == 0 ? w2b_launch_bits_top1(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, e->best, e->stream)
-                  : w2b_launch_bits_topk(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, k, splits, rpb, slots,
-                                         merged, e->stream);
-    if (le == hipSuccess) le = hipEventRecord(t1, e->stream);
-    keys.assign((size_t)(n * kk), 0ull);   // (no rows: nothing is launched and every list is empty)
+    if (int rc = m.before(n, np, d1, d2, d3)) return rc;
+    EventPair ev;
+    EHIP(ev.create());
+    EHIP(hipEventRecord(ev.t[0], e->stream));
+    hipError_t le = m.timed(n, np, d1, d2, d3);
+    if (le == hipSuccess) le = hipEventRecord(ev.t[1], e->stream);
+    keys.assign((size_t)(n * m.kk), 0ull);   // (no rows: nothing is launched and every list is empty)
     if (le == hipSuccess && e->words > 0)
-      le = hipMemcpyAsync(keys.data(), merged, (size_t)(n * kk) * 8, hipMemcpyDeviceToHost, e->stream);
+      le = hipMemcpyAsync(keys.data(), m.keys, (size_t)(n * m.kk) * 8, hipMemcpyDeviceToHost, e->stream);
     if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
     float ms = 0;
-    if (le == hipSuccess) le = hipEventElapsedTime(&ms, t0, t1);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    if (le != hipSuccess) return efail(W2B_EHIP, std::string(who) + ": " + hipGetErrorString(le));
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, ev.t[0], ev.t[1]);
+    if (le != hipSuccess) return efail(W2B_EHIP, who + ": " + hipGetErrorString(le));
     e->kernel_ms += ms;
     e->launches++;
-    e->macs += (double)n * (double)e->words * (double)e->size;
-    for (int64_t i = 0; i < n * kk; i++) {
+    e->macs += (double)n * (double)e->words * (double)e->size;   // algorithmic: padding is not work
+    for (int64_t i = 0; i < n * m.kk; i++) {
       const unsigned long long key = keys[(size_t)i];
-      best[q0 * kk + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
-      if (bestd) bestd[q0 * kk + i] = (float)(int32_t)(key >> 32) / (float)e->size;   // one correctly rounded division
+      best[q0 * m.kk + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
+      if (bestd) bestd[q0 * m.kk + i] = m.score(key);
     }
   }
   return W2B_OK;
+}
+
+// all three public queries: the checks, then the form of the scan.  k = 0 asks for the best row alone.
+static int eval_scan(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, bool topk, int32_t k,
+                     int32_t *best, float *bestd, const std::string &who) {
+  if (!e || nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !best))) return efail(W2B_EINVAL, who + ": bad argument");
+  if (topk && (k < 1 || k > W2B_EVAL_MAX_K)) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  for (int64_t q = 0; q < nq; q++)
+    if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
+      return efail(W2B_EINVAL, who + ": question row out of range");
+  EHIP(hipSetDevice(e->device));
+  if (e->bits) return eval_scan_chunks(e, ScanBits(e, nq, k), nq, b1, b2, b3, best, bestd, who);
+  if (topk) return eval_scan_chunks(e, ScanTopK(e, k), nq, b1, b2, b3, best, bestd, who);
+  return eval_scan_chunks(e, ScanTop1{e}, nq, b1, b2, b3, best, bestd, who);
 }
 
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                              int32_t *best, float *bestd) {
-  if (!e || nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !best)))
-    return efail(W2B_EINVAL, "w2b_eval_top1: bad argument");
-  for (int64_t q = 0; q < nq; q++)
-    if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
-      return efail(W2B_EINVAL, "w2b_eval_top1: question row out of range");
-  EHIP(hipSetDevice(e->device));
-  if (e->bits) return eval_bits_scan(e, nq, b1, b2, b3, 0, best, bestd, "w2b_eval_top1");
-  std::vector<unsigned long long> keys;
-  for (int64_t q0 = 0; q0 < nq; q0 += kChunkQ) {
-    const int64_t n = (nq - q0 < kChunkQ) ? nq - q0 : kChunkQ;
-    const int64_t np = (n + kTile - 1) / kTile * kTile;
-    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, "w2b_eval_top1: device allocation failed");
-    int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
-    EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
-    EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
-    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
-    hipEvent_t t0, t1;
-    EHIP(hipEventCreate(&t0));
-    EHIP(hipEventCreate(&t1));
-    EHIP(hipEventRecord(t0, e->stream));
-    hipError_t le = w2b_launch_eval_scores(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3,
-                                           e->best, e->variant, e->stream);
-    if (le == hipSuccess) le = hipEventRecord(t1, e->stream);
-    keys.resize((size_t)n);
-    if (le == hipSuccess) le = hipMemcpyAsync(keys.data(), e->best, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
-    float ms = 0;
-    if (le == hipSuccess) le = hipEventElapsedTime(&ms, t0, t1);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    if (le != hipSuccess) return efail(W2B_EHIP, std::string("w2b_eval_top1: ") + hipGetErrorString(le));
-    e->kernel_ms += ms;
-    e->launches++;
-    e->macs += (double)n * (double)e->words * (double)e->size;   // algorithmic: padding is not work
-    for (int64_t q = 0; q < n; q++) {
-      const unsigned long long k = keys[(size_t)q];
-      best[q0 + q] = k ? (int32_t)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull)) : -1;
-      if (bestd) {
-        const uint32_t bits = (uint32_t)(k >> 32);
-        memcpy(&bestd[q0 + q], &bits, 4);
-      }
-    }
-  }
-  return W2B_OK;
-}
-
-
-// ------------------------------------------------------------------------------------ top-k
-// ref :155-177 with N = k.  The questions go through the scan in chunks sized so that the slot scratch of one launch
-// (w2b_internal.h) stays within the budget; a chunk is never smaller than one 128-question tile.
-static int eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t k,
-                     int32_t *best, float *bestd, const char *who) {
-  if (!e || nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !best)))
-    return efail(W2B_EINVAL, std::string(who) + ": bad argument");
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, std::string(who) + ": k must be 1..64");
-  for (int64_t q = 0; q < nq; q++)
-    if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
-      return efail(W2B_EINVAL, std::string(who) + ": question row out of range");
-  EHIP(hipSetDevice(e->device));
-  if (e->bits) return eval_bits_scan(e, nq, b1, b2, b3, k, best, bestd, who);
-  int nunits = 0, cap = 0;
-  w2b_eval_topk_layout(e->words, k, e->fused && e->variant != 0, &nunits, &cap);
-  // per question: bound + k buckets + one byte per slot (zeroed together), k merged keys, nunits slots of cap keys
-  const int64_t zero_q = 8 + 8 * (int64_t)k + nunits, per_q = zero_q + 8 * (int64_t)k + 8 * (int64_t)nunits * cap;
-  const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
-  int64_t chunk = budget / per_q / 128 * 128;
-  if (chunk < 128) chunk = 128;
-  if (chunk > kChunkQ) chunk = kChunkQ;
-  std::vector<unsigned long long> keys;
-  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-    const int64_t n = (nq - q0 < chunk) ? nq - q0 : chunk;
-    const int64_t np = (n + kTile - 1) / kTile * kTile;
-    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
-    const size_t zero_bytes = ((size_t)n * zero_q + 7) / 8 * 8, need = (size_t)n * per_q + 8;
-    if (need > e->tk_bytes) {
-      if (e->tk_buf) (void)hipFree(e->tk_buf);
-      e->tk_buf = nullptr;
-      e->tk_bytes = 0;
-      if (hipMalloc(&e->tk_buf, need) != hipSuccess) return efail(W2B_ENOMEM, std::string(who) + ": device allocation failed");
-      e->tk_bytes = need;
-    }
-    unsigned long long *bound = (unsigned long long *)e->tk_buf, *bkt = bound + n;
-    unsigned char *cnt = (unsigned char *)(bkt + n * k);
-    unsigned long long *merged = (unsigned long long *)((char *)e->tk_buf + zero_bytes), *slots = merged + n * k;
-    int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
-    EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
-    EHIP(hipMemsetAsync(e->tk_buf, 0, zero_bytes, e->stream));
-    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
-    hipEvent_t t0, t1;
-    EHIP(hipEventCreate(&t0));
-    EHIP(hipEventCreate(&t1));
-    EHIP(hipEventRecord(t0, e->stream));
-    hipError_t le = w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3,
-                                         k, bound, bkt, slots, cnt, merged, e->variant, e->stream);
-    if (le == hipSuccess) le = hipEventRecord(t1, e->stream);
-    keys.assign((size_t)n * k, 0ull);   // (no rows: nothing is launched and every list is empty)
-    if (le == hipSuccess && e->words > 0)
-      le = hipMemcpyAsync(keys.data(), merged, (size_t)n * k * 8, hipMemcpyDeviceToHost, e->stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
-    float ms = 0;
-    if (le == hipSuccess) le = hipEventElapsedTime(&ms, t0, t1);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    if (le != hipSuccess) return efail(W2B_EHIP, std::string(who) + ": " + hipGetErrorString(le));
-    e->kernel_ms += ms;
-    e->launches++;
-    e->macs += (double)n * (double)e->words * (double)e->size;
-    for (int64_t i = 0; i < n * k; i++) {
-      const unsigned long long key = keys[(size_t)i];
-      best[q0 * k + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
-      if (bestd) {
-        const uint32_t bits = (uint32_t)(key >> 32);
-        memcpy(&bestd[q0 * k + i], &bits, 4);
-      }
-    }
-  }
-  return W2B_OK;
+  return eval_scan(e, nq, b1, b2, b3, false, 0, best, bestd, "w2b_eval_top1");
 }
 
 extern "C" int w2b_eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                              int32_t k, int32_t *best, float *bestd) {
-  return eval_topk(e, nq, b1, b2, b3, k, best, bestd, "w2b_eval_topk");
+  return eval_scan(e, nq, b1, b2, b3, true, k, best, bestd, "w2b_eval_topk");
 }
 
 // vec = (M[r] - M[r]) + M[r]: M[r] up to the sign of a zero, which no chain that starts at +0 can see
 extern "C" int w2b_eval_neighbors(w2b_eval *e, int64_t nq, const int32_t *rows, int32_t k, int32_t *best, float *bestd) {
-  return eval_topk(e, nq, rows, rows, rows, k, best, bestd, "w2b_eval_neighbors");
+  return eval_scan(e, nq, rows, rows, rows, true, k, best, bestd, "w2b_eval_neighbors");
 }
 
 extern "C" int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes) {
@@ -735,6 +717,17 @@ void appendf(std::string &out, const char *fmt, ...) {
   const int n = vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
   out.append(buf, (size_t)(n < (int)sizeof buf ? n : (int)sizeof buf - 1));
+}
+
+// a text result leaves the library as a malloc'ed, 0-terminated copy (w2b_eval_free_text)
+int text_out(const std::string &txt, const char *who, char **out, int64_t *out_len) {
+  char *buf = (char *)malloc(txt.size() + 1);
+  if (!buf) return efail(W2B_ENOMEM, std::string(who) + ": out of memory");
+  memcpy(buf, txt.data(), txt.size());
+  buf[txt.size()] = 0;
+  *out = buf;
+  if (out_len) *out_len = (int64_t)txt.size();
+  return W2B_OK;
 }
 }  // namespace
 
@@ -808,13 +801,7 @@ extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t l
     }
   }
   appendf(txt, "Questions seen / total: %d %d   %.2f %% \n", TQS, TQ, TQS / (float)TQ * 100);
-  char *buf = (char *)malloc(txt.size() + 1);
-  if (!buf) return efail(W2B_ENOMEM, "w2b_eval_transcript: out of memory");
-  memcpy(buf, txt.data(), txt.size());
-  buf[txt.size()] = 0;
-  *out = buf;
-  if (out_len) *out_len = (int64_t)txt.size();
-  return W2B_OK;
+  return text_out(txt, "w2b_eval_transcript", out, out_len);
 }
 
 
@@ -882,13 +869,7 @@ extern "C" int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t l
       appendf(txt, "%d\t%s\t%.6f\n", j + 1, e->vocab.data() + (int64_t)c * kMaxW, (double)bestd[(size_t)(ln.q * k + j)]);
     }
   }
-  char *buf = (char *)malloc(txt.size() + 1);
-  if (!buf) return efail(W2B_ENOMEM, "w2b_eval_nearest_text: out of memory");
-  memcpy(buf, txt.data(), txt.size());
-  buf[txt.size()] = 0;
-  *out = buf;
-  if (out_len) *out_len = (int64_t)txt.size();
-  return W2B_OK;
+  return text_out(txt, "w2b_eval_nearest_text", out, out_len);
 }
 
 extern "C" void w2b_eval_free_text(char *text) { free(text); }

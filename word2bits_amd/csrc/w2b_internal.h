@@ -1,5 +1,5 @@
-// w2b_internal.h -- structures shared by the HIP kernels (w2b_kernels.hip) and the host side of the
-// C ABI (w2b_trainer.cpp, w2b_plan.cpp).  Not part of the public interface (include/word2bits_hip.h).
+// w2b_internal.h -- structures and launchers shared by the HIP kernels (w2b_kernels_*.hip) and the host side of the
+// C ABI (w2b_trainer.cpp, w2b_plan.cpp, w2b_eval.cpp, w2b_corpus.cpp).  Not part of the public interface (include/).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -96,7 +96,7 @@ struct w2b_config;
 struct w2b_tuning;
 void w2b_shape_params(W2bParams &p, const w2b_config &cfg, const w2b_tuning &tune);
 
-// launchers implemented in w2b_kernels.hip --------------------------------------------------------
+// launchers implemented in w2b_kernels_*.hip ------------------------------------------------------
 // block size chosen from dim: one thread per 16-byte (or 4-byte) column of a row
 int w2b_block_threads(int dim, int *vec_out, int *wide_out = nullptr);
 size_t w2b_lds_bytes(int dim, int window, int negative, bool worker_form, bool exact = false);

@@ -79,43 +79,41 @@ class Evaluator:
         _lib.check(self._L.w2b_eval_get_bits(self._h, out.ctypes.data_as(_lib.u64p)))
         return out
 
-    def top1(self, b1, b2, b3):
-        """ref :155-177 for a batch: (best row or -1, its score) per question."""
-        b1, b2, b3 = (np.ascontiguousarray(x, np.int32) for x in (b1, b2, b3))
-        n = len(b1)
-        best, bestd = np.empty(n, np.int32), np.empty(n, np.float32)
+    def _scan(self, fn, rows, *k):
+        """One batched query of the C ABI: int32 row arrays (and k) in, (rows, scores) of shape [nq] or [nq, k] out."""
+        rows = [np.ascontiguousarray(x, np.int32) for x in rows]
+        shape = (len(rows[0]),) + tuple(max(x, 0) for x in k)
+        best, bestd = np.empty(shape, np.int32), np.empty(shape, np.float32)
         p = lambda a: a.ctypes.data_as(_lib.i32p)
-        _lib.check(self._L.w2b_eval_top1(self._h, n, p(b1), p(b2), p(b3), p(best), bestd.ctypes.data_as(_lib.f32p)))
+        _lib.check(fn(self._h, shape[0], *map(p, rows), *k, p(best), bestd.ctypes.data_as(_lib.f32p)))
         return best, bestd
 
-    def topk(self, b1, b2, b3, k):
-        """ref :155-177 with N = k: (rows int32 [nq, k], scores float32 [nq, k]) in the reference's order (score down,
-        equal scores by ascending row); a list of fewer than k rows ends in row -1 / score 0.  1 <= k <= 64."""
-        b1, b2, b3 = (np.ascontiguousarray(x, np.int32) for x in (b1, b2, b3))
-        n, k = len(b1), int(k)
-        best, bestd = np.empty((n, max(k, 0)), np.int32), np.empty((n, max(k, 0)), np.float32)
-        p = lambda a: a.ctypes.data_as(_lib.i32p)
-        _lib.check(self._L.w2b_eval_topk(self._h, n, p(b1), p(b2), p(b3), k, p(best), bestd.ctypes.data_as(_lib.f32p)))
-        return best, bestd
-
-    def neighbors(self, rows, k):
-        """The k nearest rows of each row in `rows` (the row itself excluded): topk(rows, rows, rows, k)."""
-        rows = np.ascontiguousarray(rows, np.int32)
-        n, k = len(rows), int(k)
-        best, bestd = np.empty((n, max(k, 0)), np.int32), np.empty((n, max(k, 0)), np.float32)
-        p = lambda a: a.ctypes.data_as(_lib.i32p)
-        _lib.check(self._L.w2b_eval_neighbors(self._h, n, p(rows), k, p(best), bestd.ctypes.data_as(_lib.f32p)))
-        return best, bestd
-
-    def nearest_text(self, queries, k):
-        """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
-        queries = bytes(queries)
+    def _text(self, fn, text, *k):
+        """One text query of the C ABI: bytes in, the malloc'ed answer copied out and freed."""
+        text = bytes(text)
         out, n = C.c_void_p(), C.c_int64()
-        _lib.check(self._L.w2b_eval_nearest_text(self._h, queries, len(queries), int(k), C.byref(out), C.byref(n)))
+        _lib.check(fn(self._h, text, len(text), *k, C.byref(out), C.byref(n)))
         try:
             return C.string_at(out, n.value)
         finally:
             self._L.w2b_eval_free_text(out)
+
+    def top1(self, b1, b2, b3):
+        """ref :155-177 for a batch: (best row or -1, its score) per question."""
+        return self._scan(self._L.w2b_eval_top1, (b1, b2, b3))
+
+    def topk(self, b1, b2, b3, k):
+        """ref :155-177 with N = k: (rows int32 [nq, k], scores float32 [nq, k]) in the reference's order (score down,
+        equal scores by ascending row); a list of fewer than k rows ends in row -1 / score 0.  1 <= k <= 64."""
+        return self._scan(self._L.w2b_eval_topk, (b1, b2, b3), int(k))
+
+    def neighbors(self, rows, k):
+        """The k nearest rows of each row in `rows` (the row itself excluded): topk(rows, rows, rows, k)."""
+        return self._scan(self._L.w2b_eval_neighbors, (rows,), int(k))
+
+    def nearest_text(self, queries, k):
+        """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
+        return self._text(self._L.w2b_eval_nearest_text, queries, int(k))
 
     def set_topk_scratch(self, nbytes):
         """Upper bound for the device scratch of one top-k launch (0 = default); results never depend on it."""
@@ -123,13 +121,7 @@ class Evaluator:
 
     def transcript(self, questions):
         """stdout of `compute_accuracy FILE bitlevel threshold < questions` as bytes."""
-        questions = bytes(questions)
-        out, n = C.c_void_p(), C.c_int64()
-        _lib.check(self._L.w2b_eval_transcript(self._h, questions, len(questions), C.byref(out), C.byref(n)))
-        try:
-            return C.string_at(out, n.value)
-        finally:
-            self._L.w2b_eval_free_text(out)
+        return self._text(self._L.w2b_eval_transcript, questions)
 
     def set_kernel(self, variant):
         """1 = f32 MFMA kernel (default), 0 = the same fused chain on the vector ALU (cross-check)"""
