@@ -111,9 +111,9 @@ int w2b_eval_timing_read(w2b_eval *e, double *kernel_ms, int64_t *launches, doub
  * On a bits handle w2b_eval_top1 / _topk / _neighbors / _nearest_text / _transcript / _set_topk_scratch /
  * _timing_read (macs = questions x rows x size) work with these semantics, w2b_eval_set_kernel does nothing and
  * w2b_eval_get_matrix is W2B_EINVAL.
- * Two-bit models are out of scope: their rows differ in length, so the ranking needs a per-row float scale. */
+ * Two-bit models have the codes mode below: their rows differ in length, so the ranking needs a per-row float scale. */
 
-/* FILE is a bit-packed .w2bp of bitlevel 1, read without expanding it (bitlevel 2: W2B_EINVAL), or a file of the
+/* FILE is a bit-packed .w2bp of bitlevel 1, read without expanding it (bitlevel 2: W2B_EINVAL, see w2b_eval_load_codes), or a file of the
  * reference's binary format, each value reduced to its sign by the bitlevel-1 rule of ref :26-61 (negative iff
  * num < 0: +0, -0 and NaN are positive).  `threshold` caps the rows as in w2b_eval_load; W2B_EIO "Input file not
  * found" when the file cannot be opened. */
@@ -129,6 +129,48 @@ int w2b_eval_get_bits(w2b_eval *e, uint64_t *out);
  * question (b1, b2, b3) for EVERY row c of packed[words][ceil(dim / 64)], b1, b2, b3 included, into I_out[words]. */
 int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
                          int32_t *I_out);
+
+/* ---- codes mode: the integer scan on bit-packed 2-bit vectors ------------------------------------------------------
+ * A 2-bit value is t/4 with t in {-1, +1, -3, +3}: the SIGN bit set means negative, the MAGNITUDE bit set means 3 (0.75),
+ * clear means 1 (0.25) -- exactly the .w2bp layout of include/word2bits_corpus.h, per 64 columns one sign word then one
+ * magnitude word.  The same opaque w2b_eval in a third mode keeps the rows packed on the device, [words][2 * ceil(size /
+ * 64)] 64-bit words, 1/16 of the float matrix, and scans them on the i8 matrix cores
+ * (word2bits_amd/csrc/w2b_kernels_evalcodes.hip).  For row r:
+ *     n3(r) = the number of magnitude bits set among the `size` columns,   N(r) = size + 8 * n3(r)   ( = 16 |r|^2 ),
+ *     w(r)  = (float)(1.0 / sqrt((double)N(r)))    -- the double square root and the double division each correctly
+ *             rounded, the result rounded to float; w depends on n3 alone: a host-built table of size + 1 floats.
+ * For rows x, c:  J(x, c) = sum_a t_x[a] * t_c[a] over the `size` columns, an exact integer, |J| <= 9 * size.
+ * The score of row c for the question (b1, b2, b3), in float32, every operation rounded to nearest on its own and
+ * nothing contracted into an FMA:
+ *     p1 = (float)J(b1,c) * w(b1);  p2 = (float)J(b2,c) * w(b2);  p3 = (float)J(b3,c) * w(b3);
+ *     score = ((p2 - p1) + p3) * w(c);
+ * (the reference's (M[b2] - M[b1]) + M[b3] order with normalised rows; with b1 = b2 = b3 = r it reduces exactly to
+ * ((float)J(r,c) * w(r)) * w(c), so w2b_eval_neighbors stays equal to w2b_eval_topk(rows, rows, rows)).
+ * The answer list of a question: the rows c other than b1, b2, b3 with score > 0, by score descending, equal float
+ * scores in ascending row order, k of them, a short list ending in row -1 / score 0 -- the key of the fp32 path,
+ * score bits << 32 | ~row.  The fp32 modes agree with this ranking wherever two scores differ by more than the fp32
+ * path's accumulated rounding error.
+ * On a codes handle w2b_eval_top1 / _topk / _neighbors / _nearest_text / _transcript / _set_topk_scratch / _timing_read
+ * (macs = 3 x questions x rows x size) work with these semantics, w2b_eval_set_kernel does nothing, w2b_eval_get_matrix
+ * and w2b_eval_get_bits are W2B_EINVAL, and w2b_eval_is_bits is 0. */
+
+/* FILE is a bit-packed .w2bp of bitlevel 2, read without expanding it (bitlevel 1: W2B_EINVAL, see w2b_eval_load_bits),
+ * or a file of the reference's binary format, each value reduced by the bitlevel-2 rule of ref :26-61 (negative iff
+ * num < 0; magnitude .25 iff |num| <= .5, else .75: NaN becomes +.75, +0 and -0 become +.25).  `threshold` and "Input
+ * file not found" as in w2b_eval_load_bits. */
+int w2b_eval_load_codes(const char *file, int64_t threshold, int32_t device, w2b_eval **out);
+/* The same on a live trainer at -bitlevel 2 (else W2B_EINVAL): the rows are packed on the device from u + v.  What
+ * w2b_eval_load_codes holds after the trainer's vectors have been written with -packed. */
+int w2b_eval_codes_from_trainer(struct w2b_trainer *t, int64_t n_words, const char *const *words, int64_t threshold,
+                                w2b_eval **out);
+int32_t w2b_eval_is_codes(const w2b_eval *e);
+/* the packed rows, [words][2 * ceil(size / 64)] in the file's layout; W2B_EINVAL on any other handle */
+int w2b_eval_get_codes(w2b_eval *e, uint64_t *out);
+/* Host twin of the codes kernels (pure C, no device): for the question (b1, b2, b3) and EVERY row c of
+ * packed[words][2 * ceil(dim / 64)], b1, b2, b3 included, J_out[3][words] = J(b1,c), J(b2,c), J(b3,c) and
+ * score_out[words] = the float score.  Either output may be NULL. */
+int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
+                          int32_t *J_out, float *score_out);
 
 #ifdef __cplusplus
 }

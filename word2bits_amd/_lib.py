@@ -151,6 +151,11 @@ SIGNATURES = {
     "w2b_eval_is_bits": (C.c_int32, [vp]),
     "w2b_eval_get_bits": (C.c_int, [vp, u64p]),
     "w2b_bits_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p]),
+    "w2b_eval_load_codes": (C.c_int, [C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp)]),
+    "w2b_eval_codes_from_trainer": (C.c_int, [vp, C.c_int64, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(vp)]),
+    "w2b_eval_is_codes": (C.c_int32, [vp]),
+    "w2b_eval_get_codes": (C.c_int, [vp, u64p]),
+    "w2b_codes_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p, f32p]),
 }
 
 _lib = None

@@ -1,11 +1,13 @@
 // compute_accuracy_main.cpp -- drop-in for the reference's evaluator program (ref src/compute-accuracy.c:63-189):
-//   ./compute_accuracy <FILE> <bitlevel> <threshold> [fma|nofma|bits] < questions-words.txt
+//   ./compute_accuracy <FILE> <bitlevel> <threshold> [fma|nofma|bits|codes] < questions-words.txt
 // Same positional arguments, same stdout.  The scan runs on the MI355X through include/word2bits_eval.h.
 // The optional 4th argument (or W2B_EVAL_FUSED=0|1) selects which build of the reference the scores are
 // bit-identical to: "fma" (default; the reference's own Makefile flags on an FMA-capable host) or "nofma"
 // (-ffp-contract=off).  The reference ignores a 4th argument, so scripts can pass it to both.
 // "bits" (1-bit models only; <bitlevel> is ignored) keeps the rows bit-packed and answers by the exact integer score
 // with ties to the lowest row (include/word2bits_eval.h, "bits mode"); the transcript keeps the reference's format.
+// "codes" (2-bit models only; <bitlevel> is ignored) does the same for 2-bit rows: exact integer dot products on the packed
+// rows, scaled by the rows' lengths in a fixed float sequence ("codes mode").
 #include "w2b_eval_cli.h"
 
 int main(int argc, char **argv) {
@@ -16,7 +18,8 @@ int main(int argc, char **argv) {
     // (stdout is the reference's, byte for byte; what this program adds goes to stderr)
     fprintf(stderr, "Optional 4th argument: fma (default) | nofma = the build of the reference whose arithmetic is "
                     "reproduced; bits = 1-bit models only: exact integer scores on the bit-packed rows, ties to the lowest "
-                    "row (<bitlevel> is ignored)\n");
+                    "row (<bitlevel> is ignored); codes = 2-bit models only: exact integer dot products on the bit-packed "
+                    "rows, scaled by the rows' lengths (<bitlevel> is ignored)\n");
     return 0;
   }
   const int bitlevel = argc > 2 ? atoi(argv[2]) : 0;          // ref :78

@@ -1,18 +1,20 @@
 // nearest_main.cpp -- what is near a word, and the best few answers to an analogy:
-//   ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits] < queries
+//   ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits|codes] < queries
 // FILE is a vectors file in the reference's binary format or a bit-packed .w2bp file, loaded exactly like
 // ./compute_accuracy loads it (ref src/compute-accuracy.c:80-112).  One query per input line: one word = its k
 // nearest words, three words A B C = the k best answers to "A is to B as C is to ?" (ref :155-177 with N = k).
 // All lines are scored in one batch on the MI355X; the output format is that of w2b_eval_nearest_text.
 // "bits" (1-bit models only; bitlevel is ignored): exact integer scores on the bit-packed rows, ties to the lowest row.
+// "codes" (2-bit models only; bitlevel is ignored): exact integer dot products on the bit-packed rows, scaled by the rows' lengths.
 #include "w2b_eval_cli.h"
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    printf("Usage: ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits] < queries\nwhere FILE contains word "
+    printf("Usage: ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits|codes] < queries\nwhere FILE contains word "
            "projections and every input line is one word (its k nearest words) or three words A B C (the k best "
            "answers to A : B = C : ?); 1 <= k <= %d; bits = 1-bit models only: exact integer scores on the bit-packed "
-           "rows, ties to the lowest row (bitlevel is ignored)\n", W2B_EVAL_MAX_K);
+           "rows, ties to the lowest row (bitlevel is ignored); codes = 2-bit models only: exact integer dot products on "
+           "the bit-packed rows, scaled by the rows' lengths (bitlevel is ignored)\n", W2B_EVAL_MAX_K);
     return 0;
   }
   const int k = argc > 2 ? atoi(argv[2]) : 10;

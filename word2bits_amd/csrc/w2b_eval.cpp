@@ -1,11 +1,13 @@
 // w2b_eval.cpp -- host side of include/word2bits_eval.h: the vector-file reader, the question-stream state
 // machine and the stdout transcript of the reference evaluator (ref src/compute-accuracy.c:80-188), around the
-// GPU scans in w2b_kernels_eval.hip (fp32 rows) and w2b_kernels_evalbits.hip (bit-packed 1-bit rows).  No arithmetic
-// on scores happens here and there is no CPU fallback.
+// GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
+// w2b_kernels_evalcodes.hip (bit-packed 2-bit rows).  No arithmetic on scores happens here and there is no CPU fallback
+// (w2b_codes_scores_host is the tests' twin of the codes kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -44,8 +46,13 @@ struct w2b_eval {
   // bits mode (w2b_eval_load_bits / w2b_eval_bits_from_trainer): the rows stay packed and M does not exist
   int bits = 0;
   int64_t wpr = 0;                                      // 64-bit words per row
-  uint64_t *B = nullptr;                                // [words][wpr], the file's layout
-  uint32_t *P = nullptr;                                // per-call: the questions' planes [2 * 2 * wpr][cap_q]
+  uint64_t *B = nullptr;                                // [words][wpr], the file's layout (both packed modes)
+  uint32_t *P = nullptr;                                // per-call, bits: the questions' planes [2 * 2 * wpr][cap_q];
+                                                        // codes: their int8 operands (w2b_codes_operand_bytes)
+  // codes mode (w2b_eval_load_codes / w2b_eval_codes_from_trainer): 2-bit rows packed in B; Q holds the questions'
+  // weights [3][cap_q]
+  int codes = 0;
+  float *wrow = nullptr;                                // [rows_padded] w(c), 0 past the vocabulary
   // per-call scratch (grown on demand)
   float *Q = nullptr;
   int32_t *b123 = nullptr;
@@ -65,6 +72,7 @@ static void eval_release(w2b_eval *e) {
   (void)hipSetDevice(e->device);
   if (e->M) (void)hipFree(e->M);
   if (e->B) (void)hipFree(e->B);
+  if (e->wrow) (void)hipFree(e->wrow);
   if (e->P) (void)hipFree(e->P);
   if (e->Q) (void)hipFree(e->Q);
   if (e->b123) (void)hipFree(e->b123);
@@ -161,20 +169,22 @@ struct VectorFile {
 }  // namespace
 
 // What both loaders do before they read rows.  A bit-packed model file (include/word2bits_corpus.h) keeps its rows
-// packed when `keep_packed`; otherwise it is rebuilt in memory as the bytes of the reference's binary file (ref
+// packed when `keep_packed` (the bitlevel that the caller scans in packed form: 1 or 2); otherwise it is rebuilt in memory as the bytes of the reference's binary file (ref
 // src/word2bits.cpp:560-576), which then go through the reader like any other file.  Everything that is wrong with the
 // file is reported before a device is asked for.
-static int open_vector_file(const char *file, bool keep_packed, int64_t threshold, int32_t device, const std::string &who,
+static int open_vector_file(const char *file, int keep_packed, int64_t threshold, int32_t device, const std::string &who,
                             VectorFile &f) {
   if (int rc = read_whole_file(file, who, f.d)) return rc;
-  f.packed = keep_packed && w2b_internal_is_packed(f.d.data(), f.d.size());
+  f.packed = keep_packed != 0 && w2b_internal_is_packed(f.d.data(), f.d.size());
   if (f.packed) {
     int64_t dim = 0;
     int bitlevel = 0;
     if (w2b_internal_parse_packed_head(f.d.data(), f.d.size(), f.names, &dim, &bitlevel, &f.pos) != W2B_OK)
       return efail(W2B_EIO, who + ": damaged bit-packed file");
-    if (bitlevel != 1)
+    if (keep_packed == 1 && bitlevel != 1)
       return efail(W2B_EINVAL, who + ": a 2-bit model has no integer ranking (rows differ in length); use w2b_eval_load");
+    if (keep_packed == 2 && bitlevel != 2)
+      return efail(W2B_EINVAL, who + ": a 1-bit model is scanned in bits mode (w2b_eval_load_bits, `bits`)");
     f.words = (long long)f.names.size();
     f.size = dim;
   } else {
@@ -211,15 +221,17 @@ static int open_vector_file(const char *file, bool keep_packed, int64_t threshol
 }
 
 // ------------------------------------------------------------------------------------ the constructors
-static EvalPtr eval_new(long long words, long long size, int32_t fused, int32_t device, bool bits) {
+// `packed`: 0 = fp32 rows, 1 = bits mode, 2 = codes mode
+static EvalPtr eval_new(long long words, long long size, int32_t fused, int32_t device, int packed) {
   EvalPtr e(new w2b_eval);
   e->device = device;
   e->words = words;
   e->size = size;
   e->fused = fused ? 1 : 0;
-  e->bits = bits ? 1 : 0;
-  e->wpr = bits ? (size + 63) / 64 : 0;
-  e->ld = bits ? 0 : (size + 15) / 16 * 16;
+  e->bits = packed == 1;
+  e->codes = packed == 2;
+  e->wpr = (size + 63) / 64 * packed;
+  e->ld = packed ? 0 : (size + 15) / 16 * 16;
   e->rows_padded = (words + kTile - 1) / kTile * kTile;
   if (e->rows_padded == 0) e->rows_padded = kTile;
   e->vocab.assign((size_t)(words * kMaxW + kMaxW + 2), 0);
@@ -254,8 +266,15 @@ static int eval_finish(EvalPtr e, int32_t bitlevel, const float *rows, hipMemcpy
   return W2B_OK;
 }
 
-// common tail of the two bits constructors: `host_bits` ([words][wpr], may be unaligned) is uploaded, or the rows are
-// produced on the device from the trainer's tables (u != null) on its stream
+// w(r) by n3 (include/word2bits_eval.h, "codes mode"): (float)(1.0 / sqrt((double)(dim + 8 n3))), n3 = 0..dim
+static std::vector<float> codes_weights(int64_t dim) {
+  std::vector<float> w((size_t)dim + 1);
+  for (int64_t n3 = 0; n3 <= dim; n3++) w[(size_t)n3] = (float)(1.0 / sqrt((double)(dim + 8 * n3)));
+  return w;
+}
+
+// common tail of the bits and codes constructors: `host_bits` ([words][wpr], may be unaligned) is uploaded, or the rows
+// are produced on the device from the trainer's tables (u != null) on its stream; codes: then w(c) of every row
 static int eval_finish_bits(EvalPtr e, const unsigned char *host_bits, const float *u, const float *v, hipStream_t ts,
                             w2b_eval **out) {
   if (int rc = eval_open_device(e.get())) return rc;
@@ -265,8 +284,18 @@ static int eval_finish_bits(EvalPtr e, const unsigned char *host_bits, const flo
   hipError_t he = hipSuccess;
   if (words > 0 && host_bits) he = hipMemcpy(e->B, host_bits, bytes, hipMemcpyHostToDevice);
   if (words > 0 && u) {
-    he = w2b_launch_export_packed(u, v, (unsigned long long *)e->B, words, (int)e->size, 1, ts);
+    he = w2b_launch_export_packed(u, v, (unsigned long long *)e->B, words, (int)e->size, e->codes ? 2 : 1, ts);
     if (he == hipSuccess) he = hipStreamSynchronize(ts);
+  }
+  DeviceTemp wtab;
+  if (he == hipSuccess && e->codes) {
+    const std::vector<float> w = codes_weights(e->size);
+    if (hipMalloc(&e->wrow, (size_t)e->rows_padded * 4) != hipSuccess || hipMalloc(&wtab.p, w.size() * 4) != hipSuccess)
+      return efail(W2B_ENOMEM, "w2b_eval: device allocation failed");
+    he = hipMemcpy(wtab.p, w.data(), w.size() * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess)
+      he = w2b_launch_codes_roww((const uint32_t *)e->B, (int)e->size, words, e->rows_padded, wtab.p, e->wrow, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
   }
   if (he != hipSuccess) return efail(W2B_EHIP, std::string("w2b_eval: ") + hipGetErrorString(he));
   *out = e.release();
@@ -278,8 +307,8 @@ extern "C" int w2b_eval_load(const char *file, int32_t bitlevel, int64_t thresho
   if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load: null argument");
   *out = nullptr;
   VectorFile f;
-  if (int rc = open_vector_file(file, false, threshold, device, "w2b_eval_load", f)) return rc;
-  EvalPtr e = eval_new(f.words, f.size, fused, device, false);
+  if (int rc = open_vector_file(file, 0, threshold, device, "w2b_eval_load", f)) return rc;
+  EvalPtr e = eval_new(f.words, f.size, fused, device, 0);
   std::vector<float> raw((size_t)(f.words * f.size), 0.f);
   for (long long b = 0; b < f.words; b++) {
     const unsigned char *values;
@@ -295,8 +324,8 @@ extern "C" int w2b_eval_load_bits(const char *file, int64_t threshold, int32_t d
   if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load_bits: null argument");
   *out = nullptr;
   VectorFile f;
-  if (int rc = open_vector_file(file, true, threshold, device, "w2b_eval_load_bits", f)) return rc;
-  EvalPtr e = eval_new(f.words, f.size, 1, device, true);
+  if (int rc = open_vector_file(file, 1, threshold, device, "w2b_eval_load_bits", f)) return rc;
+  EvalPtr e = eval_new(f.words, f.size, 1, device, 1);
   if (f.packed) {
     names_from_words(e.get(), f.words, [&](long long b) -> const std::string & { return f.names[(size_t)b]; });
     // the file's words, as they are
@@ -317,6 +346,33 @@ extern "C" int w2b_eval_load_bits(const char *file, int64_t threshold, int32_t d
   return eval_finish_bits(std::move(e), (const unsigned char *)hb.data(), nullptr, nullptr, nullptr, out);
 }
 
+extern "C" int w2b_eval_load_codes(const char *file, int64_t threshold, int32_t device, w2b_eval **out) {
+  if (!file || !out) return efail(W2B_EINVAL, "w2b_eval_load_codes: null argument");
+  *out = nullptr;
+  VectorFile f;
+  if (int rc = open_vector_file(file, 2, threshold, device, "w2b_eval_load_codes", f)) return rc;
+  EvalPtr e = eval_new(f.words, f.size, 1, device, 2);
+  if (f.packed) {
+    names_from_words(e.get(), f.words, [&](long long b) -> const std::string & { return f.names[(size_t)b]; });
+    return eval_finish_bits(std::move(e), f.d.data() + f.pos, nullptr, nullptr, nullptr, out);
+  }
+  // a float file: each value reduced by the bitlevel-2 rule (ref :26-61: negative iff num < 0, .25 iff |num| <= .5; NaN
+  // fails both comparisons: +.75)
+  std::vector<uint64_t> hb((size_t)(f.words * e->wpr), 0ull);
+  for (long long b = 0; b < f.words; b++) {
+    const unsigned char *values;
+    const size_t take = read_row(f.d, f.pos, f.size, e->vocab.data() + b * kMaxW, &values);
+    uint64_t *row = hb.data() + b * e->wpr;
+    for (size_t a = 0; a < take; a++) {
+      float x;
+      memcpy(&x, values + a * 4, 4);
+      if (x < 0.f) row[2 * (a >> 6)] |= 1ull << (a & 63);
+      if (!(fabsf(x) <= .5f)) row[2 * (a >> 6) + 1] |= 1ull << (a & 63);
+    }
+  }
+  return eval_finish_bits(std::move(e), (const unsigned char *)hb.data(), nullptr, nullptr, nullptr, out);
+}
+
 namespace {
 struct TrainerView {
   float *u = nullptr, *v = nullptr;
@@ -331,15 +387,16 @@ struct TrainerView {
 // forms share: the checks, the trainer's tables and the handle with its names, which go through the same reader logic
 // as a file's would.
 static int eval_new_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int64_t threshold,
-                                 int32_t fused, bool bits, const std::string &who, TrainerView &tv, EvalPtr &e,
+                                 int32_t fused, int packed, const std::string &who, TrainerView &tv, EvalPtr &e,
                                  w2b_eval **out) {
   if (!t || !out || (n_words > 0 && !words_in)) return efail(W2B_EINVAL, who + ": null argument");
   *out = nullptr;
   w2b_internal_trainer_view(t, &tv.u, &tv.v, &tv.V, &tv.D, &tv.bitlevel, &tv.device, &tv.stream);
-  if (bits && tv.bitlevel != 1) return efail(W2B_EINVAL, who + ": the trainer must be at -bitlevel 1");
+  if (packed && tv.bitlevel != packed)
+    return efail(W2B_EINVAL, who + ": the trainer must be at -bitlevel " + std::to_string(packed));
   if (n_words != tv.V) return efail(W2B_EINVAL, who + ": one word per vocabulary row is needed");
   const long long words = threshold && tv.V > threshold ? threshold : tv.V;   // ref :86
-  e = eval_new(words, tv.D, fused, tv.device, bits);
+  e = eval_new(words, tv.D, fused, tv.device, packed);
   names_from_words(e.get(), words, [&](long long b) { return words_in[b]; });
   return W2B_OK;
 }
@@ -349,7 +406,7 @@ extern "C" int w2b_eval_from_trainer(w2b_trainer *t, int64_t n_words, const char
                                      int64_t threshold, int32_t fused, w2b_eval **out) {
   TrainerView tv;
   EvalPtr e;
-  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, fused, false, "w2b_eval_from_trainer", tv, e, out))
+  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, fused, 0, "w2b_eval_from_trainer", tv, e, out))
     return rc;
   const long long words = e->words;
   if (hipSetDevice(tv.device) != hipSuccess) return efail(W2B_EHIP, "hipSetDevice failed");
@@ -367,12 +424,30 @@ extern "C" int w2b_eval_bits_from_trainer(w2b_trainer *t, int64_t n_words, const
                                           w2b_eval **out) {
   TrainerView tv;
   EvalPtr e;
-  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, 1, true, "w2b_eval_bits_from_trainer", tv, e, out))
+  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, 1, 1, "w2b_eval_bits_from_trainer", tv, e, out))
+    return rc;
+  return eval_finish_bits(std::move(e), nullptr, tv.u, tv.v, tv.stream, out);
+}
+
+extern "C" int w2b_eval_codes_from_trainer(w2b_trainer *t, int64_t n_words, const char *const *words_in, int64_t threshold,
+                                           w2b_eval **out) {
+  TrainerView tv;
+  EvalPtr e;
+  if (int rc = eval_new_from_trainer(t, n_words, words_in, threshold, 1, 2, "w2b_eval_codes_from_trainer", tv, e, out))
     return rc;
   return eval_finish_bits(std::move(e), nullptr, tv.u, tv.v, tv.stream, out);
 }
 
 extern "C" int32_t w2b_eval_is_bits(const w2b_eval *e) { return e ? e->bits : 0; }
+extern "C" int32_t w2b_eval_is_codes(const w2b_eval *e) { return e ? e->codes : 0; }
+
+extern "C" int w2b_eval_get_codes(w2b_eval *e, uint64_t *out) {
+  if (!e || !out) return efail(W2B_EINVAL, "w2b_eval_get_codes: null argument");
+  if (!e->codes) return efail(W2B_EINVAL, "w2b_eval_get_codes: not a codes handle");
+  EHIP(hipSetDevice(e->device));
+  if (e->words > 0) EHIP(hipMemcpy(out, e->B, (size_t)e->words * (size_t)e->wpr * 8, hipMemcpyDeviceToHost));
+  return W2B_OK;
+}
 
 extern "C" int w2b_eval_get_bits(w2b_eval *e, uint64_t *out) {
   if (!e || !out) return efail(W2B_EINVAL, "w2b_eval_get_bits: null argument");
@@ -403,6 +478,55 @@ extern "C" int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64
   return W2B_OK;
 }
 
+// Host twin of the codes kernels.  The float sequence of the header, one rounding per operation: this file is built with
+// -ffp-contract=off and the function's body repeats it, so that no build fuses p * w + p.
+extern "C" int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
+                                     int32_t *J_out, float *score_out) {
+#pragma clang fp contract(off)
+  if (!packed || words < 0 || dim < 1 || b1 < 0 || b2 < 0 || b3 < 0 || b1 >= words || b2 >= words || b3 >= words)
+    return efail(W2B_EINVAL, "w2b_codes_scores_host: bad argument");
+  const int64_t nb = (dim + 63) / 64, wpr = 2 * nb;
+  const std::vector<float> wt = codes_weights(dim);
+  auto valid = [&](int64_t b) { return (b + 1) * 64 <= dim ? ~0ull : (1ull << (dim - b * 64)) - 1; };   // padding bits do not count
+  auto weight = [&](const uint64_t *r) {
+    int64_t n3 = 0;
+    for (int64_t b = 0; b < nb; b++) n3 += __builtin_popcountll(r[2 * b + 1] & valid(b));
+    return wt[(size_t)n3];
+  };
+  // sum_a t_x t_c over a block: |t_x t_c| is 1 + 2 m_x + 2 m_c + 4 m_x m_c, its sign that of s_x ^ s_c
+  auto dot = [&](const uint64_t *x, const uint64_t *c) {
+    int64_t j = 0;
+    for (int64_t b = 0; b < nb; b++) {
+      const uint64_t v = valid(b), neg = (x[2 * b] ^ c[2 * b]) & v, pos = ~neg & v;
+      const uint64_t mx = x[2 * b + 1], mc = c[2 * b + 1];
+      auto mag = [&](uint64_t m) {
+        return (int64_t)__builtin_popcountll(m) + 2 * __builtin_popcountll(m & mx) + 2 * __builtin_popcountll(m & mc) +
+               4 * __builtin_popcountll(m & mx & mc);
+      };
+      j += mag(pos) - mag(neg);
+    }
+    return (int32_t)j;
+  };
+  const uint64_t *r1 = packed + b1 * wpr, *r2 = packed + b2 * wpr, *r3 = packed + b3 * wpr;
+  const float w1 = weight(r1), w2 = weight(r2), w3 = weight(r3);
+  for (int64_t c = 0; c < words; c++) {
+    const uint64_t *rc = packed + c * wpr;
+    const int32_t j1 = dot(r1, rc), j2 = dot(r2, rc), j3 = dot(r3, rc);
+    if (J_out) {
+      J_out[c] = j1;
+      J_out[words + c] = j2;
+      J_out[2 * words + c] = j3;
+    }
+    if (score_out) {
+      const float p1 = (float)j1 * w1, p2 = (float)j2 * w2, p3 = (float)j3 * w3;
+      const float d = p2 - p1;
+      const float s = d + p3;
+      score_out[c] = s * weight(rc);
+    }
+  }
+  return W2B_OK;
+}
+
 extern "C" void w2b_eval_free(w2b_eval *e) { eval_release(e); }
 extern "C" int64_t w2b_eval_words(const w2b_eval *e) { return e ? e->words : 0; }
 extern "C" int64_t w2b_eval_size(const w2b_eval *e) { return e ? e->size : 0; }
@@ -419,6 +543,7 @@ extern "C" int64_t w2b_eval_lookup(const w2b_eval *e, const char *upper_word) {
 extern "C" int w2b_eval_get_matrix(w2b_eval *e, float *out) {
   if (!e || !out) return efail(W2B_EINVAL, "w2b_eval_get_matrix: null argument");
   if (e->bits) return efail(W2B_EINVAL, "w2b_eval_get_matrix: a bits handle holds no float matrix (w2b_eval_get_bits)");
+  if (e->codes) return efail(W2B_EINVAL, "w2b_eval_get_matrix: a codes handle holds no float matrix (w2b_eval_get_codes)");
   EHIP(hipSetDevice(e->device));
   if (e->words > 0)
     EHIP(hipMemcpy2D(out, (size_t)e->size * 4, e->M, (size_t)e->ld * 4, (size_t)e->size * 4, (size_t)e->words,
@@ -434,7 +559,10 @@ static int eval_reserve_questions(w2b_eval *e, int64_t np) {
   if (e->b123) (void)hipFree(e->b123);
   if (e->best) (void)hipFree(e->best);
   e->Q = nullptr; e->P = nullptr; e->b123 = nullptr; e->best = nullptr; e->cap_q = 0;
-  const hipError_t qe = e->bits ? hipMalloc(&e->P, (size_t)np * (size_t)e->wpr * 16) : hipMalloc(&e->Q, (size_t)np * e->ld * 4);
+  hipError_t qe = e->bits ? hipMalloc(&e->P, (size_t)np * (size_t)e->wpr * 16)
+                          : e->codes ? hipMalloc(&e->P, w2b_codes_operand_bytes((int)e->size, np))
+                                     : hipMalloc(&e->Q, (size_t)np * e->ld * 4);
+  if (qe == hipSuccess && e->codes) qe = hipMalloc(&e->Q, (size_t)np * 12);
   if (qe != hipSuccess || hipMalloc(&e->b123, (size_t)np * 12) != hipSuccess ||
       hipMalloc(&e->best, (size_t)np * 8) != hipSuccess)
     return W2B_ENOMEM;
@@ -487,43 +615,94 @@ struct ScanTop1 {   // fp32 rows, the best row
   float score(unsigned long long key) const { return f32_score(key); }
 };
 
-// fp32 rows, the k best (N = k).  A chunk is sized so that the slot scratch of one launch (w2b_internal.h) stays within
-// the budget; it is never smaller than one 128-question tile.
+// The selection state of one top-k launch (w2b_internal.h): per question the bound, k buckets and one byte per slot
+// (zeroed together), k merged keys, nunits slots of cap keys.  A chunk of questions is sized so that it stays within the
+// budget, never smaller than one 128-question tile.
+struct TopkScratch {
+  int32_t k = 0;
+  int nunits = 0, cap = 0;
+  int64_t zero_q = 0, per_q = 0;
+  unsigned long long *bound = nullptr, *bkt = nullptr, *merged = nullptr, *slots = nullptr;
+  unsigned char *cnt = nullptr;
+  int64_t chunk(int64_t budget_or_0) {
+    zero_q = 8 + 8 * (int64_t)k + nunits;
+    per_q = zero_q + 8 * (int64_t)k + 8 * (int64_t)nunits * cap;
+    const int64_t budget = budget_or_0 > 0 ? budget_or_0 : kTopkScratch;
+    int64_t c = budget / per_q / 128 * 128;
+    if (c < 128) c = 128;
+    return c > kChunkQ ? kChunkQ : c;
+  }
+  size_t bytes(int64_t n) const { return (size_t)n * per_q + 8; }
+  size_t place(void *buf, int64_t n) {   // returns the bytes to zero
+    const size_t zero_bytes = ((size_t)n * zero_q + 7) / 8 * 8;
+    bound = (unsigned long long *)buf;
+    bkt = bound + n;
+    cnt = (unsigned char *)(bkt + n * k);
+    merged = (unsigned long long *)((char *)buf + zero_bytes);
+    slots = merged + n * k;
+    return zero_bytes;
+  }
+};
+
+// fp32 rows, the k best (N = k)
 struct ScanTopK {
   w2b_eval *e;
   int32_t k;
-  int nunits = 0, cap = 0;
-  int64_t zero_q, per_q, chunk, kk;
+  TopkScratch t;
+  int64_t chunk, kk;
   const unsigned long long *keys = nullptr;
-  unsigned long long *bound = nullptr, *bkt = nullptr, *merged = nullptr, *slots = nullptr;
-  unsigned char *cnt = nullptr;
   ScanTopK(w2b_eval *e_, int32_t k_) : e(e_), k(k_), kk(k_) {
-    w2b_eval_topk_layout(e->words, k, e->fused && e->variant != 0, &nunits, &cap);
-    // per question: bound + k buckets + one byte per slot (zeroed together), k merged keys, nunits slots of cap keys
-    zero_q = 8 + 8 * (int64_t)k + nunits;
-    per_q = zero_q + 8 * (int64_t)k + 8 * (int64_t)nunits * cap;
-    const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
-    chunk = budget / per_q / 128 * 128;
-    if (chunk < 128) chunk = 128;
-    if (chunk > kChunkQ) chunk = kChunkQ;
+    t.k = k;
+    w2b_eval_topk_layout(e->words, k, e->fused && e->variant != 0, &t.nunits, &t.cap);
+    chunk = t.chunk(e->tk_budget);
   }
-  size_t scratch(int64_t n) const { return (size_t)n * per_q + 8; }
+  size_t scratch(int64_t n) const { return t.bytes(n); }
   int before(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
-    const size_t zero_bytes = ((size_t)n * zero_q + 7) / 8 * 8;
-    bound = (unsigned long long *)e->tk_buf;
-    bkt = bound + n;
-    cnt = (unsigned char *)(bkt + n * k);
-    merged = (unsigned long long *)((char *)e->tk_buf + zero_bytes);
-    slots = merged + n * k;
+    const size_t zero_bytes = t.place(e->tk_buf, n);
     EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
     EHIP(hipMemsetAsync(e->tk_buf, 0, zero_bytes, e->stream));
     EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
-    keys = merged;
+    keys = t.merged;
     return W2B_OK;
   }
   hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
-    return w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3, k, bound, bkt,
-                                slots, cnt, merged, e->variant, e->stream);
+    return w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3, k, t.bound, t.bkt,
+                                t.slots, t.cnt, t.merged, e->variant, e->stream);
+  }
+  float score(unsigned long long key) const { return f32_score(key); }
+};
+
+// The scan on 2-bit rows of include/word2bits_eval.h ("codes mode"); k = 0 is the top-1 form.  The keys are the fp32
+// scans' (score bits << 32 | ~row), and the top-k form uses their selection state.
+struct ScanCodes {
+  w2b_eval *e;
+  int32_t k;
+  TopkScratch t;
+  int64_t chunk = kChunkQ, kk;
+  const unsigned long long *keys = nullptr;
+  ScanCodes(w2b_eval *e_, int32_t k_) : e(e_), k(k_), kk(k_ > 0 ? k_ : 1) {
+    if (k == 0) return;
+    t.k = k;
+    w2b_codes_topk_layout(e->words, (int)e->size, k, &t.nunits, &t.cap);
+    chunk = t.chunk(e->tk_budget);
+  }
+  size_t scratch(int64_t n) const { return k > 0 ? t.bytes(n) : 0; }
+  int before(int64_t n, int64_t np, const int32_t *, const int32_t *, const int32_t *) {
+    if (k == 0) {
+      EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
+      keys = e->best;
+    } else {
+      EHIP(hipMemsetAsync(e->tk_buf, 0, t.place(e->tk_buf, n), e->stream));
+      keys = t.merged;
+    }
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+    const uint32_t *B32 = (const uint32_t *)e->B;
+    hipError_t le = w2b_launch_codes_operands(B32, (int)e->size, (int)n, e->wrow, d1, d2, d3, e->P, e->Q, e->stream);
+    if (le != hipSuccess) return le;
+    return w2b_launch_codes_scan(B32, (int)e->words, (int)e->size, e->wrow, e->P, e->Q, (int)n, d1, d2, d3, k,
+                                 k == 0 ? e->best : t.bound, t.bkt, t.slots, t.cnt, t.merged, e->stream);
   }
   float score(unsigned long long key) const { return f32_score(key); }
 };
@@ -616,7 +795,7 @@ static int eval_scan_chunks(w2b_eval *e, Scan &&m, int64_t nq, const int32_t *b1
     if (le != hipSuccess) return efail(W2B_EHIP, who + ": " + hipGetErrorString(le));
     e->kernel_ms += ms;
     e->launches++;
-    e->macs += (double)n * (double)e->words * (double)e->size;   // algorithmic: padding is not work
+    e->macs += (e->codes ? 3.0 : 1.0) * (double)n * (double)e->words * (double)e->size;   // algorithmic: padding is not work
     for (int64_t i = 0; i < n * m.kk; i++) {
       const unsigned long long key = keys[(size_t)i];
       best[q0 * m.kk + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
@@ -636,6 +815,7 @@ static int eval_scan(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *
       return efail(W2B_EINVAL, who + ": question row out of range");
   EHIP(hipSetDevice(e->device));
   if (e->bits) return eval_scan_chunks(e, ScanBits(e, nq, k), nq, b1, b2, b3, best, bestd, who);
+  if (e->codes) return eval_scan_chunks(e, ScanCodes(e, k), nq, b1, b2, b3, best, bestd, who);
   if (topk) return eval_scan_chunks(e, ScanTopK(e, k), nq, b1, b2, b3, best, bestd, who);
   return eval_scan_chunks(e, ScanTop1{e}, nq, b1, b2, b3, best, bestd, who);
 }
@@ -663,7 +843,7 @@ extern "C" int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes) {
 
 extern "C" int w2b_eval_set_kernel(w2b_eval *e, int32_t variant) {
   if (!e) return efail(W2B_EINVAL, "w2b_eval_set_kernel: null evaluator");
-  if (e->bits) return W2B_OK;                                         // one kernel: nothing to select
+  if (e->bits || e->codes) return W2B_OK;                             // one kernel: nothing to select
   if (variant < 0 || variant > 64) return efail(W2B_EINVAL, "w2b_eval_set_kernel: variant must be 0..64");
   e->variant = variant;
   return W2B_OK;

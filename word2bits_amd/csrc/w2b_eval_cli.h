@@ -9,7 +9,7 @@
 #include <cstring>
 #include <string>
 
-// `mode` is the optional fma|nofma|bits argument (null when absent); `text(e, in, len, &txt, &txt_len)` is the query.
+// `mode` is the optional fma|nofma|bits|codes argument (null when absent); `text(e, in, len, &txt, &txt_len)` is the query.
 // What the reference prints goes to stdout, what these programs add goes to stderr under `prog`.
 template <class Text>
 static int w2b_eval_cli(const char *prog, const char *file, int bitlevel, long long threshold, const char *mode, Text text) {
@@ -20,9 +20,10 @@ static int w2b_eval_cli(const char *prog, const char *file, int bitlevel, long l
   if (const char *env = getenv("W2B_DEVICE")) device = atoi(env);
 
   w2b_eval *e = nullptr;
-  const bool bits = mode && !strcmp(mode, "bits");
-  const int rc = bits ? w2b_eval_load_bits(file, threshold, device, &e)
-                      : w2b_eval_load(file, bitlevel, threshold, fused, device, &e);
+  const bool bits = mode && !strcmp(mode, "bits"), codes = mode && !strcmp(mode, "codes");
+  const int rc = bits    ? w2b_eval_load_bits(file, threshold, device, &e)
+                 : codes ? w2b_eval_load_codes(file, threshold, device, &e)
+                         : w2b_eval_load(file, bitlevel, threshold, fused, device, &e);
   if (rc == W2B_EIO && !strcmp(w2b_last_error(), "Input file not found")) {
     printf("Input file not found\n");                          // ref :81-84
     return -1;

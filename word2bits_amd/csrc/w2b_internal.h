@@ -156,6 +156,26 @@ hipError_t w2b_launch_bits_topk(const uint32_t *B, int words, int dim, const uin
                                 const int *b1, const int *b2, const int *b3, int k, int splits, int rows_per_split,
                                 unsigned long long *slots /* [nq][splits][k] */, unsigned long long *out /* [nq][k] */,
                                 hipStream_t s);
+// the merge of the top-k form alone: out[q * k + j] from the slots `keys` / `cnt` that a scan has filled
+hipError_t w2b_launch_eval_topk_merge(unsigned long long *keys, unsigned char *cnt, int nunits, int cap, int k, int nq,
+                                      unsigned long long *out, hipStream_t s);
+// the same scan on bit-packed 2-bit rows (w2b_kernels_evalcodes.hip).  B = [words][nw] 32-bit halves of the packed rows
+// (nw = 4 * ceil(dim / 64)), wrow = w(c) per row ([rows_padded], a multiple of 256 rows, 0 past the vocabulary; wtab =
+// w by n3, dim + 1 floats), T / Wq = the questions' int8 operands (w2b_codes_operand_bytes) and weights [3][32 * ceil(nq / 32)].
+// Keys are score bits << 32 | ~row, 0 = no row.  k = 0: `best` (zeroed) receives the best key of each question; k >= 1:
+// `best` is the bound and bkt / keys / cnt the selection state of w2b_launch_eval_topk (zeroed alike, sized by
+// w2b_codes_topk_layout), out[q * k + j] the j-th best key.
+#define W2B_CODES_KS_MAX 38         // K steps of 32 columns that a wavefront keeps in registers (1216 columns)
+size_t w2b_codes_operand_bytes(int dim, long long nq);
+void w2b_codes_topk_layout(long long words, int dim, int k, int *nunits, int *cap);
+hipError_t w2b_launch_codes_roww(const uint32_t *B, int dim, long long words, long long rows_padded, const float *wtab,
+                                 float *wrow, hipStream_t s);
+hipError_t w2b_launch_codes_operands(const uint32_t *B, int dim, int nq, const float *wrow, const int *b1, const int *b2,
+                                     const int *b3, void *T, float *Wq, hipStream_t s);
+hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const float *wrow, const void *T, const float *Wq,
+                                 int nq, const int *b1, const int *b2, const int *b3, int k, unsigned long long *best,
+                                 unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
+                                 unsigned long long *out, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

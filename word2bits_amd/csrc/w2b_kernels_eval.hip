@@ -26,6 +26,7 @@
 // (39.3 T/s) for the two-instruction unfused form.  XCD-aware launch order: each XCD owns a contiguous stripe
 // of row tiles (see k_eval_scores_mfma for the finer order).
 #include "w2b_device.hpp"
+#include "w2b_eval_select.hpp"
 
 namespace {
 
@@ -95,33 +96,7 @@ __device__ __forceinline__ f32x2 mac2(float a, f32x2 b, f32x2 acc) {
 //     their minimum bounds the k-th best from below (with every row scanned it is about the 3k-th best score).
 // A stale bound is only lower.  A key above the final bound was above every bound its unit saw, so it was dropped
 // only if its unit held k larger ones: k_eval_topk_merge finds the exact top k among the slots.
-struct TopkArgs {
-  unsigned long long *keys;   // [nq][nunits][cap]
-  unsigned char *cnt;         // [nq][nunits]
-  unsigned long long *bkt;    // [nq][k]
-  int k, cap, nunits;
-};
-
-__device__ __forceinline__ unsigned long long ld_key(const unsigned long long *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// `key` is the largest candidate of (q, unit)
-__device__ inline void topk_note_max(unsigned long long *bkt, int k, unsigned long long *bound, int q, int unit,
-                                     unsigned long long key) {
-  unsigned long long *b = bkt + (long long)q * k;
-  const unsigned long long old = atomicMax(&b[unit % k], key);
-  if (old >= key) return;
-  const unsigned long long cur = ld_key(&bound[q]);
-  if (old > cur) return;                 // the bucket was not the smallest one: the minimum stays
-  unsigned long long mn = ~0ull;
-#pragma unroll 8
-  for (int j = 0; j < k; j++) {
-    const unsigned long long v = ld_key(&b[j]);
-    mn = v < mn ? v : mn;
-  }
-  if (mn > cur) atomicMax(&bound[q], mn);
-}
+// (TopkArgs, ld_key and topk_note_max: w2b_eval_select.hpp, shared with the scan on 2-bit rows.)
 
 template <bool FUSED, bool TOPK>
 __device__ __forceinline__ void
@@ -763,6 +738,21 @@ hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int word
   else
     hipLaunchKernelGGL((k_eval_topk<false>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
                        q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
+  hipLaunchKernelGGL(k_eval_topk_merge, dim3((unsigned)nq), dim3(256), 0, s, tk, out);
+  return hipGetLastError();
+}
+
+// the merge alone, for a scan that fills the slots itself (w2b_kernels_evalcodes.hip)
+hipError_t w2b_launch_eval_topk_merge(unsigned long long *keys, unsigned char *cnt, int nunits, int cap, int k, int nq,
+                                      unsigned long long *out, hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  TopkArgs tk;
+  tk.keys = keys;
+  tk.cnt = cnt;
+  tk.bkt = nullptr;
+  tk.k = k;
+  tk.cap = cap;
+  tk.nunits = nunits;
   hipLaunchKernelGGL(k_eval_topk_merge, dim3((unsigned)nq), dim3(256), 0, s, tk, out);
   return hipGetLastError();
 }

@@ -40,7 +40,7 @@ struct Options {                       // defaults: ref src/word2bits.cpp:48-54,
   int row_groups = -1;                 // -row-groups N: -1 automatic, 0 never, 1 the row-group worker kernel wherever it fits
   int exact = 0;                       // 1: serial dot product in the reference's order (bit parity at -threads 1)
   std::string eval_file;               // -eval FILE: questions to score on the GPU after the final save (-binary 1)
-  int eval_bits = 0;                   // -eval-bits 1: score them on the bit-packed rows (-bitlevel 1; word2bits_eval.h "bits mode")
+  int eval_bits = 0;                   // -eval-bits 1: score them on the bit-packed rows (-bitlevel 1: word2bits_eval.h "bits mode"; -bitlevel 2: "codes mode")
   int hot_rows = -1;                   // -hot-rows N: leading rows of v (and u) with per-XCD copies; -1 = from the counts
   int hot_rows_u = -1, hot_rows_v = -1; // -hot-rows-u / -hot-rows-v N: the same for one table only
   int hot_cap = -1;                    // -hot-cap N: most rows the automatic choice takes (-1 = default)
@@ -543,7 +543,8 @@ int main(int argc, char **argv) {
       w2b_eval *ev = nullptr;
       char *txt = nullptr;
       int64_t len = 0;
-      const int rc_ev = o.eval_bits ? w2b_eval_bits_from_trainer(reps[0].t, V, names.data(), 0, &ev)
+      const int rc_ev = o.eval_bits && o.bitlevel == 2 ? w2b_eval_codes_from_trainer(reps[0].t, V, names.data(), 0, &ev)
+                        : o.eval_bits ? w2b_eval_bits_from_trainer(reps[0].t, V, names.data(), 0, &ev)
                                     : w2b_eval_from_trainer(reps[0].t, V, names.data(), 0, 0, 1, &ev);
       if (rc_ev != W2B_OK ||
           w2b_eval_transcript(ev, qs.data(), (int64_t)qs.size(), &txt, &len) != W2B_OK) {

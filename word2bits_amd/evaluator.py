@@ -5,9 +5,10 @@
 
     ev = Evaluator("vectors.w2bp", bits=True)                        # 1-bit model kept packed: the exact integer scan
     rows, scores = ev.neighbors([ev.lookup(b"KING")], 10)
+    ev = Evaluator("vectors2.w2bp", codes=True)                      # 2-bit model kept packed: the i8 matrix-core scan
 
-The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip); there is no CPU path in this
-module.
+The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip);
+there is no CPU path in this module.
 """
 import ctypes as C
 
@@ -22,33 +23,46 @@ class Evaluator:
 
     `bits=True` (1-bit models: a bitlevel-1 .w2bp, or a float file reduced to its signs) keeps the rows packed on the
     device and ranks by the exact integer score I (include/word2bits_eval.h, "bits mode"): rows with I > 0, I descending,
-    equal I by ascending row, score = float32(I) / float32(size).  `bitlevel` and `fused` are ignored."""
+    equal I by ascending row, score = float32(I) / float32(size).  `bitlevel` and `fused` are ignored.
 
-    def __init__(self, path, bitlevel=0, threshold=0, fused=True, device=0, _handle=None, bits=False):
+    `codes=True` (2-bit models: a bitlevel-2 .w2bp, or a float file reduced by the bitlevel-2 rule) keeps the rows packed
+    and scores by exact integer dot products scaled by the rows' lengths in a fixed float32 sequence
+    (include/word2bits_eval.h, "codes mode").  `bitlevel` and `fused` are ignored."""
+
+    def __init__(self, path, bitlevel=0, threshold=0, fused=True, device=0, _handle=None, bits=False, codes=False):
         self._h = C.c_void_p()
+        if bits and codes:
+            raise ValueError("bits and codes are two modes: give one of them")
         self._L = _lib.lib()
         if _handle is not None:
             self._h = _handle
         elif bits:
             _lib.check(self._L.w2b_eval_load_bits(str(path).encode(), int(threshold), int(device), C.byref(self._h)))
+        elif codes:
+            _lib.check(self._L.w2b_eval_load_codes(str(path).encode(), int(threshold), int(device), C.byref(self._h)))
         else:
             _lib.check(self._L.w2b_eval_load(str(path).encode(), int(bitlevel), int(threshold), int(bool(fused)),
                                              int(device), C.byref(self._h)))
         self.words = int(self._L.w2b_eval_words(self._h))
         self.size = int(self._L.w2b_eval_size(self._h))
         self.is_bits = bool(self._L.w2b_eval_is_bits(self._h))
+        self.is_codes = bool(self._L.w2b_eval_is_codes(self._h))
 
     @classmethod
-    def from_trainer(cls, trainer, words, bitlevel=0, threshold=0, fused=True, bits=False):
+    def from_trainer(cls, trainer, words, bitlevel=0, threshold=0, fused=True, bits=False, codes=False):
         """The evaluator on a live Trainer (no file round trip): what Evaluator(path) would hold after the trainer's
         vectors had been saved to `path` with binary=1.  `words` = the vocabulary (Corpus.words()).  `bits=True` (a
         bitlevel-1 trainer): what Evaluator(path, bits=True) would hold after the packed save; the rows are packed on
-        the device."""
+        the device.  `codes=True` (a bitlevel-2 trainer): the same for Evaluator(path, codes=True)."""
+        if bits and codes:
+            raise ValueError("bits and codes are two modes: give one of them")
         L = _lib.lib()
         arr = (C.c_char_p * len(words))(*[w if isinstance(w, bytes) else w.encode("latin1") for w in words])
         h = C.c_void_p()
         if bits:
             _lib.check(L.w2b_eval_bits_from_trainer(trainer._h, len(words), arr, int(threshold), C.byref(h)))
+        elif codes:
+            _lib.check(L.w2b_eval_codes_from_trainer(trainer._h, len(words), arr, int(threshold), C.byref(h)))
         else:
             _lib.check(L.w2b_eval_from_trainer(trainer._h, len(words), arr, int(bitlevel), int(threshold), int(bool(fused)),
                                                C.byref(h)))
@@ -77,6 +91,12 @@ class Evaluator:
         """The packed rows of a bits handle: uint64 [words, ceil(size / 64)] in the .w2bp layout."""
         out = np.empty((self.words, (self.size + 63) // 64), np.uint64)
         _lib.check(self._L.w2b_eval_get_bits(self._h, out.ctypes.data_as(_lib.u64p)))
+        return out
+
+    def codes(self):
+        """The packed rows of a codes handle: uint64 [words, 2 * ceil(size / 64)] in the .w2bp layout."""
+        out = np.empty((self.words, 2 * ((self.size + 63) // 64)), np.uint64)
+        _lib.check(self._L.w2b_eval_get_codes(self._h, out.ctypes.data_as(_lib.u64p)))
         return out
 
     def _scan(self, fn, rows, *k):
