@@ -50,8 +50,8 @@ tokens, counts = corpus.tokens(), corpus.counts()
 V, D, R = corpus.vocab_size, a.size, a.replicas
 print("RR corpus: %d words, vocabulary %d  [%.1f s]" % (corpus.train_words, V, time.time() - t0), flush=True)
 N_MODEL = 2 * V * D
-XCHUNK = ((N_MODEL + 3) & ~3) if N_MODEL < (64 << 20) else (64 << 20)      # w2b_trainer.cpp xchg_setup
-# expected updates of every row of [u || v] per centre word (w2b_plan.cpp w2b_plan_set_counts / w2b_trainer.cpp xchg_saturated_prefix)
+XCHUNK = ((N_MODEL + 3) & ~3) if N_MODEL < (64 << 20) else (64 << 20)      # w2b_exchange.cpp xchg_alloc
+# expected updates of every row of [u || v] per centre word (w2b_plan.cpp w2b_plan_set_counts / w2b_exchange.cpp xchg_saturated_prefix)
 c64 = counts.astype(np.float64)
 rate = np.concatenate([(a.window + 1) * c64 / c64.sum(), a.negative * c64 ** 0.75 / (c64 ** 0.75).sum() + c64 / c64.sum()])
 rate_dev = torch.tensor(rate, dtype=torch.float32, device=dev)

@@ -19,6 +19,7 @@ import pytest
 
 import word2bits_amd as w2b
 from word2bits_amd import replicas
+from word2bits_amd._lib import W2B_EINVAL
 from w2b_testlib import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -47,7 +48,7 @@ def flat(t):
 
 
 def saturated_rows(counts, words, window, negative):
-    """the library's rule for mode 2 restated (w2b_trainer.cpp xchg_saturated_prefix): per table, rows 1..n with n the result of
+    """the library's rule for mode 2 restated (w2b_exchange.cpp xchg_saturated_prefix): per table, rows 1..n with n the result of
     the same binary search over `rate x words >= 32` (the vocabulary is meant to be sorted by count)"""
     c = counts.astype(np.float64)
     pw, tot = (c ** 0.75).sum(), c.sum()
@@ -96,9 +97,10 @@ def test_size_one_communicator_runs_the_whole_exchange_and_changes_nothing(gpu):
     assert res[0][1:] == res[1][1:]
 
 
-def local_exchange(ts, mode=0, counts_out=None):
+def local_exchange(ts, mode=0, counts_out=None, chunks_out=None):
     """the host-supplied collective of the phase API for replicas that live in this process: sum of the delta buffers
-    (counts_out: a list that receives the summed per-row contributor counts of mode 2 as a numpy array)"""
+    (counts_out: a list that receives the summed per-row contributor counts of mode 2 as a numpy array; chunks_out: a list
+    that receives the length of every chunk in floats)"""
     import torch
     begun = [t.exchange_begin() for t in ts]
     n_chunks = begun[0][0]
@@ -113,6 +115,8 @@ def local_exchange(ts, mode=0, counts_out=None):
         torch.cuda.synchronize()
     for c in range(n_chunks):
         bufs = [t.device_tensor(*t.exchange_delta(c)) for t in ts]
+        if chunks_out is not None:
+            chunks_out.append(bufs[0].numel())
         total = torch.stack(bufs).sum(0)
         for b in bufs:
             b.copy_(total)
@@ -126,8 +130,8 @@ def local_exchange(ts, mode=0, counts_out=None):
 
 
 def smooth_factors(counts, words, window, negative, c, tau_u=64.0, tau_v=64.0):
-    """the library's default combination rule of mode 2 restated (w2b_kernels_misc.hip k_xchg_factor, w2b_trainer.cpp
-    xchg_upload_rates; -sample 0): per row of [u || v], with n = expected updates per replica since the last exchange and c =
+    """the library's default combination rule of mode 2 restated (w2b_kernels_misc.hip k_xchg_factor, w2b_exchange.cpp
+    w2b_xchg_upload_rates; -sample 0): per row of [u || v], with n = expected updates per replica since the last exchange and c =
     replicas that changed the row,  k = (1 - exp(-c n / tau)) / (c (1 - exp(-n / tau)))  for c > 1, else 1"""
     cn = counts.astype(np.float64)
     V = len(cn)
@@ -230,6 +234,122 @@ def test_exchange_needs_init(gpu):
     with pytest.raises(w2b.W2bError) as e:
         t.exchange_begin()
     assert "exchange_init" in str(e.value)
+    t.close()
+
+
+# ---------------------------------------------------------------------------------------------- more than one chunk
+# The smallest model with three chunks: 2 V D = 168 M floats = 2.503 chunks of 64 Mi floats, so slot 0 of the two staging
+# buffers is used twice and the last chunk is partial.  No corpus, no training: the "training" is a perturbation written
+# through model_tensor().  About 2.4 GB of device memory per trainer; all arithmetic stays on the device.
+BIG_V, BIG_D, CHUNK = 210_000, 400, 64 << 20
+
+
+def big_trainer():
+    t = w2b.Trainer(BIG_V, BIG_D, 5, 5, 1, num_threads=1, iter=1, sample=0.0, compute_loss=False)
+    t.init_net()
+    return t
+
+
+def perturb(t, seed):
+    """uniform +-0.25 on a seeded subset of [u || v] that contains both sides of every chunk boundary and the last float"""
+    import torch
+    m = t.model_tensor()
+    n = m.numel()
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.cat([torch.randint(0, n, (200_000,), generator=g),
+                     torch.tensor([CHUNK - 1, CHUNK, 2 * CHUNK - 1, 2 * CHUNK, n - 1])]).unique()
+    val = torch.rand(idx.numel(), generator=g) * 0.5 - 0.25
+    m[idx.to(m.device)] += val.to(m.device)
+    torch.cuda.synchronize()                          # (the library's streams do not wait for torch's)
+
+
+def test_three_chunks_with_a_ragged_tail_phase_api(gpu):
+    """Two replicas, three chunks, modes 0 and 1 one after the other: every replica ends at mine + (a S - d), computed in float32 on
+    the device from a tracked copy of base (tolerances of test_phase_api_arithmetic_two_replicas); the second round is what checks
+    base += comb over all three chunks."""
+    import torch
+    n = 2 * BIG_V * BIG_D
+    ts = [big_trainer() for _ in range(2)]
+    for t in ts:
+        t.exchange_init()
+    base = ts[0].model_tensor().clone()
+    assert torch.equal(base, ts[1].model_tensor())
+    for rnd, mode in enumerate((0, 1)):
+        for r, t in enumerate(ts):
+            perturb(t, 10 * rnd + r + 1)
+        mine = [t.model_tensor().clone() for t in ts]
+        d = [m - base for m in mine]
+        S = d[0] + d[1]
+        total = S * (1.0 if mode == 0 else 0.5)
+        chunks = []
+        local_exchange(ts, mode, chunks_out=chunks)
+        assert len(chunks) == 3 and chunks == [CHUNK, CHUNK, n - 2 * CHUNK]
+        got = [t.model_tensor() for t in ts]
+        for r in range(2):
+            err = (got[r] - (mine[r] + (total - d[r]))).abs().max().item()
+            print("EXCHANGE three chunks: round %d mode %d replica %d max error %.3g" % (rnd, mode, r, err))
+            assert err <= 2e-6, (rnd, r, err)
+            assert (got[r] - mine[r]).abs().max().item() > 0         # the other replica's work arrived
+        agree = (got[0] - got[1]).abs().max().item()
+        print("EXCHANGE three chunks: round %d replicas differ by %.3g" % (rnd, agree))
+        assert agree <= 4e-6
+        base = base + total
+        del got
+    for t in ts:
+        t.close()
+    del base, mine, d, S, total
+    torch.cuda.empty_cache()
+
+
+def test_three_chunks_through_the_library_pipeline(gpu):
+    """One rank, a real communicator, three chunks: the software pipeline of w2b_sync_replicas reuses slot 0 and ends on a partial
+    chunk, and must leave the model bit-identical in every mode."""
+    import torch
+    t = big_trainer()
+    rng = np.random.default_rng(5)
+    ids = rng.zipf(1.3, 2_000_000) % (BIG_V - 1) + 1
+    t.set_vocab_counts(np.maximum(np.bincount(ids, minlength=BIG_V), 1).astype(np.int64), 100000)
+    t.comm_init(1, 0, w2b.comm_unique_id())
+    for mode in (0, 1, 2):
+        perturb(t, 20 + mode)
+        before = t.model_tensor().clone()
+        t.sync_replicas(mode)
+        assert torch.equal(before.view(torch.int32), t.model_tensor().view(torch.int32)), mode
+    n, ms = t.sync_stats()
+    assert n == 3 and ms > 0
+    t.close()
+    del before
+    torch.cuda.empty_cache()
+
+
+def test_phase_api_state_and_argument_errors(gpu):
+    t = small_setup(2, 2, 0)
+    t.exchange_init()
+    for call in (t.exchange_counts, lambda: t.exchange_delta(0), lambda: t.exchange_apply(0), t.exchange_end):
+        with pytest.raises(w2b.W2bError, match="w2b_exchange_begin first"):
+            call()
+    n_chunks, _ = t.exchange_begin()
+    with pytest.raises(w2b.W2bError, match="not ended"):
+        t.exchange_begin()
+    for call in (t.exchange_delta, t.exchange_apply):
+        for chunk in (-1, n_chunks):
+            with pytest.raises(w2b.W2bError) as e:
+                call(chunk)
+            assert e.value.code == W2B_EINVAL
+    with pytest.raises(w2b.W2bError):
+        t.sync_stats()
+    for c in range(n_chunks):
+        t.exchange_delta(c)
+        t.exchange_apply(c)
+    t.exchange_end()
+    local_exchange([t])                               # after the end a full further exchange succeeds
+    assert t.sync_stats()[0] == 2
+    t.exchange_begin()
+    t.close()                                         # between begin and end
+    t = small_setup(2, 2, 0)
+    t.exchange_init()
+    local_exchange([t])
+    assert t.sync_stats()[0] == 1
     t.close()
 
 

@@ -1,5 +1,5 @@
 // w2b_internal.h -- structures and launchers shared by the HIP kernels (w2b_kernels_*.hip) and the host side of the
-// C ABI (w2b_trainer.cpp, w2b_plan.cpp, w2b_eval.cpp, w2b_corpus.cpp).  Not part of the public interface (include/).
+// C ABI (w2b_trainer.cpp, w2b_exchange.cpp, w2b_plan.cpp, w2b_eval.cpp, w2b_corpus.cpp).  Not part of the public interface (include/).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

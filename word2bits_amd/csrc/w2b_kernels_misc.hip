@@ -58,7 +58,7 @@ __global__ void k_export_packed(const float *__restrict__ u, const float *__rest
   }
 }
 
-// ---- replica exchange (w2b_trainer.cpp, "multi-GPU"): one CHUNK of [u || v] at a time, 16 bytes per lane, on the
+// ---- replica exchange (w2b_exchange.cpp): one CHUNK of [u || v] at a time, 16 bytes per lane, on the
 // exchange streams WHILE the training kernels keep updating the same rows.  The model is therefore read and written at
 // agent scope (sc1 buffer accesses, like the training kernels' own row accesses); base / d / s belong to the exchange.
 typedef float w2b_f4 __attribute__((ext_vector_type(4)));
@@ -137,7 +137,7 @@ __global__ void k_xchg_apply(float *w, float *__restrict__ base, const float *__
   }
 }
 // The combination rule of mode 2, per ROW of [u || v]: cnt[g] (in) = number of replicas that changed row g since the last
-// exchange, (out) = the factor k on the SUM of their deltas (w2b_trainer.cpp "the combination rule of mode 2" has what was measured).
+// exchange, (out) = the factor k on the SUM of their deltas (DESIGN.md section 3.5 has what was measured).
 //   rules 0 and 2 (round 6; 0 = the default, with the per-element cells of k_xchg_apply on top; 2 = without) -- exponential
 //     saturation.  A row that has received n updates in a replica since the last exchange
 //     has contracted towards where those updates pull it by rho = 1 - exp(-n / tau); c replicas' updates applied one after the

@@ -1,117 +1,18 @@
-// w2b_trainer.cpp -- host side of the C ABI declared in include/word2bits_hip.h.
-// Owns device memory, streams, events and the RCCL communicator; all arithmetic of the hot
-// path lives in w2b_kernels.hip.  There is deliberately no CPU fallback in this file.
-#include "../../include/word2bits_hip.h"
+// w2b_trainer.cpp -- host side of the C ABI declared in include/word2bits_hip.h: lifetime, model, sampler state, launches,
+// tuples.  Owns the trainer's device memory, streams and events; all arithmetic of the hot path lives in w2b_kernels_*.hip, the
+// launch policy in w2b_plan.cpp, the replica exchange in w2b_exchange.cpp.  There is deliberately no CPU fallback in this file.
 #include "../../include/word2bits_corpus.h"
-#include "w2b_internal.h"
-#include "w2b_plan.h"
-
-#include <rccl/rccl.h>
+#include "w2b_exchange.h"
+#include "w2b_host.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
-// shared with the other host translation units of the library (w2b_eval.cpp)
-int w2b_internal_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(W2B_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-#define NCCLCHK(x)                                                                        \
-  do {                                                                                    \
-    ncclResult_t r_ = (x);                                                                \
-    if (r_ != ncclSuccess)                                                                \
-      return fail(W2B_ERCCL, std::string(#x) + ": " + ncclGetErrorString(r_));            \
-  } while (0)
-
-struct w2b_trainer {
-  W2bPlanInputs in;             // configuration, tuning knobs, compute units, word-count statistics: what the launch policy reads (w2b_plan.h)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  float *uv = nullptr;          // u followed by v (one allocation: one all-reduce)
-  float *base = nullptr;        // snapshot for the delta-sum replica sync
-  long long table_elems = 0;    // vocab_size * layer1_size
-  float *exp_table = nullptr;
-  int32_t *table = nullptr;
-  long long table_size = 0;
-  float *keep = nullptr;
-  float *entry = nullptr;       // scratch rows of the sentence-resident kernel
-  size_t entry_floats = 0;
-  float *wide_scratch = nullptr;        // process_word_wide: [workgroups][2][dim]
-  size_t wide_floats = 0;
-  // XCD-shared copies of the hottest rows (XHot in w2b_device.hpp)
-  float *xhot = nullptr;        // [W2B_NXCD]{copies [nu + nv][dim], entries [nu + nv][dim], merge locks [nu + nv][W2B_MAXW]}
-  size_t xhot_floats = 0;
-  float *rc = nullptr;          // row-group kernel: 64 ints of flags + refreshed per-XCD copies of the hottest context rows
-  size_t rc_floats = 0;
-  hipStream_t rc_stream = nullptr;   // the refresher kernel's stream
-  hipEvent_t rc_go = nullptr, rc_end = nullptr;
-  int xhot_nu = -1, xhot_nv = -1;       // layout the buffer currently has (-1: none)
-  bool xhot_master_changed = true;      // the master rows may differ from what the copies were folded into
-  bool debug = false;           // W2B_DEBUG was set when the trainer was created (diagnostics on stderr)
-  const int32_t *corpus = nullptr;
-  int32_t *corpus_owned = nullptr;
-  long long n_tokens = 0;
-  bool corpus_more = false;     // the tokens are a slice of the file and the file continues behind it
-  W2bWorker *workers = nullptr;
-  W2bShared *shared = nullptr;
-  unsigned long long *jump_a = nullptr, *jump_c = nullptr;
-  std::vector<long long> shard_start;
-  std::vector<int> shard_override;
-  bool shards_set = false;
-  // staging for the host-pointer tuple form
-  int32_t *st_center = nullptr, *st_off = nullptr, *st_ctx = nullptr, *st_neg = nullptr;
-  size_t cap_center = 0, cap_off = 0, cap_ctx = 0, cap_neg = 0;
-  // timing
-  bool timing = false;
-  std::vector<hipEvent_t> ev;    // pairs
-  std::vector<hipEvent_t> ev_pool;
-  // RCCL
-  ncclComm_t comm = nullptr;
-  int nranks = 1, rank = 0;
-  // non-blocking progress: after every launch the shared block is copied into a pinned ring slot behind an event
-  static const int kPoll = 4;
-  W2bShared *poll_host = nullptr;          // pinned [kPoll]
-  hipEvent_t poll_ev[kPoll] = {nullptr, nullptr, nullptr, nullptr};
-  long long launches = 0;                  // w2b_train_step calls since w2b_epoch_begin
-  unsigned long long *wca_buf = nullptr;   // [2]: this replica's word_count_actual, the sum over all replicas
-  // replica exchange (see "multi-GPU" below): two exchange streams, chunk staging buffers, events
-  hipStream_t xs[2] = {nullptr, nullptr};
-  float *xd[2] = {nullptr, nullptr}, *xsum[2] = {nullptr, nullptr};   // per slot: own delta / sum over the replicas
-  struct XRange { long long off, len; };    // floats of [u || v]
-  std::vector<XRange> x_ranges;             // the chunks of the exchange in progress (full: the whole model; hot tier: two prefixes)
-  bool x_open = false;                      // the exchange in progress has begun and not ended
-  long long x_words_full = 0;               // centre words since the previous exchange
-  hipEvent_t x_evd[2] = {nullptr, nullptr}, x_evs[2] = {nullptr, nullptr}, x_evc = nullptr;   // delta / sum of a slot complete; counts summed
-  float *xcnt = nullptr;                    // [2 * vocab_size]: replicas that changed each row, then the row's factor on the summed delta (mode 2)
-  float *xrate = nullptr;                   // [2 * vocab_size]: expected updates of every row of [u || v] per trained centre word (from the word counts)
-  std::vector<float> xrate_host;            // (host copy: empty = no word counts yet)
-  bool x_fac_pending = false;               // xcnt holds contributor counts that k_xchg_factor has not yet turned into factors
-  bool x_use_cnt = false;                   // the exchange in progress damps the saturated rows' sums by xcnt
-  int x_sat_u = 0, x_sat_v = 0;             // rows 1..x_sat_* of u / v count as saturated in the exchange in progress
-  long long x_words_sync = 0;               // x_words_full at the begin of the exchange in progress (the n of the combination rule)
-  long long x_words = 0;                    // centre words this replica can have trained since the previous exchange (launches x
-                                            // positions x workers: the same number on every replica of a symmetric job)
-  long long xchunk = 0;                     // floats per chunk
-  hipEvent_t x_train = nullptr;             // "the launches issued so far": the exchange streams wait for it
-  hipEvent_t x_done[2] = {nullptr, nullptr};     // last operation of the latest exchange on each exchange stream
-  bool x_any_done = false;                       // x_done[] have been recorded at least once
-  bool x_pending = false;                   // the training stream has not yet waited for x_done
-  std::vector<hipEvent_t> x_ev;             // (begin, end) pairs of the exchanges since the last w2b_sync_stats
-  long long sync_count = 0;
-  long long sync_bytes = 0;
-};
+// shared with the other host translation units of the library (fail() of w2b_host.h, w2b_eval.cpp)
+int w2b_internal_fail(int code, const char *msg) { g_err = msg ? msg : ""; return code; }
 
 // --------------------------------------------------------------------------------- host tables
 extern "C" const char *w2b_version(void) { return "word2bits-hip 0.1 (gfx950)"; }
@@ -196,7 +97,7 @@ static W2bParams make_params(const w2b_trainer *t, const W2bLaunchPlan &lp) {
   p.v = t->uv + t->table_elems;
   p.exp_table = t->exp_table;
   p.table = t->table;
-  p.table_size = t->table_size;
+  p.table_size = (long long)t->table.cap;
   p.keep = (t->in.cfg.sample > 0) ? t->keep : nullptr;
   p.corpus = t->corpus;
   p.n_tokens = t->n_tokens;
@@ -205,7 +106,7 @@ static W2bParams make_params(const w2b_trainer *t, const W2bLaunchPlan &lp) {
   p.shared = t->shared;
   p.jump_a = t->jump_a;
   p.jump_c = t->jump_c;
-  p.table_magic = t->table_size > 1 ? (unsigned long long)((((unsigned __int128)1) << 64) / (unsigned __int128)t->table_size) : 0;
+  p.table_magic = p.table_size > 1 ? (unsigned long long)((((unsigned __int128)1) << 64) / (unsigned __int128)p.table_size) : 0;
   p.entry = t->entry;
   p.wide_scratch = t->wide_scratch;
   p.xhot = nullptr;                    // set by xhot_prepare() for the launch that uses the copies
@@ -227,14 +128,10 @@ static W2bParams make_params(const w2b_trainer *t, const W2bLaunchPlan &lp) {
 // Device buffer of at least `need` elements, grown on demand: the stream drains before the old buffer is freed (a launch in
 // flight may still use it).  *grown is set when the buffer is a new one (its contents are undefined).
 template <class T>
-static int grow(w2b_trainer *t, T **buf, size_t *cap, size_t need, bool *grown = nullptr) {
-  if (need <= *cap) return W2B_OK;
+static int grow(w2b_trainer *t, W2bDevBuf<T> &buf, size_t need, bool *grown = nullptr) {
+  if (need <= buf.cap) return W2B_OK;
   HIPCHK(hipStreamSynchronize(t->stream));
-  if (*buf) HIPCHK(hipFree(*buf));
-  *buf = nullptr;
-  *cap = 0;
-  HIPCHK(hipMalloc(buf, sizeof(T) * need));
-  *cap = need;
+  HIPCHK(buf.alloc(need));
   if (grown) *grown = true;
   return W2B_OK;
 }
@@ -262,23 +159,23 @@ extern "C" int w2b_trainer_create(const w2b_config *cfg, w2b_trainer **out) {
   t->in.num_cus = prop.multiProcessorCount;
   t->debug = getenv("W2B_DEBUG") != nullptr;
   t->in.tune = w2b_default_tuning();
-  HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+  HIPCHK(t->stream.create());
   t->table_elems = (long long)cfg->vocab_size * cfg->layer1_size;
-  HIPCHK(hipMalloc(&t->uv, sizeof(float) * 2 * t->table_elems));
+  HIPCHK(t->uv.alloc((size_t)(2 * t->table_elems)));
   HIPCHK(hipMemsetAsync(t->uv, 0, sizeof(float) * 2 * t->table_elems, t->stream));
-  HIPCHK(hipMalloc(&t->exp_table, sizeof(float) * (W2B_EXP_TABLE_SIZE + 8)));
+  HIPCHK(t->exp_table.alloc(W2B_EXP_TABLE_SIZE + 8));
   {
     std::vector<float> et(W2B_EXP_TABLE_SIZE + 8, 0.f);
     w2b_build_exp_table(et.data());
     HIPCHK(hipMemcpy(t->exp_table, et.data(), sizeof(float) * et.size(), hipMemcpyHostToDevice));
   }
-  HIPCHK(hipMalloc(&t->shared, sizeof(W2bShared)));
+  HIPCHK(t->shared.alloc(1));
   {
     W2bShared sh{};
     sh.alpha = cfg->alpha;
     HIPCHK(hipMemcpy(t->shared, &sh, sizeof sh, hipMemcpyHostToDevice));
   }
-  HIPCHK(hipMalloc(&t->workers, sizeof(W2bWorker) * cfg->num_threads));
+  HIPCHK(t->workers.alloc((size_t)cfg->num_threads));
   HIPCHK(hipMemset(t->workers, 0, sizeof(W2bWorker) * cfg->num_threads));
   {
     // LCG jump-ahead table: x_{n+k} = A^k x_n + C (A^k - 1)/(A - 1)   (mod 2^64)
@@ -290,8 +187,8 @@ extern "C" int w2b_trainer_create(const w2b_config *cfg, w2b_trainer **out) {
       ja[k] = ja[k - 1] * W2B_LCG_A;
       jc[k] = jc[k - 1] * W2B_LCG_A + W2B_LCG_C;
     }
-    HIPCHK(hipMalloc(&t->jump_a, sizeof(unsigned long long) * nj));
-    HIPCHK(hipMalloc(&t->jump_c, sizeof(unsigned long long) * nj));
+    HIPCHK(t->jump_a.alloc((size_t)nj));
+    HIPCHK(t->jump_c.alloc((size_t)nj));
     HIPCHK(hipMemcpy(t->jump_a, ja.data(), sizeof(unsigned long long) * nj, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(t->jump_c, jc.data(), sizeof(unsigned long long) * nj, hipMemcpyHostToDevice));
   }
@@ -301,9 +198,7 @@ extern "C" int w2b_trainer_create(const w2b_config *cfg, w2b_trainer **out) {
   return W2B_OK;
 }
 
-static int xchg_fence(w2b_trainer *t);      // the training stream waits for a replica exchange in flight (below)
-static void xchg_teardown(w2b_trainer *t);  // streams, events and buffers of the replica exchange
-
+// Every stream is synchronised before anything is released; the members of w2b_trainer then release themselves.
 extern "C" void w2b_trainer_destroy(w2b_trainer *t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
@@ -316,25 +211,19 @@ extern "C" void w2b_trainer_destroy(w2b_trainer *t) {
       fprintf(stderr, "\n");
     }
   }
-  if (t->rc_stream) { (void)hipStreamSynchronize(t->rc_stream); (void)hipStreamDestroy(t->rc_stream); }
-  if (t->rc_go) (void)hipEventDestroy(t->rc_go);
-  if (t->rc_end) (void)hipEventDestroy(t->rc_end);
-  if (t->comm) ncclCommDestroy(t->comm);
-  for (hipEvent_t e : t->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : t->ev_pool) (void)hipEventDestroy(e);
-  for (hipEvent_t e : t->poll_ev) if (e) (void)hipEventDestroy(e);
+  if (t->rc_stream) (void)hipStreamSynchronize(t->rc_stream);
+  w2b_xchg_destroy(t->xchg);
   if (t->poll_host) (void)hipHostFree(t->poll_host);
-  for (hipStream_t q : t->xs) if (q) (void)hipStreamSynchronize(q);
-  for (hipEvent_t e : t->x_ev) (void)hipEventDestroy(e);
-  xchg_teardown(t);
-  void *ptrs[] = {t->uv, t->wca_buf, t->exp_table, t->table, t->keep, t->entry, t->xhot, t->rc, t->wide_scratch, t->corpus_owned, t->workers, t->shared,
-                  t->jump_a, t->jump_c, t->st_center, t->st_off, t->st_ctx, t->st_neg};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
   delete t;
 }
 
+// readers of the model wait for a replica exchange in flight, which has written the master rows
+static int xchg_fence(w2b_trainer *t) {
+  bool waited = false;
+  const int rc = w2b_xchg_fence(t->xchg, &waited);
+  if (waited) t->xhot_master_changed = true;
+  return rc;
+}
 
 // --------------------------------------------------------------------------------- tuning knobs
 extern "C" int w2b_get_tuning(w2b_trainer *t, w2b_tuning *out) {
@@ -372,12 +261,6 @@ extern "C" int w2b_set_tuning(w2b_trainer *t, const w2b_tuning *in) {
   return W2B_OK;
 }
 
-#define NEED(t)                                                                  \
-  do {                                                                           \
-    if (!(t)) return fail(W2B_EINVAL, "null trainer");                          \
-    HIPCHK(hipSetDevice((t)->device));                                           \
-  } while (0)
-
 // --------------------------------------------------------------------------------- model
 extern "C" int w2b_init_net(w2b_trainer *t) {
   NEED(t);
@@ -390,16 +273,13 @@ extern "C" int w2b_init_net(w2b_trainer *t) {
     x = x * W2B_LCG_A + W2B_LCG_C;
     lut[k] = (float)(((x & 0xFFFF) / (float)65536) - 0.5);
   }
-  float *dl = nullptr;
-  HIPCHK(hipMalloc(&dl, sizeof(float) * 65536));
+  W2bDevBuf<float> dl;
+  HIPCHK(dl.alloc(65536));
   HIPCHK(hipMemcpyAsync(dl, lut.data(), sizeof(float) * 65536, hipMemcpyHostToDevice, t->stream));
   HIPCHK(w2b_launch_init_net(t->uv, t->uv + t->table_elems, t->table_elems, dl, t->stream));
   t->xhot_master_changed = true;
-  if (t->base)
-    HIPCHK(hipMemcpyAsync(t->base, t->uv, sizeof(float) * 2 * t->table_elems, hipMemcpyDeviceToDevice,
-                          t->stream));
+  HIPCHK(w2b_xchg_rebase(t->xchg, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
-  HIPCHK(hipFree(dl));
   return W2B_OK;
 }
 
@@ -411,7 +291,7 @@ extern "C" int w2b_set_model(w2b_trainer *t, const float *u, const float *v) {
   HIPCHK(hipMemcpyAsync(t->uv, u, bytes, hipMemcpyHostToDevice, t->stream));
   HIPCHK(hipMemcpyAsync(t->uv + t->table_elems, v, bytes, hipMemcpyHostToDevice, t->stream));
   t->xhot_master_changed = true;
-  if (t->base) HIPCHK(hipMemcpyAsync(t->base, t->uv, 2 * bytes, hipMemcpyDeviceToDevice, t->stream));
+  HIPCHK(w2b_xchg_rebase(t->xchg, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   return W2B_OK;
 }
@@ -454,20 +334,16 @@ extern "C" int w2b_export_quantized(w2b_trainer *t, float *out) {
   if (int rc = xchg_fence(t)) return rc;
   // exported in slabs so that a 14.8 GB table does not need a second full-size device buffer
   const long long slab = 64ll << 20;
-  float *tmp = nullptr;
+  W2bDevBuf<float> tmp;
   const long long n = t->table_elems;
-  HIPCHK(hipMalloc(&tmp, sizeof(float) * (n < slab ? n : slab)));
+  HIPCHK(tmp.alloc((size_t)(n < slab ? n : slab)));
   for (long long o = 0; o < n; o += slab) {
     const long long m = (n - o < slab) ? n - o : slab;
     hipError_t e = w2b_launch_export(t->uv + o, t->uv + t->table_elems + o, tmp, m, t->in.cfg.bitlevel, t->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out + o, tmp, sizeof(float) * m, hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(tmp);
-      return fail(W2B_EHIP, std::string("w2b_export_quantized: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(W2B_EHIP, std::string("w2b_export_quantized: ") + hipGetErrorString(e));
   }
-  HIPCHK(hipFree(tmp));
   return W2B_OK;
 }
 
@@ -479,8 +355,8 @@ extern "C" int w2b_export_packed(w2b_trainer *t, uint64_t *out) {
   if (wpr < 0) return fail(W2B_EUNSUPPORTED, "w2b_export_packed: bit-packed output exists for -bitlevel 1 and 2");
   if (int rc = xchg_fence(t)) return rc;
   const long long V = t->in.cfg.vocab_size, slab_rows = (32ll << 20) / wpr > 0 ? (32ll << 20) / wpr : 1;   // <= 256 MB of words
-  unsigned long long *tmp = nullptr;
-  HIPCHK(hipMalloc(&tmp, sizeof(unsigned long long) * (size_t)((V < slab_rows ? V : slab_rows) * wpr)));
+  W2bDevBuf<unsigned long long> tmp;
+  HIPCHK(tmp.alloc((size_t)((V < slab_rows ? V : slab_rows) * wpr)));
   for (long long r = 0; r < V; r += slab_rows) {
     const long long m = (V - r < slab_rows) ? V - r : slab_rows;
     const long long o = r * t->in.cfg.layer1_size;
@@ -488,12 +364,8 @@ extern "C" int w2b_export_packed(w2b_trainer *t, uint64_t *out) {
                                             t->in.cfg.bitlevel, t->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out + r * wpr, tmp, sizeof(uint64_t) * (size_t)(m * wpr), hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(tmp);
-      return fail(W2B_EHIP, std::string("w2b_export_packed: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(W2B_EHIP, std::string("w2b_export_packed: ") + hipGetErrorString(e));
   }
-  HIPCHK(hipFree(tmp));
   return W2B_OK;
 }
 
@@ -502,24 +374,19 @@ extern "C" int w2b_set_unigram_table(w2b_trainer *t, const int32_t *table, int64
   NEED(t);
   if (!table || tsz <= 0) return fail(W2B_EINVAL, "w2b_set_unigram_table: bad argument");
   HIPCHK(hipStreamSynchronize(t->stream));
-  if (t->table) HIPCHK(hipFree(t->table));
-  t->table = nullptr;
-  HIPCHK(hipMalloc(&t->table, sizeof(int32_t) * tsz));
+  HIPCHK(t->table.alloc((size_t)tsz));
   HIPCHK(hipMemcpy(t->table, table, sizeof(int32_t) * tsz, hipMemcpyHostToDevice));
-  t->table_size = tsz;
   return W2B_OK;
 }
-
-static int xchg_upload_rates(w2b_trainer *t);   // per-row update rates for the replica exchange's combination rule (below)
 
 extern "C" int w2b_set_vocab_counts(w2b_trainer *t, const int64_t *cn, int64_t table_size) {
   NEED(t);
   if (!cn) return fail(W2B_EINVAL, "w2b_set_vocab_counts: null counts");
   const int64_t V = t->in.cfg.vocab_size;
   const std::vector<float> keep = w2b_plan_set_counts(t->in, cn);
-  if (!t->keep) HIPCHK(hipMalloc(&t->keep, sizeof(float) * V));
+  if (!t->keep) HIPCHK(t->keep.alloc((size_t)V));
   HIPCHK(hipMemcpy(t->keep, keep.data(), sizeof(float) * V, hipMemcpyHostToDevice));
-  if (int rc = xchg_upload_rates(t)) return rc;
+  if (int rc = w2b_xchg_upload_rates(t->xchg)) return rc;
   if (table_size > 0) {
     std::vector<int32_t> tab((size_t)table_size);
     int rc = w2b_build_unigram_table(cn, V, tab.data(), table_size);
@@ -540,19 +407,18 @@ extern "C" int w2b_set_exp_table(w2b_trainer *t, const float *et) {
 // --------------------------------------------------------------------------------- timing helpers
 static hipError_t timing_begin(w2b_trainer *t) {
   if (!t->timing) return hipSuccess;
-  hipEvent_t a, b;
+  W2bEvent a, b;
   if (t->ev_pool.size() >= 2) {
-    a = t->ev_pool.back(); t->ev_pool.pop_back();
-    b = t->ev_pool.back(); t->ev_pool.pop_back();
+    a = std::move(t->ev_pool.back()); t->ev_pool.pop_back();
+    b = std::move(t->ev_pool.back()); t->ev_pool.pop_back();
   } else {
-    hipError_t e = hipEventCreate(&a);
-    if (e != hipSuccess) return e;
-    e = hipEventCreate(&b);
+    hipError_t e = a.create(hipEventDefault);
+    if (e == hipSuccess) e = b.create(hipEventDefault);
     if (e != hipSuccess) return e;
   }
-  t->ev.push_back(a);
-  t->ev.push_back(b);
-  return hipEventRecord(a, t->stream);
+  t->ev.push_back(std::move(a));
+  t->ev.push_back(std::move(b));
+  return hipEventRecord(t->ev[t->ev.size() - 2], t->stream);
 }
 static hipError_t timing_end(w2b_trainer *t) {
   if (!t->timing) return hipSuccess;
@@ -576,7 +442,7 @@ extern "C" int w2b_timing_read(w2b_trainer *t, double *kernel_ms, int64_t *launc
   }
   if (kernel_ms) *kernel_ms = ms;
   if (launches) *launches = (int64_t)(t->ev.size() / 2);
-  for (hipEvent_t e : t->ev) t->ev_pool.push_back(e);
+  for (W2bEvent &e : t->ev) t->ev_pool.push_back(std::move(e));
   t->ev.clear();
   return W2B_OK;
 }
@@ -616,9 +482,7 @@ extern "C" int w2b_set_corpus(w2b_trainer *t, const int32_t *ids, int64_t n) {
   for (int64_t i = 0; i < n; i++)       // a bad id would be an out-of-bounds row access on the device
     if (ids[i] < 0 || ids[i] >= t->in.cfg.vocab_size) return fail(W2B_EINVAL, "w2b_set_corpus: token id out of range");
   HIPCHK(hipStreamSynchronize(t->stream));
-  if (t->corpus_owned) HIPCHK(hipFree(t->corpus_owned));
-  t->corpus_owned = nullptr;
-  HIPCHK(hipMalloc(&t->corpus_owned, sizeof(int32_t) * (n > 0 ? n : 1)));
+  HIPCHK(t->corpus_owned.alloc((size_t)(n > 0 ? n : 1)));
   HIPCHK(hipMemcpy(t->corpus_owned, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice));
   t->corpus = t->corpus_owned;
   t->n_tokens = n;
@@ -629,8 +493,7 @@ extern "C" int w2b_set_corpus_device(w2b_trainer *t, const void *ids_dev, int64_
   NEED(t);
   if (!ids_dev || n < 0) return fail(W2B_EINVAL, "w2b_set_corpus_device: bad argument");
   HIPCHK(hipStreamSynchronize(t->stream));
-  if (t->corpus_owned) HIPCHK(hipFree(t->corpus_owned));
-  t->corpus_owned = nullptr;
+  HIPCHK(t->corpus_owned.reset());
   t->corpus = (const int32_t *)ids_dev;
   t->corpus_more = false;
   t->n_tokens = n;
@@ -682,16 +545,16 @@ extern "C" int w2b_epoch_begin(w2b_trainer *t) {
 // buffer, flags and counters of the refreshed copies (W2bLaunchPlan::refresh_rows_u) for one launch of the row-group kernel
 static int rc_prepare(w2b_trainer *t, W2bParams &p, const W2bLaunchPlan &lp) {
   if (lp.refresh_rows_u <= 0) return W2B_OK;
-  if (int rc = grow(t, &t->rc, &t->rc_floats, 64 + (size_t)W2B_NXCD * W2B_RC_MAX * t->in.cfg.layer1_size)) return rc;   // 64 ints of flags, then the copies
+  if (int rc = grow(t, t->rc, 64 + (size_t)W2B_NXCD * W2B_RC_MAX * t->in.cfg.layer1_size)) return rc;   // 64 ints of flags, then the copies
   if (!t->rc_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&t->rc_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&t->rc_go, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&t->rc_end, hipEventDisableTiming));
+    HIPCHK(t->rc_stream.create());
+    HIPCHK(t->rc_go.create());
+    HIPCHK(t->rc_end.create());
   }
   HIPCHK(hipMemsetAsync(t->rc, 0, 64 * sizeof(int), t->stream));                    // claims and alive flags of this launch
   HIPCHK(hipMemsetAsync(&t->shared->launch_done, 0, sizeof(int), t->stream));
   p.rc_rows = lp.refresh_rows_u;
-  p.rc_flags = reinterpret_cast<int *>(t->rc);
+  p.rc_flags = reinterpret_cast<int *>(t->rc.p);
   p.rc = t->rc + 64;
   return W2B_OK;
 }
@@ -699,7 +562,7 @@ static int rc_prepare(w2b_trainer *t, W2bParams &p, const W2bLaunchPlan &lp) {
 // scratch rows of process_word_wide for `workgroups` workgroups
 static int wide_prepare(w2b_trainer *t, W2bParams &p, long long workgroups) {
   if (!p.wide) return W2B_OK;
-  if (int rc = grow(t, &t->wide_scratch, &t->wide_floats, (size_t)workgroups * 2 * t->in.cfg.layer1_size)) return rc;
+  if (int rc = grow(t, t->wide_scratch, (size_t)workgroups * 2 * t->in.cfg.layer1_size)) return rc;
   p.wide_scratch = t->wide_scratch;
   return W2B_OK;
 }
@@ -711,7 +574,7 @@ static int xhot_prepare(w2b_trainer *t, W2bParams &p) {
   if (nu + nv == 0) return W2B_OK;
   const size_t need = (size_t)W2B_NXCD * ((size_t)2 * (nu + nv) * t->in.cfg.layer1_size + (size_t)(nu + nv) * W2B_MAXW);
   bool fresh = (nu != t->xhot_nu || nv != t->xhot_nv);
-  if (int rc = grow(t, &t->xhot, &t->xhot_floats, need, &fresh)) return rc;
+  if (int rc = grow(t, t->xhot, need, &fresh)) return rc;
   p.xhot = t->xhot;
   if (fresh) {         // copy == entry (== 0) everywhere: the fold below adopts the master rows
     HIPCHK(hipMemsetAsync(t->xhot, 0, sizeof(float) * need, t->stream));
@@ -763,14 +626,13 @@ extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
   if (max_positions <= 0) return fail(W2B_EINVAL, "w2b_train_step: max_positions must be positive");
   const W2bLaunchPlan lp = w2b_plan_launch(t->in, t->in.cfg.num_threads);
   if (lp.kernel == W2B_KERNEL_RESIDENT)    // scratch rows of the sentence-resident kernel
-    if (int rc = grow(t, &t->entry, &t->entry_floats,
+    if (int rc = grow(t, t->entry,
                       (size_t)t->in.cfg.num_threads * (size_t)w2b_resident_scratch_rows(lp.radius) * t->in.cfg.layer1_size)) return rc;
   W2bParams p = make_params(t, lp);
   if (int rc = xhot_prepare(t, p)) return rc;
   if (int rc = wide_prepare(t, p, t->in.cfg.num_threads)) return rc;
 
-  t->x_words += (long long)max_positions * t->in.cfg.num_threads;
-  t->x_words_full += (long long)max_positions * t->in.cfg.num_threads;
+  w2b_xchg_add_words(t->xchg, (long long)max_positions * t->in.cfg.num_threads);
   HIPCHK(timing_begin(t));
   if (lp.kernel == W2B_KERNEL_RESIDENT) HIPCHK(w2b_launch_resident(p, max_positions, lp.radius, t->in.cfg.compute_loss != 0, t->stream, t->debug));
   else if (lp.kernel == W2B_KERNEL_GROUPS) {
@@ -806,7 +668,7 @@ extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
   {   // progress snapshot of this launch for w2b_epoch_poll (asynchronous; pinned host memory)
     if (!t->poll_host) {
       HIPCHK(hipHostMalloc((void **)&t->poll_host, sizeof(W2bShared) * w2b_trainer::kPoll, hipHostMallocDefault));
-      for (int i = 0; i < w2b_trainer::kPoll; i++) HIPCHK(hipEventCreateWithFlags(&t->poll_ev[i], hipEventDisableTiming));
+      for (int i = 0; i < w2b_trainer::kPoll; i++) HIPCHK(t->poll_ev[i].create());
     }
     const int slot = (int)(t->launches % w2b_trainer::kPoll);
     HIPCHK(hipMemcpyAsync(&t->poll_host[slot], t->shared, sizeof(W2bShared), hipMemcpyDeviceToHost, t->stream));
@@ -916,10 +778,10 @@ extern "C" int w2b_train_tuples(w2b_trainer *t, int64_t n, const int32_t *center
     return W2B_OK;
   }
   int rc;
-  if ((rc = grow(t, &t->st_center, &t->cap_center, n))) return rc;
-  if ((rc = grow(t, &t->st_off, &t->cap_off, n + 1))) return rc;
-  if ((rc = grow(t, &t->st_ctx, &t->cap_ctx, nctx > 0 ? nctx : 1))) return rc;
-  if ((rc = grow(t, &t->st_neg, &t->cap_neg, (size_t)n * (K > 0 ? K : 1)))) return rc;
+  if ((rc = grow(t, t->st_center, n))) return rc;
+  if ((rc = grow(t, t->st_off, n + 1))) return rc;
+  if ((rc = grow(t, t->st_ctx, nctx > 0 ? nctx : 1))) return rc;
+  if ((rc = grow(t, t->st_neg, (size_t)n * (K > 0 ? K : 1)))) return rc;
   HIPCHK(hipMemcpyAsync(t->st_center, center, sizeof(int32_t) * n, hipMemcpyHostToDevice, t->stream));
   HIPCHK(hipMemcpyAsync(t->st_off, ctx_off, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, t->stream));
   if (nctx) HIPCHK(hipMemcpyAsync(t->st_ctx, ctx, sizeof(int32_t) * nctx, hipMemcpyHostToDevice, t->stream));
@@ -935,429 +797,5 @@ extern "C" int w2b_train_tuples(w2b_trainer *t, int64_t n, const int32_t *center
     if (t->in.cfg.compute_loss)
       HIPCHK(hipMemcpy(loss_out, &t->shared->loss_tuples, sizeof(double), hipMemcpyDeviceToHost));
   }
-  return W2B_OK;
-}
-
-// --------------------------------------------------------------------------------- multi-GPU (RCCL)
-extern "C" int w2b_comm_unique_id(void *out128) {
-  if (!out128) return fail(W2B_EINVAL, "w2b_comm_unique_id: null");
-  static_assert(sizeof(ncclUniqueId) == W2B_UNIQUE_ID_BYTES, "ncclUniqueId size");
-  ncclUniqueId id;
-  NCCLCHK(ncclGetUniqueId(&id));
-  memcpy(out128, &id, sizeof id);
-  return W2B_OK;
-}
-
-// Buffers, streams and events of the replica exchange (first use).  xs[0] is the ELEMENTWISE stream (delta / apply /
-// touched kernels, the begin / end events), xs[1] the COLLECTIVE stream: RCCL serialises the collectives of one
-// communicator anyway, so one stream carries all of them, and the elementwise kernels of chunk c + 1 run while the
-// collective of chunk c is on the links (round 3 alternated whole chunks between two streams and claimed an overlap of
-// the two collectives that RCCL does not give).
-static void xchg_teardown(w2b_trainer *t) {
-  for (int k = 0; k < 2; k++) {
-    if (t->xs[k]) (void)hipStreamSynchronize(t->xs[k]);
-    if (t->xd[k]) (void)hipFree(t->xd[k]);
-    if (t->xsum[k]) (void)hipFree(t->xsum[k]);
-    if (t->x_done[k]) (void)hipEventDestroy(t->x_done[k]);
-    if (t->x_evd[k]) (void)hipEventDestroy(t->x_evd[k]);
-    if (t->x_evs[k]) (void)hipEventDestroy(t->x_evs[k]);
-    if (t->xs[k]) (void)hipStreamDestroy(t->xs[k]);
-    t->xd[k] = t->xsum[k] = nullptr;
-    t->x_done[k] = t->x_evd[k] = t->x_evs[k] = nullptr;
-    t->xs[k] = nullptr;
-  }
-  if (t->x_train) (void)hipEventDestroy(t->x_train);
-  if (t->x_evc) (void)hipEventDestroy(t->x_evc);
-  t->x_train = t->x_evc = nullptr;
-  t->x_any_done = false;
-  if (t->xcnt) (void)hipFree(t->xcnt);
-  if (t->xrate) (void)hipFree(t->xrate);
-  if (t->base) (void)hipFree(t->base);
-  t->xcnt = nullptr;
-  t->xrate = nullptr;
-  t->base = nullptr;
-}
-
-// Expected updates of every row of [u || v] per trained centre word, from the word counts (what w2b_plan_set_counts computes for the
-// leading rows, for all of them): a context row (u) is updated once per window it is in -- window + 1 windows per kept
-// occurrence on average --, a target row (v) once per draw from the unigram table (ref :112-128, 455-458: raw
-// counts; row 0 is remapped, never drawn) and once as the centre word.  "Kept": what survives sub-sampling (ref :403-406).
-static int xchg_upload_rates(w2b_trainer *t) {
-  if (!t->xrate || t->in.counts.empty() || t->in.counts_tot_kept <= 0 || t->in.counts_pw <= 0) return W2B_OK;
-  const long long V = t->in.cfg.vocab_size;
-  std::vector<float> r((size_t)(2 * V), 0.f);
-  for (long long a = 1; a < V; a++) {
-    const double c = (double)t->in.counts[(size_t)a], k = w2b_plan_kept(t->in, c) / t->in.counts_tot_kept;
-    r[(size_t)a] = (float)((t->in.cfg.window + 1) * k);
-    r[(size_t)(V + a)] = (float)(t->in.cfg.negative * pow(c, 0.75) / t->in.counts_pw + k);
-  }
-  HIPCHK(hipMemcpy(t->xrate, r.data(), sizeof(float) * 2 * V, hipMemcpyHostToDevice));
-  t->xrate_host.swap(r);
-  return W2B_OK;
-}
-
-static int xchg_setup(w2b_trainer *t) {
-  if (t->base) return W2B_OK;
-  const long long n = 2 * t->table_elems;
-  // chunks of at most 64 M floats (256 MB): small enough that the elementwise kernels of one chunk overlap with the
-  // collective of the other, large enough that a ring all-reduce over xGMI runs at its bus bandwidth
-  t->xchunk = n < (64ll << 20) ? ((n + 3) & ~3ll) : (64ll << 20);
-  hipError_t e = hipMalloc(&t->base, sizeof(float) * n);
-  for (int k = 0; k < 2 && e == hipSuccess; k++) {
-    e = hipMalloc(&t->xd[k], sizeof(float) * t->xchunk);
-    if (e == hipSuccess) e = hipMalloc(&t->xsum[k], sizeof(float) * t->xchunk);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&t->xs[k], hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_done[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_evd[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_evs[k], hipEventDisableTiming);
-  }
-  if (e == hipSuccess && !t->wca_buf) e = hipMalloc(&t->wca_buf, 2 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&t->xcnt, sizeof(float) * 2 * t->in.cfg.vocab_size);
-  if (e == hipSuccess) e = hipMemsetAsync(t->xcnt, 0, sizeof(float) * 2 * t->in.cfg.vocab_size, t->stream);
-  if (e == hipSuccess) e = hipMalloc(&t->xrate, sizeof(float) * 2 * t->in.cfg.vocab_size);
-  if (e == hipSuccess) e = hipMemsetAsync(t->xrate, 0, sizeof(float) * 2 * t->in.cfg.vocab_size, t->stream);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_train, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&t->x_evc, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->base, t->uv, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  if (e != hipSuccess) {
-    xchg_teardown(t);                          // everything or nothing: a retry starts from scratch
-    return fail(W2B_EHIP, std::string("replica exchange setup: ") + hipGetErrorString(e));
-  }
-  if (int rc = xchg_upload_rates(t)) { xchg_teardown(t); return rc; }   // (word counts given later: w2b_set_vocab_counts uploads them)
-  return W2B_OK;
-}
-
-// The training stream (and with it every reader of the model) waits for the exchange in flight.
-static int xchg_fence(w2b_trainer *t) {
-  if (!t->x_pending) return W2B_OK;
-  for (int k = 0; k < 2; k++) HIPCHK(hipStreamWaitEvent(t->stream, t->x_done[k], 0));
-  t->x_pending = false;
-  t->xhot_master_changed = true;
-  return W2B_OK;
-}
-
-extern "C" int w2b_comm_init(w2b_trainer *t, int32_t nranks, int32_t rank, const void *id128) {
-  NEED(t);
-  if (nranks < 1 || rank < 0 || rank >= nranks) return fail(W2B_EINVAL, "w2b_comm_init: bad rank");
-  t->nranks = nranks;
-  t->rank = rank;
-  // replicas of one and no id: nothing to exchange.  With an id a communicator of size 1 is created all the same, so
-  // that the whole exchange path (delta, all-reduce, apply, progress counters) can run on a one-GPU machine.
-  if (nranks == 1 && !id128) return W2B_OK;
-  if (!id128) return fail(W2B_EINVAL, "w2b_comm_init: null id");
-  ncclUniqueId id;
-  memcpy(&id, id128, sizeof id);
-  NCCLCHK(ncclCommInitRank(&t->comm, nranks, id, rank));
-  if (int rc = xchg_setup(t)) {                 // leave the trainer as a single replica, not half-initialised
-    ncclCommDestroy(t->comm);
-    t->comm = nullptr;
-    t->nranks = 1;
-    t->rank = 0;
-    return rc;
-  }
-  return W2B_OK;
-}
-
-extern "C" int w2b_comm_count(w2b_trainer *t, int32_t *nranks_out) {
-  if (!t || !nranks_out) return fail(W2B_EINVAL, "w2b_comm_count: null argument");
-  *nranks_out = 0;
-  if (!t->comm) return W2B_OK;
-  int n = 0;
-  NCCLCHK(ncclCommCount(t->comm, &n));
-  *nranks_out = n;
-  return W2B_OK;
-}
-
-// ---- one exchange = a list of RANGES of [u || v], each at most one staging buffer long.  A FULL exchange covers the whole
-// model in chunks.  (Round 4's HOT-TIER exchange -- the leading rows of both tables only, after every launch -- measured no
-// gain over the full exchanges alone and was removed from the ABI in round 5: DESIGN.md Appendix A.)
-static long long xchg_chunks(const w2b_trainer *t) { return (long long)t->x_ranges.size(); }
-
-static void xchg_add_range(w2b_trainer *t, long long off, long long len) {
-  for (long long o = 0; o < len; o += t->xchunk) {
-    const long long m = len - o < t->xchunk ? len - o : t->xchunk;
-    t->x_ranges.push_back({off + o, m});
-  }
-}
-
-extern "C" int w2b_exchange_init(w2b_trainer *t) {
-  NEED(t);
-  return xchg_setup(t);
-}
-
-// Which rows are SATURATED -- have been updated so often in this replica over `words` centre words that the replica's
-// delta is no longer a small step.  A row that is a target (v) / a context row (u) of `rate` centre words has received
-// rate x words updates; at alpha = 0.05 a few dozen updates move a row most of the way, so W2B_SAT_UPDATES = 32 of them
-// make it saturated.  The vocabulary is sorted by count: a prefix per table.
-static const double W2B_SAT_UPDATES = 32.0;
-static void xchg_saturated_prefix(const w2b_trainer *t, long long words, int *sat_u, int *sat_v) {
-  *sat_u = *sat_v = 0;
-  const long long V = t->in.cfg.vocab_size;
-  if (t->in.counts.empty() || t->in.counts_tot <= 0 || words <= 0) return;
-  const double sat = t->in.tune.exchange_sat_updates > 0 ? (double)t->in.tune.exchange_sat_updates : W2B_SAT_UPDATES;
-  auto prefix = [&](bool is_v) -> int {
-    long long lo = 0, hi = V - 1;
-    while (lo < hi) {
-      const long long mid = (lo + hi + 1) / 2;
-      const double c = (double)t->in.counts[(size_t)mid];
-      const double rate = is_v ? w2b_plan_rate_v(t->in, c) : (t->in.cfg.window + 1) * c / t->in.counts_tot;
-      if (rate * (double)words >= sat) lo = mid; else hi = mid - 1;
-    }
-    return (int)lo;
-  };
-  *sat_u = prefix(false);
-  *sat_v = prefix(true);
-}
-
-static void xchg_abort(w2b_trainer *t) {       // an exchange that failed between begin and end: forget its (begin, end) events
-  if (t->x_open && t->x_ev.size() >= 2) {
-    (void)hipEventDestroy(t->x_ev.back()); t->x_ev.pop_back();
-    (void)hipEventDestroy(t->x_ev.back()); t->x_ev.pop_back();
-  }
-  t->x_open = false;
-}
-
-static int xchg_begin(w2b_trainer *t) {
-  if (!t->base) return fail(W2B_ESTATE, "replica exchange: w2b_comm_init / w2b_exchange_init first (while all replicas "
-                                        "still hold the same model)");
-  if (t->x_open) return fail(W2B_ESTATE, "replica exchange: the previous exchange was not ended (w2b_exchange_end)");
-  while (t->x_ev.size() >= 512) {            // nobody reads the timings (w2b_sync_stats): keep the list bounded
-    HIPCHK(hipEventSynchronize(t->x_ev[1]));
-    (void)hipEventDestroy(t->x_ev[0]);
-    (void)hipEventDestroy(t->x_ev[1]);
-    t->x_ev.erase(t->x_ev.begin(), t->x_ev.begin() + 2);
-  }
-  // the exchange sees every launch issued so far (and nothing forces the launches issued later to wait for a FULL exchange)
-  HIPCHK(hipEventRecord(t->x_train, t->stream));
-  for (int k = 0; k < 2; k++) HIPCHK(hipStreamWaitEvent(t->xs[k], t->x_train, 0));
-  // ... and follows the PREVIOUS exchange on both of its streams: the collective stream's first operations of this exchange
-  // (word counts, per-row contributor counts: they read `base`, write `xcnt`) must not run beside the previous exchange's
-  // last apply on the elementwise stream (reads `xcnt`, writes `base`).  x_done[0] is recorded after the elementwise stream
-  // has waited for the collective one (xchg_end), so it covers both.
-  if (t->x_any_done) for (int k = 0; k < 2; k++) HIPCHK(hipStreamWaitEvent(t->xs[k], t->x_done[0], 0));
-  hipEvent_t a, b;
-  HIPCHK(hipEventCreate(&a));
-  HIPCHK(hipEventCreate(&b));
-  t->x_ev.push_back(a);
-  t->x_ev.push_back(b);
-  t->x_open = true;
-  {
-    const hipError_t e = hipEventRecord(a, t->xs[0]);
-    if (e != hipSuccess) { xchg_abort(t); return fail(W2B_EHIP, std::string("replica exchange begin: ") + hipGetErrorString(e)); }
-  }
-  t->x_ranges.clear();
-  xchg_add_range(t, 0, 2 * t->table_elems);
-  xchg_saturated_prefix(t, t->x_words_full, &t->x_sat_u, &t->x_sat_v);    // over the words since the last exchange
-  t->x_words_sync = t->x_words_full;
-  t->x_fac_pending = false;
-  return W2B_OK;
-}
-static int xchg_delta(w2b_trainer *t, long long c) {
-  const auto &r = t->x_ranges[(size_t)c];
-  const int k = (int)(c & 1);
-  HIPCHK(w2b_launch_xchg_delta(t->uv + r.off, t->base + r.off, t->xd[k], t->xsum[k], r.len, t->xs[0]));
-  return W2B_OK;
-}
-// ---- the combination rule of mode 2: a per-row factor on the SUM of the replicas' deltas (k_xchg_factor has the formulas).
-// Round 6 measured three families on 8 replicas x 128 workers against the single replica with the same 1024 workers
-// (tests/experiments/replica_rules.py, replica_truth.py; profiles/r06_sessions/):
-//   * the hard threshold of rounds 4-5 (mean of the contributors from 32 expected updates on, sum below): -9.0 % of the single
-//     replica's epoch loss at 131 K words per replica between two exchanges, -9.9 % at 16 K;
-//   * exponential saturation (rule 2): -7.4 % (tau = 64; 8: -14 %, 32: -8.1 %, 128: -7.7 %, 256: -9.1 %);
-//   * the per-row least-squares factor of a truth run's delta on the replicas' summed delta (0.75 at one update, falling only
-//     logarithmically: 0.45 at 256 updates) -- optimal for ONE interval from a common model, and divergent in closed loop: -18 %,
-//     the final model worthless.  It is dominated by the drift of the fp32 masters (which no forward value sees) and over-relaxes the
-//     elements near a sign flip (which every forward value sees).  Not shipped; the measurement stays in the experiment scripts.
-//   * rule 0, the default: exponential saturation decides every element's QUANTIZED value, and where the whole sum lands in the
-//     same quantization cell it is taken instead (k_xchg_apply) -- the forward values of the stable rule, the masters' inertia of a
-//     shared model: -2.9 % at 131 K words per replica on the 22 M-token proxy (-0.3 % with doubling intervals), -0.5 % on the
-//     literal configs[1] stream at 1 M words.  ONE BIT ONLY: there a forward value is a sign and a master's magnitude is pure inertia.
-//     With more bits the magnitude is part of the forward value and the cells do harm -- two bits, same proxy at 86 K words: cells
-//     -9.4 %, saturation alone -1.9 %, the sign alone as the criterion diverges (four bits: cells -6.3 %; profiles/r06_sessions/r06o,
-//     r06p) -- so every other bitlevel runs the saturation factor alone.
-// contributor counts in xcnt -> factors on the summed delta (k_xchg_factor), once per exchange, on stream q
-static const double W2B_XCHG_TAU_U = 64.0, W2B_XCHG_TAU_V = 64.0;   // updates that move a row most of the way
-static int xchg_factor(w2b_trainer *t, hipStream_t q) {
-  if (!t->x_fac_pending) return W2B_OK;
-  const int rule = t->in.tune.exchange_rule;
-  const float tau_u = t->in.tune.exchange_tau_u > 0 ? (float)t->in.tune.exchange_tau_u : (float)W2B_XCHG_TAU_U;
-  const float tau_v = t->in.tune.exchange_tau_v > 0 ? (float)t->in.tune.exchange_tau_v : (float)W2B_XCHG_TAU_V;
-  HIPCHK(w2b_launch_xchg_factor(t->xcnt, t->xrate_host.empty() ? nullptr : t->xrate, (float)t->x_words_sync, tau_u, tau_v, t->in.cfg.vocab_size,
-                                rule, t->x_sat_u, t->x_sat_v, q));
-  t->x_fac_pending = false;
-  return W2B_OK;
-}
-static int xchg_apply(w2b_trainer *t, long long c, float scale) {
-  const auto &r = t->x_ranges[(size_t)c];
-  const int k = (int)(c & 1);
-  if (t->x_use_cnt) if (int rc = xchg_factor(t, t->xs[0])) return rc;
-  HIPCHK(w2b_launch_xchg_apply(t->uv + r.off, t->base + r.off, t->xd[k], t->xsum[k], scale, r.len, t->x_use_cnt ? t->xcnt : nullptr,
-                               r.off, t->in.cfg.layer1_size, t->in.cfg.bitlevel, (t->in.tune.exchange_rule == 0 && t->in.cfg.bitlevel == 1) ? 1 : 0, t->xs[0]));
-  return W2B_OK;
-}
-// per row of [u || v]: has this replica changed it since the last exchange?
-static int xchg_touched(w2b_trainer *t, hipStream_t s) {
-  const long long V = t->in.cfg.vocab_size, D = t->in.cfg.layer1_size;
-  return w2b_launch_xchg_touched(t->uv, t->base, t->xcnt, 2 * V, (int)D, s) == hipSuccess ? W2B_OK : fail(W2B_EHIP, "k_xchg_touched");
-}
-
-static int xchg_end(w2b_trainer *t) {
-  t->x_words_full = 0;
-  t->x_words = 0;
-  // x_ev.back() = the end of this exchange: the elementwise stream waits for the collective stream's last operation first
-  HIPCHK(hipEventRecord(t->x_done[1], t->xs[1]));
-  HIPCHK(hipStreamWaitEvent(t->xs[0], t->x_done[1], 0));
-  HIPCHK(hipEventRecord(t->x_ev.back(), t->xs[0]));
-  HIPCHK(hipEventRecord(t->x_done[0], t->xs[0]));
-  t->x_any_done = true;
-  t->x_open = false;
-  t->x_pending = true;
-  t->sync_count++;
-  long long bytes = 0;
-  for (const auto &r : t->x_ranges) bytes += r.len * (long long)sizeof(float);
-  t->sync_bytes += bytes;
-  return W2B_OK;
-}
-
-// The library's own collective.  Software pipeline over the chunks: E = xs[0] (elementwise), C = xs[1] (collective)
-//      E: delta(0) delta(1) apply(0) delta(2) apply(1) ...          C: sum(0) sum(1) sum(2) ...
-// with events delta(c) -> sum(c) -> apply(c); slot c & 1 of the staging buffers is free again when apply(c) has been issued
-// on E before delta(c + 2).
-static int xchg_run_rccl(w2b_trainer *t, int32_t mode) {
-  hipStream_t E = t->xs[0], Cs = t->xs[1];
-  // progress first (16 bytes): every replica learns the global word count -- the alpha schedule (ref :391) is exact
-  // at every exchange and extrapolates in between (W2bShared::wca_others)
-  HIPCHK(w2b_launch_wca_pack(t->shared, t->wca_buf, Cs));
-  NCCLCHK(ncclAllReduce(t->wca_buf, t->wca_buf + 1, 1, ncclUint64, ncclSum, t->comm, Cs));
-  HIPCHK(w2b_launch_wca_unpack(t->shared, t->wca_buf, Cs));
-  const float scale = mode == 1 ? 1.f / (float)t->nranks : 1.f;
-  t->x_use_cnt = mode == 2;
-  if (mode == 2) {          // who has trained which row since the last exchange (2 V floats), before the first apply
-    if (int rc = xchg_touched(t, Cs)) return rc;
-    NCCLCHK(ncclAllReduce(t->xcnt, t->xcnt, (size_t)(2 * t->in.cfg.vocab_size), ncclFloat, ncclSum, t->comm, Cs));
-    t->x_fac_pending = true;
-    if (int rc = xchg_factor(t, Cs)) return rc;
-    HIPCHK(hipEventRecord(t->x_evc, Cs));
-    HIPCHK(hipStreamWaitEvent(E, t->x_evc, 0));
-  }
-  const long long nc = xchg_chunks(t);
-  auto issue_delta_sum = [&](long long c) -> int {
-    const int k = (int)(c & 1);
-    if (int rc = xchg_delta(t, c)) return rc;
-    HIPCHK(hipEventRecord(t->x_evd[k], E));
-    HIPCHK(hipStreamWaitEvent(Cs, t->x_evd[k], 0));
-    NCCLCHK(ncclAllReduce(t->xsum[k], t->xsum[k], (size_t)t->x_ranges[(size_t)c].len, ncclFloat, ncclSum, t->comm, Cs));
-    HIPCHK(hipEventRecord(t->x_evs[k], Cs));
-    return W2B_OK;
-  };
-  if (nc > 0) if (int rc = issue_delta_sum(0)) return rc;
-  for (long long c = 0; c < nc; c++) {
-    if (c + 1 < nc) if (int rc = issue_delta_sum(c + 1)) return rc;
-    HIPCHK(hipStreamWaitEvent(E, t->x_evs[c & 1], 0));
-    if (int rc = xchg_apply(t, c, scale)) return rc;
-  }
-  return W2B_OK;
-}
-
-extern "C" int64_t w2b_suggested_exchange_words(int64_t train_words_per_epoch, int32_t replicas) {
-  if (replicas < 1) replicas = 1;
-  long long words = train_words_per_epoch / replicas / 32;
-  if (words < 32768) words = 32768;
-  if (words > 1048576) words = 1048576;
-  return words;
-}
-
-extern "C" int w2b_sync_replicas(w2b_trainer *t, int32_t mode) {
-  NEED(t);
-  if (!t->comm) return W2B_OK;             // a single replica without a communicator: nothing to exchange
-  if (mode < 0 || mode > 2) return fail(W2B_EINVAL, "w2b_sync_replicas: unknown mode");
-  if (int rc = xchg_begin(t)) return rc;
-  if (int rc = xchg_run_rccl(t, mode)) { xchg_abort(t); return rc; }
-  return xchg_end(t);
-}
-
-// ---- the same exchange for a host that brings its own collective (MPI, torch.distributed over gloo / RCCL, ...):
-//   w2b_exchange_begin -> (w2b_exchange_counts, <sum over the replicas>) -> for every chunk: w2b_exchange_delta,
-//   <sum *buf over the replicas, in place>, w2b_exchange_apply -> w2b_exchange_end.  The buffer handed out is device
-// memory; the library's kernels run on its elementwise exchange stream, so w2b_exchange_delta returns after the delta is
-// complete (the host's collective may use any stream or the CPU) and w2b_exchange_apply expects the sum to be complete
-// when it is called.
-static int xchg_begin_host(w2b_trainer *t, int64_t *n_chunks, int64_t *local_word_count) {
-  if (int rc = xchg_begin(t)) return rc;
-  t->x_use_cnt = false;
-  if (n_chunks) *n_chunks = xchg_chunks(t);
-  if (local_word_count) {
-    hipError_t e = w2b_launch_wca_pack(t->shared, t->wca_buf, t->xs[0]);
-    unsigned long long v = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&v, t->wca_buf, sizeof v, hipMemcpyDeviceToHost, t->xs[0]);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->xs[0]);
-    if (e != hipSuccess) { xchg_abort(t); return fail(W2B_EHIP, std::string("w2b_exchange_begin: ") + hipGetErrorString(e)); }
-    *local_word_count = (int64_t)v;
-  }
-  return W2B_OK;
-}
-extern "C" int w2b_exchange_begin(w2b_trainer *t, int64_t *n_chunks, int64_t *local_word_count) {
-  NEED(t);
-  return xchg_begin_host(t, n_chunks, local_word_count);
-}
-extern "C" int w2b_exchange_counts(w2b_trainer *t, void **buf_dev, int64_t *elems) {
-  NEED(t);
-  if (!t->base || !t->x_open) return fail(W2B_ESTATE, "w2b_exchange_counts: w2b_exchange_begin first");
-  if (!buf_dev || !elems) return fail(W2B_EINVAL, "w2b_exchange_counts: null argument");
-  if (int rc = xchg_touched(t, t->xs[0])) return rc;
-  HIPCHK(hipStreamSynchronize(t->xs[0]));
-  t->x_use_cnt = true;
-  t->x_fac_pending = true;                   // (the host sums the counts; the first w2b_exchange_apply turns them into factors)
-  *buf_dev = t->xcnt;
-  *elems = 2 * t->in.cfg.vocab_size;
-  return W2B_OK;
-}
-
-extern "C" int w2b_exchange_delta(w2b_trainer *t, int64_t chunk, void **buf_dev, int64_t *elems) {
-  NEED(t);
-  if (!t->base || !t->x_open) return fail(W2B_ESTATE, "w2b_exchange_delta: w2b_exchange_begin first");
-  if (chunk < 0 || chunk >= xchg_chunks(t) || !buf_dev || !elems) return fail(W2B_EINVAL, "w2b_exchange_delta: bad argument");
-  if (int rc = xchg_delta(t, chunk)) return rc;
-  HIPCHK(hipStreamSynchronize(t->xs[0]));
-  *buf_dev = t->xsum[chunk & 1];
-  *elems = t->x_ranges[(size_t)chunk].len;
-  return W2B_OK;
-}
-extern "C" int w2b_exchange_apply(w2b_trainer *t, int64_t chunk, float scale) {
-  NEED(t);
-  if (!t->base || !t->x_open) return fail(W2B_ESTATE, "w2b_exchange_apply: w2b_exchange_begin first");
-  if (chunk < 0 || chunk >= xchg_chunks(t)) return fail(W2B_EINVAL, "w2b_exchange_apply: bad chunk");
-  return xchg_apply(t, chunk, scale);
-}
-extern "C" int w2b_exchange_end(w2b_trainer *t, int64_t word_count_all_replicas) {
-  NEED(t);
-  if (!t->base || !t->x_open) return fail(W2B_ESTATE, "w2b_exchange_end: w2b_exchange_begin first");
-  if (word_count_all_replicas >= 0) {        // the alpha schedule runs on the global count (ref :391)
-    unsigned long long v = (unsigned long long)word_count_all_replicas;
-    HIPCHK(hipMemcpyAsync(t->wca_buf + 1, &v, sizeof v, hipMemcpyHostToDevice, t->xs[0]));
-    HIPCHK(hipStreamSynchronize(t->xs[0]));
-    HIPCHK(w2b_launch_wca_unpack(t->shared, t->wca_buf, t->xs[0]));
-  }
-  return xchg_end(t);
-}
-
-extern "C" int w2b_sync_stats(w2b_trainer *t, int64_t *exchanges, double *device_ms) {
-  if (!t) return fail(W2B_EINVAL, "null trainer");
-  HIPCHK(hipSetDevice(t->device));
-  if (exchanges) *exchanges = t->sync_count;
-  double ms = 0;
-  if (t->x_open) return fail(W2B_ESTATE, "w2b_sync_stats: an exchange is in progress (w2b_exchange_end first)");
-  for (size_t i = 0; i + 1 < t->x_ev.size(); i += 2) {      // begin -> end of every exchange, read after the fact
-    HIPCHK(hipEventSynchronize(t->x_ev[i + 1]));
-    float m = 0;
-    HIPCHK(hipEventElapsedTime(&m, t->x_ev[i], t->x_ev[i + 1]));
-    ms += m;
-  }
-  for (hipEvent_t e : t->x_ev) (void)hipEventDestroy(e);
-  t->x_ev.clear();
-  if (device_ms) *device_ms = ms;
-  t->sync_count = 0;
-  t->sync_bytes = 0;
   return W2B_OK;
 }
