@@ -68,6 +68,28 @@ int w2b_eval_topk(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2,
                   int32_t *best, float *bestd);
 /* The neighbours of a word: vec = M[row], only `row` is skipped.  Equals w2b_eval_topk(b1 = b2 = b3 = rows). */
 int w2b_eval_neighbors(w2b_eval *e, int64_t nq, const int32_t *rows, int32_t k, int32_t *best, float *bestd);
+/* The general form of both: a question is a sum of signed rows (word2vec's `distance` on a phrase; gensim's
+ * most_similar(positive, negative)).  rows / signs are [nq][nt], 1 <= nt <= W2B_EVAL_MAX_TERMS; a slot with sign 0 is unused
+ * and its row is ignored.  The same row may stand in several slots: its coefficients add.  Every used slot's row is
+ * excluded from that question's answers.  best / bestd are [nq][k] and have the shape of w2b_eval_topk's: best first,
+ * equal scores in ascending row order, a short list ends in row -1 / score 0; bestd may be NULL.
+ *   fp32 handle: the used slots in slot order; vec[a] starts as M[r0][a] (sign +1) or its exact negation (sign -1), every
+ *     further slot is ONE float32 add or subtract of M[rt][a], rounded on its own; the score of row c is the chain that
+ *     w2b_eval_top1 runs on that vec (the handle's `fused` mode and w2b_eval_set_kernel variant); answers are the rows
+ *     with score > 0.  So slots (+b2, -b1, +b3) give bit for bit what w2b_eval_topk(b1, b2, b3) gives, and one slot (+r)
+ *     what w2b_eval_neighbors gives.
+ *   bits handle: t[a] = sum over the used slots of sign * s_r[a], an integer in [-nt, nt], zero included;
+ *     I(c) = sum_a t[a] * s_c[a], exact; answers are the rows with I > 0, by I descending then row ascending, score
+ *     (float)I / (float)size.  Slots (+b2, -b1, +b3) again equal w2b_eval_topk exactly.
+ *   codes handle: W2B_EINVAL ("not available in codes mode").  Deliberately: the 2-bit scan keeps three accumulator tiles
+ *     per (question, row) next to 104-152 registers of unpacked rows, and a per-question number of terms does not fit that
+ *     shape without another kernel design.
+ * W2B_EINVAL, with the cause in w2b_last_error(): nt outside 1..W2B_EVAL_MAX_TERMS, k outside 1..W2B_EVAL_MAX_K, a sign
+ * other than -1, 0, +1, a used slot's row outside [0, words), a question without a used slot.
+ * w2b_eval_timing_read counts these launches like the top-k ones, and w2b_eval_set_topk_scratch bounds their scratch. */
+#define W2B_EVAL_MAX_TERMS 7
+int w2b_eval_combine(w2b_eval *e, int64_t nq, int32_t nt, const int32_t *rows, const int8_t *signs, int32_t k,
+                     int32_t *best, float *bestd);
 /* Upper bound in bytes for the device scratch (candidate slots) of one top-k launch; 0 = the default, 1 GiB.  The
  * questions are scored in chunks that fit, never smaller than 128 questions.  Results never depend on it. */
 int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes);
@@ -80,6 +102,14 @@ int w2b_eval_set_topk_scratch(w2b_eval *e, int64_t bytes);
  * (the first such word).  All lines are scored in one w2b_eval_topk batch.  *out is malloc'ed; release it with
  * w2b_eval_free_text. */
 int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out, int64_t *out_len);
+
+/* The text form of `./nearest ... signed`: every non-empty line is 1 to W2B_EVAL_MAX_TERMS tokens +WORD, -WORD or WORD (a
+ * bare word counts as +; only the first character of a token is read as a sign), the words upper-cased and looked up as in
+ * w2b_eval_nearest_text: "new york", "+king -man +woman".  The answer has the format of w2b_eval_nearest_text; the head is
+ * the tokens as given, upper-cased and joined by one space.  Error lines: "<head>: expected 1 to 7 signed words\n" and
+ * "<head>: not in vocabulary: <WORD>\n" (the first such word, without its sign).  All valid lines are scored in one
+ * w2b_eval_combine batch. */
+int w2b_eval_combine_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out, int64_t *out_len);
 
 /* ref :94,113-188: the program's stdout for the question stream `questions[0..len)` (what the reference reads
  * from stdin with scanf("%s")), including "Starting eval...".  *out is malloc'ed; release it with
@@ -108,8 +138,8 @@ int w2b_eval_timing_read(w2b_eval *e, double *kernel_ms, int64_t *launches, doub
  * reported score is (float)I / (float)size, one correctly rounded division.  The fp32 modes above agree with this
  * ranking wherever I differs and order rows of equal I by rounding noise instead; a row with I == 0, which they
  * sometimes score as a tiny positive number, is never an answer here.
- * On a bits handle w2b_eval_top1 / _topk / _neighbors / _nearest_text / _transcript / _set_topk_scratch /
- * _timing_read (macs = questions x rows x size) work with these semantics, w2b_eval_set_kernel does nothing and
+ * On a bits handle w2b_eval_top1 / _topk / _neighbors / _combine / _nearest_text / _combine_text / _transcript /
+ * _set_topk_scratch / _timing_read (macs = questions x rows x size) work with these semantics, w2b_eval_set_kernel does nothing and
  * w2b_eval_get_matrix is W2B_EINVAL.
  * Two-bit models have the codes mode below: their rows differ in length, so the ranking needs a per-row float scale. */
 
@@ -129,6 +159,13 @@ int w2b_eval_get_bits(w2b_eval *e, uint64_t *out);
  * question (b1, b2, b3) for EVERY row c of packed[words][ceil(dim / 64)], b1, b2, b3 included, into I_out[words]. */
 int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
                          int32_t *I_out);
+
+/* Host twin of the bits form of w2b_eval_combine (pure C, no device): I(c) of the question rows[nt] / signs[nt] for EVERY
+ * row c of packed[words][ceil(dim / 64)], the question's own rows included, into I_out[words].  W2B_EINVAL as
+ * w2b_eval_combine has it: nt outside 1..W2B_EVAL_MAX_TERMS, a sign other than -1, 0, +1, a used slot's row outside
+ * [0, words), no used slot. */
+int w2b_bits_combine_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t nt, const int32_t *rows,
+                                 const int8_t *signs, int32_t *I_out);
 
 /* ---- codes mode: the integer scan on bit-packed 2-bit vectors ------------------------------------------------------
  * A 2-bit value is t/4 with t in {-1, +1, -3, +3}: the SIGN bit set means negative, the MAGNITUDE bit set means 3 (0.75),

@@ -56,6 +56,7 @@ class RowPlan(C.Structure):
 vp, i32p, i64p, f32p, f64p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), \
     C.POINTER(C.c_float), C.POINTER(C.c_double)
 u64p = C.POINTER(C.c_uint64)
+i8p = C.POINTER(C.c_int8)
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
 SIGNATURES = {
@@ -140,6 +141,8 @@ SIGNATURES = {
     "w2b_eval_top1": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, i32p, f32p]),
     "w2b_eval_topk": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, C.c_int32, i32p, f32p]),
     "w2b_eval_neighbors": (C.c_int, [vp, C.c_int64, i32p, C.c_int32, i32p, f32p]),
+    "w2b_eval_combine": (C.c_int, [vp, C.c_int64, C.c_int32, i32p, i8p, C.c_int32, i32p, f32p]),
+    "w2b_eval_combine_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp), i64p]),
     "w2b_eval_nearest_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp), i64p]),
     "w2b_eval_set_topk_scratch": (C.c_int, [vp, C.c_int64]),
     "w2b_eval_transcript": (C.c_int, [vp, C.c_char_p, C.c_int64, C.POINTER(vp), i64p]),
@@ -151,6 +154,7 @@ SIGNATURES = {
     "w2b_eval_is_bits": (C.c_int32, [vp]),
     "w2b_eval_get_bits": (C.c_int, [vp, u64p]),
     "w2b_bits_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p]),
+    "w2b_bits_combine_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, i32p, i8p, i32p]),
     "w2b_eval_load_codes": (C.c_int, [C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp)]),
     "w2b_eval_codes_from_trainer": (C.c_int, [vp, C.c_int64, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(vp)]),
     "w2b_eval_is_codes": (C.c_int32, [vp]),

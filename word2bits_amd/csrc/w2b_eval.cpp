@@ -1,7 +1,8 @@
 // w2b_eval.cpp -- host side of include/word2bits_eval.h: the vector-file reader, the question-stream state
 // machine and the stdout transcript of the reference evaluator (ref src/compute-accuracy.c:80-188), around the
 // GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
-// w2b_kernels_evalcodes.hip (bit-packed 2-bit rows).  No arithmetic on scores happens here and there is no CPU fallback
+// w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
+// adds to the first two.  No arithmetic on scores happens here and there is no CPU fallback
 // (w2b_codes_scores_host is the tests' twin of the codes kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
@@ -56,6 +57,10 @@ struct w2b_eval {
   // per-call scratch (grown on demand)
   float *Q = nullptr;
   int32_t *b123 = nullptr;
+  // w2b_eval_combine: the questions' rows and signs, each [cap_t][W2B_EVAL_XSTRIDE], and (bits) their four planes
+  int32_t *terms = nullptr;
+  uint32_t *P4 = nullptr;                               // [4 * 2 * wpr][cap_t]
+  int64_t cap_t = 0;
   unsigned long long *best = nullptr;
   int64_t cap_q = 0;
   double kernel_ms = 0;                                 // score-kernel time since the last timing_read
@@ -76,6 +81,8 @@ static void eval_release(w2b_eval *e) {
   if (e->P) (void)hipFree(e->P);
   if (e->Q) (void)hipFree(e->Q);
   if (e->b123) (void)hipFree(e->b123);
+  if (e->terms) (void)hipFree(e->terms);
+  if (e->P4) (void)hipFree(e->P4);
   if (e->best) (void)hipFree(e->best);
   if (e->tk_buf) (void)hipFree(e->tk_buf);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -478,6 +485,46 @@ extern "C" int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64
   return W2B_OK;
 }
 
+namespace {
+// what w2b_eval_combine and its host twin refuse in one question's slots (null: nothing)
+const char *bad_terms(int32_t nt, const int32_t *rows, const int8_t *signs, int64_t words) {
+  int used = 0;
+  for (int32_t t = 0; t < nt; t++) {
+    if (signs[t] < -1 || signs[t] > 1) return "a sign must be -1, 0 or +1";
+    if (signs[t] == 0) continue;
+    if (rows[t] < 0 || rows[t] >= words) return "question row out of range";
+    used++;
+  }
+  return used ? nullptr : "a question needs at least one slot with a sign";
+}
+}  // namespace
+
+// host twin of the bits form of w2b_eval_combine: I(c) = sum over the used slots of sign * (dim - 2 * Hamming(r, c))
+extern "C" int w2b_bits_combine_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t nt,
+                                            const int32_t *rows, const int8_t *signs, int32_t *I_out) {
+  const std::string who = "w2b_bits_combine_scores_host";
+  if (!packed || !rows || !signs || !I_out || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (nt < 1 || nt > W2B_EVAL_MAX_TERMS) return efail(W2B_EINVAL, who + ": the number of terms must be 1..7");
+  if (const char *why = bad_terms(nt, rows, signs, words)) return efail(W2B_EINVAL, who + ": " + why);
+  const int64_t wpr = (dim + 63) / 64;
+  for (int64_t c = 0; c < words; c++) {
+    const uint64_t *rc = packed + c * wpr;
+    int64_t I = 0;
+    for (int32_t t = 0; t < nt; t++) {
+      if (signs[t] == 0) continue;
+      const uint64_t *rt = packed + (int64_t)rows[t] * wpr;
+      int64_t h = 0;
+      for (int64_t w = 0; w < wpr; w++) {
+        const uint64_t valid = (w + 1) * 64 <= dim ? ~0ull : (1ull << (dim - w * 64)) - 1;    // padding bits do not count
+        h += __builtin_popcountll((rt[w] ^ rc[w]) & valid);
+      }
+      I += signs[t] * (dim - 2 * h);
+    }
+    I_out[c] = (int32_t)I;
+  }
+  return W2B_OK;
+}
+
 // Host twin of the codes kernels.  The float sequence of the header, one rounding per operation: this file is built with
 // -ffp-contract=off and the function's body repeats it, so that no build fuses p * w + p.
 extern "C" int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
@@ -570,6 +617,18 @@ static int eval_reserve_questions(w2b_eval *e, int64_t np) {
   return W2B_OK;
 }
 
+// the per-call buffers of `np` (padded) signed multi-word questions, next to those of eval_reserve_questions
+static int eval_reserve_terms(w2b_eval *e, int64_t np) {
+  if (np <= e->cap_t) return W2B_OK;
+  if (e->terms) (void)hipFree(e->terms);
+  if (e->P4) (void)hipFree(e->P4);
+  e->terms = nullptr; e->P4 = nullptr; e->cap_t = 0;
+  if (hipMalloc(&e->terms, (size_t)np * W2B_EVAL_XSTRIDE * 8) != hipSuccess) return W2B_ENOMEM;
+  if (e->bits && hipMalloc(&e->P4, (size_t)np * (size_t)e->wpr * 32) != hipSuccess) return W2B_ENOMEM;
+  e->cap_t = np;
+  return W2B_OK;
+}
+
 // the top-k scratch of one launch
 static int eval_reserve_topk(w2b_eval *e, size_t need) {
   if (need <= e->tk_bytes) return W2B_OK;
@@ -582,13 +641,41 @@ static int eval_reserve_topk(w2b_eval *e, size_t need) {
 }
 
 // ------------------------------------------------------------------------------------ the scan (ref :155-177)
-// Every query goes through eval_scan_chunks in chunks of questions.  What differs between the forms is a Scan* struct:
+// Every query goes through eval_scan_chunks in chunks of questions.  What a question is made of is an input struct
+// (Rows3: the three rows of the reference's question; Terms: the signed rows of w2b_eval_combine) whose upload(...) puts
+// a chunk on the device.  What differs between the forms of the scan is a Scan* struct:
 //   chunk, kk     questions per launch and keys per question, sized by the constructor
 //   scratch(n)    bytes of top-k scratch that a chunk of n questions needs
 //   before(...)   what is enqueued ahead of the timed window; leaves `keys` at the chunk's [n][kk] result keys
 //   timed(...)    the launches that the kernel time covers
 //   score(key)    the score in a key's high half
 namespace {
+struct Rows3 {   // b1, b2, b3 of every question; on the device d1, d2, d3 [np]
+  const int32_t *b1, *b2, *b3;
+  int32_t *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
+  int upload(w2b_eval *e, int64_t q0, int64_t n, int64_t np) {
+    d1 = e->b123, d2 = e->b123 + np, d3 = e->b123 + 2 * np;
+    EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    return W2B_OK;
+  }
+};
+
+// rows / signs [nq][W2B_EVAL_XSTRIDE] as the kernels read them: the used slots first, in slot order, then row -1 / sign 0
+struct Terms {
+  const int32_t *rows, *signs;
+  int32_t *drows = nullptr, *dsigns = nullptr;
+  int upload(w2b_eval *e, int64_t q0, int64_t n, int64_t np) {
+    if (eval_reserve_terms(e, np) != W2B_OK) return efail(W2B_ENOMEM, "w2b_eval_combine: device allocation failed");
+    drows = e->terms, dsigns = e->terms + np * W2B_EVAL_XSTRIDE;
+    const size_t bytes = (size_t)n * W2B_EVAL_XSTRIDE * 4;
+    EHIP(hipMemcpyAsync(drows, rows + q0 * W2B_EVAL_XSTRIDE, bytes, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(dsigns, signs + q0 * W2B_EVAL_XSTRIDE, bytes, hipMemcpyHostToDevice, e->stream));
+    return W2B_OK;
+  }
+};
+
 inline float f32_score(unsigned long long key) {
   const uint32_t bits = (uint32_t)(key >> 32);
   float x;
@@ -601,15 +688,15 @@ struct ScanTop1 {   // fp32 rows, the best row
   int64_t chunk = kChunkQ, kk = 1;
   const unsigned long long *keys = nullptr;
   size_t scratch(int64_t) const { return 0; }
-  int before(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+  int before(int64_t n, int64_t np, const Rows3 &d) {
     EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
     EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
-    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
+    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d.d1, d.d2, d.d3, e->Q, e->variant, e->stream));
     keys = e->best;
     return W2B_OK;
   }
-  hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
-    return w2b_launch_eval_scores(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3, e->best,
+  hipError_t timed(int64_t n, int64_t, const Rows3 &d) {
+    return w2b_launch_eval_scores(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d.d1, d.d2, d.d3, e->best,
                                   e->variant, e->stream);
   }
   float score(unsigned long long key) const { return f32_score(key); }
@@ -657,19 +744,37 @@ struct ScanTopK {
     chunk = t.chunk(e->tk_budget);
   }
   size_t scratch(int64_t n) const { return t.bytes(n); }
-  int before(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+  int clear(int64_t n, int64_t np) {   // Q and the selection state, zeroed
     const size_t zero_bytes = t.place(e->tk_buf, n);
     EHIP(hipMemsetAsync(e->Q, 0, (size_t)np * e->ld * 4, e->stream));
     EHIP(hipMemsetAsync(e->tk_buf, 0, zero_bytes, e->stream));
-    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d1, d2, d3, e->Q, e->variant, e->stream));
     keys = t.merged;
     return W2B_OK;
   }
-  hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
-    return w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d1, d2, d3, k, t.bound, t.bkt,
-                                t.slots, t.cnt, t.merged, e->variant, e->stream);
+  int before(int64_t n, int64_t np, const Rows3 &d) {
+    if (int rc = clear(n, np)) return rc;
+    EHIP(w2b_launch_eval_queries(e->M, e->ld, n, d.d1, d.d2, d.d3, e->Q, e->variant, e->stream));
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const Rows3 &d) {
+    return w2b_launch_eval_topk(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d.d1, d.d2, d.d3, k, t.bound,
+                                t.bkt, t.slots, t.cnt, t.merged, e->variant, e->stream);
   }
   float score(unsigned long long key) const { return f32_score(key); }
+};
+
+// fp32 rows, the signed multi-word question: its own query vector, then the list form of the same top-k scan
+struct ScanCombine : ScanTopK {
+  using ScanTopK::ScanTopK;
+  int before(int64_t n, int64_t np, const Terms &d) {
+    if (int rc = clear(n, np)) return rc;
+    EHIP(w2b_launch_combine_queries(e->M, e->ld, n, d.drows, d.dsigns, e->Q, e->stream));
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const Terms &d) {
+    return w2b_launch_eval_topk_list(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d.drows, k, t.bound,
+                                     t.bkt, t.slots, t.cnt, t.merged, e->variant, e->stream);
+  }
 };
 
 // The scan on 2-bit rows of include/word2bits_eval.h ("codes mode"); k = 0 is the top-1 form.  The keys are the fp32
@@ -687,7 +792,7 @@ struct ScanCodes {
     chunk = t.chunk(e->tk_budget);
   }
   size_t scratch(int64_t n) const { return k > 0 ? t.bytes(n) : 0; }
-  int before(int64_t n, int64_t np, const int32_t *, const int32_t *, const int32_t *) {
+  int before(int64_t n, int64_t np, const Rows3 &) {
     if (k == 0) {
       EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
       keys = e->best;
@@ -697,11 +802,11 @@ struct ScanCodes {
     }
     return W2B_OK;
   }
-  hipError_t timed(int64_t n, int64_t, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+  hipError_t timed(int64_t n, int64_t, const Rows3 &d) {
     const uint32_t *B32 = (const uint32_t *)e->B;
-    hipError_t le = w2b_launch_codes_operands(B32, (int)e->size, (int)n, e->wrow, d1, d2, d3, e->P, e->Q, e->stream);
+    hipError_t le = w2b_launch_codes_operands(B32, (int)e->size, (int)n, e->wrow, d.d1, d.d2, d.d3, e->P, e->Q, e->stream);
     if (le != hipSuccess) return le;
-    return w2b_launch_codes_scan(B32, (int)e->words, (int)e->size, e->wrow, e->P, e->Q, (int)n, d1, d2, d3, k,
+    return w2b_launch_codes_scan(B32, (int)e->words, (int)e->size, e->wrow, e->P, e->Q, (int)n, d.d1, d.d2, d.d3, k,
                                  k == 0 ? e->best : t.bound, t.bkt, t.slots, t.cnt, t.merged, e->stream);
   }
   float score(unsigned long long key) const { return f32_score(key); }
@@ -734,20 +839,29 @@ struct ScanBits {
     }
   }
   size_t scratch(int64_t n) const { return k > 0 ? (size_t)n * 8 * kk * (size_t)(splits + 1) : 0; }
-  int before(int64_t n, int64_t np, const int32_t *, const int32_t *, const int32_t *) {
+  template <class In>
+  int before(int64_t n, int64_t np, const In &) {
     if (k == 0) EHIP(hipMemsetAsync(e->best, 0, (size_t)np * 8, e->stream));
     merged = k == 0 ? e->best : (unsigned long long *)e->tk_buf;
     slots = k == 0 ? nullptr : merged + n * kk;
     keys = merged;
     return W2B_OK;
   }
-  hipError_t timed(int64_t n, int64_t np, const int32_t *d1, const int32_t *d2, const int32_t *d3) {
+  hipError_t timed(int64_t n, int64_t np, const Rows3 &d) {
     const uint32_t *B32 = (const uint32_t *)e->B;
-    hipError_t le = w2b_launch_bits_planes(B32, (int)(2 * e->wpr), (int)e->size, (int)n, np, d1, d2, d3, e->P, e->stream);
+    hipError_t le = w2b_launch_bits_planes(B32, (int)(2 * e->wpr), (int)e->size, (int)n, np, d.d1, d.d2, d.d3, e->P, e->stream);
     if (le != hipSuccess) return le;
-    return k == 0 ? w2b_launch_bits_top1(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, e->best, e->stream)
-                  : w2b_launch_bits_topk(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d1, d2, d3, k, splits, rpb, slots,
-                                         merged, e->stream);
+    return k == 0 ? w2b_launch_bits_top1(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d.d1, d.d2, d.d3, e->best, e->stream)
+                  : w2b_launch_bits_topk(B32, (int)e->words, (int)e->size, e->P, np, (int)n, d.d1, d.d2, d.d3, k, splits, rpb,
+                                         slots, merged, e->stream);
+  }
+  // the signed multi-word question (k >= 1): four planes per question, the bit-sliced scan, the same merge
+  hipError_t timed(int64_t n, int64_t np, const Terms &d) {
+    const uint32_t *B32 = (const uint32_t *)e->B;
+    hipError_t le = w2b_launch_combine_planes(B32, (int)(2 * e->wpr), (int)e->size, (int)n, np, d.drows, d.dsigns, e->P4, e->stream);
+    if (le != hipSuccess) return le;
+    return w2b_launch_combine_bits(B32, (int)e->words, (int)e->size, e->P4, np, (int)n, d.drows, k, splits, rpb, slots, merged,
+                                   e->stream);
   }
   float score(unsigned long long key) const { return (float)(int32_t)(key >> 32) / (float)e->size; }   // one correctly rounded division
 };
@@ -767,24 +881,20 @@ struct EventPair {   // the two ends of a timed window
 };
 }  // namespace
 
-template <class Scan>
-static int eval_scan_chunks(w2b_eval *e, Scan &&m, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
-                            int32_t *best, float *bestd, const std::string &who) {
+template <class Scan, class In>
+static int eval_scan_chunks(w2b_eval *e, Scan &&m, In in, int64_t nq, int32_t *best, float *bestd, const std::string &who) {
   std::vector<unsigned long long> keys;
   for (int64_t q0 = 0; q0 < nq; q0 += m.chunk) {
     const int64_t n = (nq - q0 < m.chunk) ? nq - q0 : m.chunk;
     const int64_t np = (n + kTile - 1) / kTile * kTile;
     if (eval_reserve_questions(e, np) != W2B_OK || eval_reserve_topk(e, m.scratch(n)) != W2B_OK)
       return efail(W2B_ENOMEM, who + ": device allocation failed");
-    int32_t *d1 = e->b123, *d2 = e->b123 + np, *d3 = e->b123 + 2 * np;
-    EHIP(hipMemcpyAsync(d1, b1 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemcpyAsync(d2, b2 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    EHIP(hipMemcpyAsync(d3, b3 + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    if (int rc = m.before(n, np, d1, d2, d3)) return rc;
+    if (int rc = in.upload(e, q0, n, np)) return rc;
+    if (int rc = m.before(n, np, in)) return rc;
     EventPair ev;
     EHIP(ev.create());
     EHIP(hipEventRecord(ev.t[0], e->stream));
-    hipError_t le = m.timed(n, np, d1, d2, d3);
+    hipError_t le = m.timed(n, np, in);
     if (le == hipSuccess) le = hipEventRecord(ev.t[1], e->stream);
     keys.assign((size_t)(n * m.kk), 0ull);   // (no rows: nothing is launched and every list is empty)
     if (le == hipSuccess && e->words > 0)
@@ -814,10 +924,36 @@ static int eval_scan(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *
     if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
       return efail(W2B_EINVAL, who + ": question row out of range");
   EHIP(hipSetDevice(e->device));
-  if (e->bits) return eval_scan_chunks(e, ScanBits(e, nq, k), nq, b1, b2, b3, best, bestd, who);
-  if (e->codes) return eval_scan_chunks(e, ScanCodes(e, k), nq, b1, b2, b3, best, bestd, who);
-  if (topk) return eval_scan_chunks(e, ScanTopK(e, k), nq, b1, b2, b3, best, bestd, who);
-  return eval_scan_chunks(e, ScanTop1{e}, nq, b1, b2, b3, best, bestd, who);
+  const Rows3 in{b1, b2, b3};
+  if (e->bits) return eval_scan_chunks(e, ScanBits(e, nq, k), in, nq, best, bestd, who);
+  if (e->codes) return eval_scan_chunks(e, ScanCodes(e, k), in, nq, best, bestd, who);
+  if (topk) return eval_scan_chunks(e, ScanTopK(e, k), in, nq, best, bestd, who);
+  return eval_scan_chunks(e, ScanTop1{e}, in, nq, best, bestd, who);
+}
+
+// The signed multi-word question: the checks, the slots of every question compacted (used slots first, in slot order),
+// then the list form of the top-k scan.
+extern "C" int w2b_eval_combine(w2b_eval *e, int64_t nq, int32_t nt, const int32_t *rows, const int8_t *signs, int32_t k,
+                                int32_t *best, float *bestd) {
+  const std::string who = "w2b_eval_combine";
+  if (!e || nq < 0 || (nq > 0 && (!rows || !signs || !best))) return efail(W2B_EINVAL, who + ": bad argument");
+  if (e->codes) return efail(W2B_EINVAL, who + ": not available in codes mode");
+  if (nt < 1 || nt > W2B_EVAL_MAX_TERMS) return efail(W2B_EINVAL, who + ": the number of terms must be 1..7");
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  std::vector<int32_t> xr((size_t)nq * W2B_EVAL_XSTRIDE, -1), xs((size_t)nq * W2B_EVAL_XSTRIDE, 0);
+  for (int64_t q = 0; q < nq; q++) {
+    if (const char *why = bad_terms(nt, rows + q * nt, signs + q * nt, e->words)) return efail(W2B_EINVAL, who + ": " + why);
+    size_t at = (size_t)q * W2B_EVAL_XSTRIDE;
+    for (int32_t t = 0; t < nt; t++)
+      if (signs[q * nt + t] != 0) {
+        xr[at] = rows[q * nt + t];
+        xs[at++] = signs[q * nt + t];
+      }
+  }
+  EHIP(hipSetDevice(e->device));
+  const Terms in{xr.data(), xs.data()};
+  if (e->bits) return eval_scan_chunks(e, ScanBits(e, nq, k), in, nq, best, bestd, who);
+  return eval_scan_chunks(e, ScanCombine(e, k), in, nq, best, bestd, who);
 }
 
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
@@ -986,31 +1122,67 @@ extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t l
 
 
 // ------------------------------------------------------------------------------------ nearest: the text form
+namespace {
+// one line of a query text: what was understood, or what to say instead
+struct QueryLine { std::string head; std::string error; int64_t q; };
+
+// the next line of queries[pos .. len) split on white space, every token upper-cased (ref :118); false at the end
+bool next_query_line(const char *queries, int64_t len, int64_t &pos, std::vector<std::string> &tok) {
+  if (pos >= len) return false;
+  int64_t end = pos;
+  while (end < len && queries[end] != '\n') end++;
+  tok.clear();
+  for (int64_t i = pos; i < end;) {
+    while (i < end && is_space((unsigned char)queries[i])) i++;
+    const int64_t s0 = i;
+    while (i < end && !is_space((unsigned char)queries[i])) i++;
+    if (i > s0) {
+      tok.emplace_back(queries + s0, (size_t)(i - s0));
+      upper_inplace(tok.back());
+    }
+  }
+  pos = end + 1;
+  return true;
+}
+
+std::string joined(const std::vector<std::string> &tok) {
+  std::string head;
+  for (size_t i = 0; i < tok.size(); i++) head += (i ? " " : "") + tok[i];
+  return head;
+}
+
+// the answer text: per line its head, then the error or the list of question `q` in best / bestd [..][k]
+std::string query_answers(const w2b_eval *e, const std::vector<QueryLine> &lines, int32_t k, const std::vector<int32_t> &best,
+                          const std::vector<float> &bestd) {
+  std::string txt;
+  for (const QueryLine &ln : lines) {
+    txt += ln.head;
+    if (!ln.error.empty()) {
+      txt += ": " + ln.error + "\n";
+      continue;
+    }
+    txt += ":\n";
+    for (int j = 0; j < k; j++) {
+      const int32_t c = best[(size_t)(ln.q * k + j)];
+      if (c < 0) break;
+      appendf(txt, "%d\t%s\t%.6f\n", j + 1, e->vocab.data() + (int64_t)c * kMaxW, (double)bestd[(size_t)(ln.q * k + j)]);
+    }
+  }
+  return txt;
+}
+}  // namespace
+
 extern "C" int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out,
                                      int64_t *out_len) {
   if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_nearest_text: bad argument");
   if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_nearest_text: k must be 1..64");
   *out = nullptr;
-  struct Line { std::string head; std::string error; int64_t q; };
-  std::vector<Line> lines;
+  std::vector<QueryLine> lines;
   std::vector<int32_t> b1s, b2s, b3s;
-  for (int64_t pos = 0; pos < len;) {
-    int64_t end = pos;
-    while (end < len && queries[end] != '\n') end++;
-    std::vector<std::string> tok;
-    for (int64_t i = pos; i < end;) {
-      while (i < end && is_space((unsigned char)queries[i])) i++;
-      const int64_t s0 = i;
-      while (i < end && !is_space((unsigned char)queries[i])) i++;
-      if (i > s0) {
-        tok.emplace_back(queries + s0, (size_t)(i - s0));
-        upper_inplace(tok.back());                                  // ref :118
-      }
-    }
-    pos = end + 1;
+  std::vector<std::string> tok;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
     if (tok.empty()) continue;
-    Line ln{std::string(), std::string(), -1};
-    for (size_t i = 0; i < tok.size(); i++) ln.head += (i ? " " : "") + tok[i];
+    QueryLine ln{joined(tok), std::string(), -1};
     if (tok.size() != 1 && tok.size() != 3) {
       ln.error = "expected 1 or 3 words";
     } else {
@@ -1035,21 +1207,50 @@ extern "C" int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t l
     const int rc = w2b_eval_topk(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), k, best.data(), bestd.data());
     if (rc != W2B_OK) return rc;
   }
-  std::string txt;
-  for (const Line &ln : lines) {
-    txt += ln.head;
-    if (!ln.error.empty()) {
-      txt += ": " + ln.error + "\n";
-      continue;
-    }
-    txt += ":\n";
-    for (int j = 0; j < k; j++) {
-      const int32_t c = best[(size_t)(ln.q * k + j)];
-      if (c < 0) break;
-      appendf(txt, "%d\t%s\t%.6f\n", j + 1, e->vocab.data() + (int64_t)c * kMaxW, (double)bestd[(size_t)(ln.q * k + j)]);
-    }
-  }
+  const std::string txt = query_answers(e, lines, k, best, bestd);
   return text_out(txt, "w2b_eval_nearest_text", out, out_len);
+}
+
+// the signed form: +WORD, -WORD or WORD, 1 to W2B_EVAL_MAX_TERMS of them per line
+extern "C" int w2b_eval_combine_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out,
+                                     int64_t *out_len) {
+  if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_combine_text: bad argument");
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_combine_text: k must be 1..64");
+  if (e->codes) return efail(W2B_EINVAL, "w2b_eval_combine_text: not available in codes mode");
+  *out = nullptr;
+  std::vector<QueryLine> lines;
+  std::vector<int32_t> rows;
+  std::vector<int8_t> signs;
+  std::vector<std::string> tok;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
+    if (tok.empty()) continue;
+    QueryLine ln{joined(tok), std::string(), -1};
+    int32_t r[W2B_EVAL_MAX_TERMS] = {0};
+    int8_t sg[W2B_EVAL_MAX_TERMS] = {0};
+    if (tok.size() > W2B_EVAL_MAX_TERMS) ln.error = "expected 1 to 7 signed words";
+    for (size_t i = 0; i < tok.size() && ln.error.empty(); i++) {
+      const bool has_sign = tok[i][0] == '+' || tok[i][0] == '-';
+      const std::string word = tok[i].substr(has_sign ? 1 : 0);
+      const int64_t row = w2b_eval_lookup(e, word.c_str());
+      if (row == e->words) ln.error = "not in vocabulary: " + word;
+      r[i] = (int32_t)row;
+      sg[i] = tok[i][0] == '-' ? -1 : 1;
+    }
+    if (ln.error.empty()) {
+      ln.q = (int64_t)(rows.size() / W2B_EVAL_MAX_TERMS);
+      rows.insert(rows.end(), r, r + W2B_EVAL_MAX_TERMS);
+      signs.insert(signs.end(), sg, sg + W2B_EVAL_MAX_TERMS);
+    }
+    lines.push_back(ln);
+  }
+  const size_t nq = rows.size() / W2B_EVAL_MAX_TERMS;
+  std::vector<int32_t> best(nq * (size_t)k);
+  std::vector<float> bestd(nq * (size_t)k);
+  if (nq > 0) {
+    const int rc = w2b_eval_combine(e, (int64_t)nq, W2B_EVAL_MAX_TERMS, rows.data(), signs.data(), k, best.data(), bestd.data());
+    if (rc != W2B_OK) return rc;
+  }
+  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_combine_text", out, out_len);
 }
 
 extern "C" void w2b_eval_free_text(char *text) { free(text); }

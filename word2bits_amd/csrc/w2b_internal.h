@@ -156,6 +156,26 @@ hipError_t w2b_launch_bits_topk(const uint32_t *B, int words, int dim, const uin
                                 const int *b1, const int *b2, const int *b3, int k, int splits, int rows_per_split,
                                 unsigned long long *slots /* [nq][splits][k] */, unsigned long long *out /* [nq][k] */,
                                 hipStream_t s);
+// the merge of the bits top-k form alone: out[q * k + j] = the j-th largest of the question's n = splits * k keys in `slots`
+hipError_t w2b_launch_bits_merge(const unsigned long long *slots, int n, int k, int nq, unsigned long long *out,
+                                 hipStream_t s);
+// The signed multi-word question (w2b_kernels_evalcombine.hip; include/word2bits_eval.h, w2b_eval_combine).  rows / signs =
+// [nq][W2B_EVAL_XSTRIDE]: the used slots first, in slot order (sign +1 / -1), then row -1 / sign 0; the rows are also the
+// question's exclusion list.  fp32: Q as w2b_launch_eval_queries leaves it, then the list form of the top-k scan.
+// bits: P = the questions' FOUR planes [4 * nw][nqp], then the scan into `slots` ([nq][splits][k]) and the merge into `out`;
+// splits and rows_per_split from w2b_bits_layout(topk = 1).
+#define W2B_EVAL_XSTRIDE 8          // ints per question: W2B_EVAL_MAX_TERMS = 7 slots and one that is always unused
+hipError_t w2b_launch_combine_queries(const float *M, long long ld, long long nq, const int *rows, const int *signs,
+                                      float *Q, hipStream_t s);
+hipError_t w2b_launch_eval_topk_list(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
+                                     const int *rows, int k, unsigned long long *bound, unsigned long long *bkt,
+                                     unsigned long long *keys, unsigned char *cnt, unsigned long long *out, int variant,
+                                     hipStream_t s);
+hipError_t w2b_launch_combine_planes(const uint32_t *B, int nw, int dim, int nq, long long nqp, const int *rows,
+                                     const int *signs, uint32_t *P, hipStream_t s);
+hipError_t w2b_launch_combine_bits(const uint32_t *B, int words, int dim, const uint32_t *P, long long nqp, int nq,
+                                   const int *rows, int k, int splits, int rows_per_split, unsigned long long *slots,
+                                   unsigned long long *out, hipStream_t s);
 // the merge of the top-k form alone: out[q * k + j] from the slots `keys` / `cnt` that a scan has filled
 hipError_t w2b_launch_eval_topk_merge(unsigned long long *keys, unsigned char *cnt, int nunits, int cap, int k, int nq,
                                       unsigned long long *out, hipStream_t s);

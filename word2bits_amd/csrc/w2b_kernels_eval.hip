@@ -25,6 +25,7 @@
 // = 78.6 T multiply-adds/s for fused arithmetic on either pipe (v_pk_fma_f32 or the f32 MFMA), half of that
 // (39.3 T/s) for the two-instruction unfused form.  XCD-aware launch order: each XCD owns a contiguous stripe
 // of row tiles (see k_eval_scores_mfma for the finer order).
+#include "../../include/word2bits_eval.h"
 #include "w2b_device.hpp"
 #include "w2b_eval_select.hpp"
 
@@ -98,7 +99,43 @@ __device__ __forceinline__ f32x2 mac2(float a, f32x2 b, f32x2 acc) {
 // only if its unit held k larger ones: k_eval_topk_merge finds the exact top k among the slots.
 // (TopkArgs, ld_key and topk_note_max: w2b_eval_select.hpp, shared with the scan on 2-bit rows.)
 
-template <bool FUSED, bool TOPK>
+// The rows that a question's answers leave out (ref :169-171).  NX = 3: e1, e2, e3 = b1[q], b2[q], b3[q], the reference's
+// question.  NX = W2B_EVAL_MAX_TERMS: the list form of w2b_eval_combine, b1[q * W2B_EVAL_XSTRIDE + i], i = 0 .. NX - 1, with -1
+// in the unused slots (b2 and b3 are not read): e1, e2, e3 are its first three and ExclRest the others.  NX is a template
+// parameter and ExclRest<3> is empty, so the three-row kernels are the code they were.
+template <int NX>
+__device__ __forceinline__ int excl_first(const int *b1, const int *b2, const int *b3, int q, int i) {
+  if constexpr (NX == 3) return (i == 0 ? b1 : i == 1 ? b2 : b3)[q];
+  else return b1[(long long)q * W2B_EVAL_XSTRIDE + i];
+}
+template <int NX>
+struct ExclRest {
+  int e[NX > 3 ? NX - 3 : 1];
+  __device__ __forceinline__ void load(const int *b1, int q, bool live) {
+    if constexpr (NX > 3) {
+#pragma unroll
+      for (int i = 3; i < NX; i++) e[i - 3] = live ? b1[(long long)q * W2B_EVAL_XSTRIDE + i] : -1;
+    }
+  }
+  __device__ __forceinline__ bool miss(int c) const {                    // c is none of them
+    bool m = true;
+    if constexpr (NX > 3) {
+#pragma unroll
+      for (int i = 3; i < NX; i++) m = m && c != e[i - 3];
+    }
+    return m;
+  }
+  __device__ __forceinline__ bool within(int r0, unsigned n) const {     // one of them is among the rows r0 .. r0 + n - 1
+    bool h = false;
+    if constexpr (NX > 3) {
+#pragma unroll
+      for (int i = 3; i < NX; i++) h = h || (unsigned)(e[i - 3] - r0) < n;
+    }
+    return h;
+  }
+};
+
+template <bool FUSED, bool TOPK, int NX = 3>
 __device__ __forceinline__ void
 eval_scores_body(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int q_tiles,
                  int c_tiles, int c_per_xcd, const int *__restrict__ b1, const int *__restrict__ b2,
@@ -172,7 +209,9 @@ eval_scores_body(const float *__restrict__ Q, const float *__restrict__ M, int n
       const int ml = (i < 4) ? ty * 4 + i : 64 + ty * 4 + (i - 4);
       const int q = m0 + ml;
       if (q >= nq) continue;
-      const int e1 = b1[q], e2 = b2[q], e3 = b3[q];
+      const int e1 = excl_first<NX>(b1, b2, b3, q, 0), e2 = excl_first<NX>(b1, b2, b3, q, 1), e3 = excl_first<NX>(b1, b2, b3, q, 2);
+      ExclRest<NX> ex;
+      ex.load(b1, q, true);
       const unsigned long long bnd = ld_key(&best[q]);
       unsigned long long ks[8];
       int n = 0;
@@ -184,7 +223,7 @@ eval_scores_body(const float *__restrict__ Q, const float *__restrict__ M, int n
           const float d = acc[i][j][h];
           const unsigned long long k2 =
               ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
-          const bool ok = c < words && c != e1 && c != e2 && c != e3 && d > 0.f && k2 > bnd;
+          const bool ok = c < words && c != e1 && c != e2 && c != e3 && ex.miss(c) && d > 0.f && k2 > bnd;
           ks[j * 2 + h] = ok ? k2 : 0ull;
           n += ok ? 1 : 0;
         }
@@ -213,7 +252,9 @@ eval_scores_body(const float *__restrict__ Q, const float *__restrict__ M, int n
     const int ml = (i < 4) ? ty * 4 + i : 64 + ty * 4 + (i - 4);
     const int q = m0 + ml;
     if (q >= nq) continue;
-    const int e1 = b1[q], e2 = b2[q], e3 = b3[q];
+    const int e1 = excl_first<NX>(b1, b2, b3, q, 0), e2 = excl_first<NX>(b1, b2, b3, q, 1), e3 = excl_first<NX>(b1, b2, b3, q, 2);
+    ExclRest<NX> ex;
+    ex.load(b1, q, true);
     unsigned long long key = 0ull;
 #pragma unroll
     for (int j = 0; j < 4; j++)
@@ -221,7 +262,7 @@ eval_scores_body(const float *__restrict__ Q, const float *__restrict__ M, int n
       for (int h = 0; h < 2; h++) {
         const int c = n0 + ((j < 2) ? tx * 4 + j * 2 + h : 64 + tx * 4 + (j - 2) * 2 + h);
         const float d = acc[i][j][h];
-        if (c < words && c != e1 && c != e2 && c != e3 && d > 0.f) {   // NaN fails d > 0 like `dist > bestd`
+        if (c < words && c != e1 && c != e2 && c != e3 && ex.miss(c) && d > 0.f) {   // NaN fails d > 0 like `dist > bestd`
           const unsigned long long k2 =
               ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
           key = k2 > key ? k2 : key;
@@ -241,12 +282,12 @@ k_eval_scores(const float *__restrict__ Q, const float *__restrict__ M, int nq, 
   eval_scores_body<FUSED, false>(Q, M, nq, words, ld, q_tiles, c_tiles, c_per_xcd, b1, b2, b3, best, TopkArgs{});
 }
 
-template <bool FUSED>
+template <bool FUSED, int NX = 3>
 __global__ void __launch_bounds__(ETHREADS, 2)
 k_eval_topk(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int q_tiles,
             int c_tiles, int c_per_xcd, const int *__restrict__ b1, const int *__restrict__ b2,
             const int *__restrict__ b3, unsigned long long *__restrict__ bound, const TopkArgs tk) {
-  eval_scores_body<FUSED, true>(Q, M, nq, words, ld, q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
+  eval_scores_body<FUSED, true, NX>(Q, M, nq, words, ld, q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
 }
 
 // ------------------------------------------------------------------------------------ fused mode on the matrix cores
@@ -285,7 +326,7 @@ typedef __attribute__((address_space(3))) volatile float lds_vf;
 //     two other workgroups instead of one.  At most 8 reads per burst: the LDS wait counter has four bits.
 // Measured and rejected: persistent workgroups that walk their tiles as one slab stream
 // (with or without the arg-max of tile t riding between the MFMAs of tile t+1): 5-10 % slower than this.
-template <bool TOPK>
+template <bool TOPK, int NX = 3>
 __device__ __forceinline__ void
 eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int nh,
                       int q_tiles, int c_tiles, int c_per_xcd, int q_group, const int *__restrict__ b1,
@@ -314,15 +355,17 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
   if (tid < EBN) skey[tid] = 0ull;
 
   // what the epilogue needs from memory, requested now: the question words of this lane's two questions (excluded
-  // from the arg-max, ref :169-171) and the best key each question has so far (possibly stale: then it is only lower)
+  // from the arg-max, ref :169-171) and the best key each question has so far (possibly stale: then it is only lower).
+  // (The list form fetches its rows where the epilogue needs them: seven per question would not stay in registers
+  // through the main loop at three workgroups per CU.)
   int qw[2][3];
   unsigned long long seen[2];
 #pragma unroll
   for (int nt = 0; nt < 2; nt++) {
     const int q = n0 + wn + nt * 32 + l32;
-    qw[nt][0] = q < nq ? b1[q] : -1;
-    qw[nt][1] = q < nq ? b2[q] : -1;
-    qw[nt][2] = q < nq ? b3[q] : -1;
+    qw[nt][0] = NX == 3 && q < nq ? excl_first<NX>(b1, b2, b3, q, 0) : -1;
+    qw[nt][1] = NX == 3 && q < nq ? excl_first<NX>(b1, b2, b3, q, 1) : -1;
+    qw[nt][2] = NX == 3 && q < nq ? excl_first<NX>(b1, b2, b3, q, 2) : -1;
     seen[nt] = q < nq ? __hip_atomic_load(&best[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
   }
 
@@ -479,7 +522,7 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
     for (int nt = 0; nt < 2; nt++) {
       const int q = n0 + wn + nt * 32 + l32;
       const bool live = q < nq;
-      const int e1 = qw[nt][0], e2 = qw[nt][1], e3 = qw[nt][2];
+      int e1 = qw[nt][0], e2 = qw[nt][1], e3 = qw[nt][2];
       const unsigned long long bnd = seen[nt];
       float m = acc[0][nt][0];
 #pragma unroll
@@ -489,6 +532,10 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
       for (int e = 0; e < 16; e += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, acc[1][nt][e]), acc[1][nt][e + 1]);
       const bool may = live && m > 0.f && __float_as_uint(m) >= (unsigned)(bnd >> 32);          // (NaN: m > 0 fails)
       if (!__any(may)) continue;
+      ExclRest<NX> ex;
+      ex.load(b1, q, live);
+      if constexpr (NX != 3)
+        if (live) e1 = excl_first<NX>(b1, b2, b3, q, 0), e2 = excl_first<NX>(b1, b2, b3, q, 1), e3 = excl_first<NX>(b1, b2, b3, q, 2);
       unsigned cm = 0u;
 #pragma unroll
       for (int mt = 0; mt < 2; mt++)
@@ -498,7 +545,7 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
           const float d = acc[mt][nt][e];
           const unsigned long long k2 =
               ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(lo0 - (unsigned)off);
-          const bool ok = may && c < words && c != e1 && c != e2 && c != e3 && d > 0.f && k2 > bnd;
+          const bool ok = may && c < words && c != e1 && c != e2 && c != e3 && ex.miss(c) && d > 0.f && k2 > bnd;
           cm |= ok ? 1u << (mt * 16 + e) : 0u;
         }
       if (!__any(cm != 0u)) continue;
@@ -547,7 +594,7 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
   for (int nt = 0; nt < 2; nt++) {
     const int nl = wn + nt * 32 + l32, q = n0 + nl;
     const bool live = q < nq;
-    const int e1 = qw[nt][0], e2 = qw[nt][1], e3 = qw[nt][2];
+    int e1 = qw[nt][0], e2 = qw[nt][1], e3 = qw[nt][2];
     // can any of this wavefront's 64 x 32 scores still improve its question's key?  A key orders by (score, lower
     // row): a score below the one already recorded never does; an equal one only with a lower row (another XCD's
     // stripe may have recorded a higher row first), so "greater or equal" goes on to the exact comparison.
@@ -559,9 +606,13 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
     for (int e = 0; e < 16; e += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, acc[1][nt][e]), acc[1][nt][e + 1]);
     const bool may = live && m > 0.f && __float_as_uint(m) >= (unsigned)(seen[nt] >> 32);     // (NaN: m > 0 fails)
     if (!__any(may)) continue;
+    ExclRest<NX> ex;
+    ex.load(b1, q, live);
+    if constexpr (NX != 3)
+      if (live) e1 = excl_first<NX>(b1, b2, b3, q, 0), e2 = excl_first<NX>(b1, b2, b3, q, 1), e3 = excl_first<NX>(b1, b2, b3, q, 2);
     // no question word of these 32 questions among this wavefront's 64 rows and no row past the vocabulary (the
     // usual case): a float compare and two selects per accumulator
-    const bool excl = (unsigned)(e1 - r0) < 64u || (unsigned)(e2 - r0) < 64u || (unsigned)(e3 - r0) < 64u;
+    const bool excl = (unsigned)(e1 - r0) < 64u || (unsigned)(e2 - r0) < 64u || (unsigned)(e3 - r0) < 64u || ex.within(r0, 64u);
     unsigned long long key = 0ull;
     if (r0 + 64 <= words && !__any(excl)) {
       float bd = 0.f;
@@ -585,7 +636,7 @@ eval_scores_mfma_body(const float *__restrict__ Q, const float *__restrict__ M, 
         for (int e = 0; e < 16; e++) {
           const int c = r0 + mt * 32 + 8 * (e >> 2) + 4 * lk2 + (e & 3);
           const float d = acc[mt][nt][e];
-          if (live && c < words && c != e1 && c != e2 && c != e3 && d > 0.f) {
+          if (live && c < words && c != e1 && c != e2 && c != e3 && ex.miss(c) && d > 0.f) {
             const unsigned long long k2 =
                 ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
             key = k2 > key ? k2 : key;
@@ -608,12 +659,13 @@ k_eval_scores_mfma(const float *__restrict__ Q, const float *__restrict__ M, int
                                TopkArgs{});
 }
 
+template <int NX = 3>
 __global__ void __launch_bounds__(ETHREADS, 3)
 k_eval_topk_mfma(const float *__restrict__ Q, const float *__restrict__ M, int nq, int words, int ld, int nh,
                  int q_tiles, int c_tiles, int c_per_xcd, int q_group, const int *__restrict__ b1,
                  const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ bound,
                  const TopkArgs tk) {
-  eval_scores_mfma_body<true>(Q, M, nq, words, ld, nh, q_tiles, c_tiles, c_per_xcd, q_group, b1, b2, b3, bound, tk);
+  eval_scores_mfma_body<true, NX>(Q, M, nq, words, ld, nh, q_tiles, c_tiles, c_per_xcd, q_group, b1, b2, b3, bound, tk);
 }
 
 // One workgroup per question: the k largest keys among its slots, in descending order (= the reference's order).
@@ -710,10 +762,12 @@ void w2b_eval_topk_layout(long long words, int k, bool mfma, int *nunits, int *c
   *cap = k < rows ? k : rows;
 }
 
-hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
-                                const int *b1, const int *b2, const int *b3, int k, unsigned long long *bound,
-                                unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
-                                unsigned long long *out, int variant, hipStream_t s) {
+// NX = 3: the rows b1, b2, b3 of a question; NX = W2B_EVAL_MAX_TERMS: its list at b1 (excl_first, ExclRest)
+template <int NX>
+static hipError_t launch_eval_topk(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
+                                   const int *b1, const int *b2, const int *b3, int k, unsigned long long *bound,
+                                   unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
+                                   unsigned long long *out, int variant, hipStream_t s) {
   if (nq <= 0 || words <= 0) return hipSuccess;
   const int q_tiles = (nq + EBM - 1) / EBM, c_tiles = (words + EBN - 1) / EBN;
   const int c_per_xcd = (c_tiles + 7) / 8;
@@ -729,17 +783,32 @@ hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int word
     int g = variant > 1 ? variant : 8;
     if (g > q_tiles) g = q_tiles;
     const long long grid2 = 8ll * c_per_xcd * ((q_tiles + g - 1) / g * g);
-    hipLaunchKernelGGL(k_eval_topk_mfma, dim3((unsigned)grid2), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
+    hipLaunchKernelGGL((k_eval_topk_mfma<NX>), dim3((unsigned)grid2), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
                        (size + 7) / 8, q_tiles, c_tiles, c_per_xcd, g, b1, b2, b3, bound, tk);
   }
   else if (fused)
-    hipLaunchKernelGGL((k_eval_topk<true>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
+    hipLaunchKernelGGL((k_eval_topk<true, NX>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
                        q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
   else
-    hipLaunchKernelGGL((k_eval_topk<false>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
+    hipLaunchKernelGGL((k_eval_topk<false, NX>), dim3((unsigned)grid), dim3(ETHREADS), 0, s, Q, M, nq, words, ld,
                        q_tiles, c_tiles, c_per_xcd, b1, b2, b3, bound, tk);
   hipLaunchKernelGGL(k_eval_topk_merge, dim3((unsigned)nq), dim3(256), 0, s, tk, out);
   return hipGetLastError();
+}
+
+hipError_t w2b_launch_eval_topk(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
+                                const int *b1, const int *b2, const int *b3, int k, unsigned long long *bound,
+                                unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
+                                unsigned long long *out, int variant, hipStream_t s) {
+  return launch_eval_topk<3>(Q, M, nq, words, size, ld, fused, b1, b2, b3, k, bound, bkt, keys, cnt, out, variant, s);
+}
+
+hipError_t w2b_launch_eval_topk_list(const float *Q, const float *M, int nq, int words, int size, int ld, int fused,
+                                     const int *rows, int k, unsigned long long *bound, unsigned long long *bkt,
+                                     unsigned long long *keys, unsigned char *cnt, unsigned long long *out, int variant,
+                                     hipStream_t s) {
+  return launch_eval_topk<W2B_EVAL_MAX_TERMS>(Q, M, nq, words, size, ld, fused, rows, nullptr, nullptr, k, bound, bkt, keys,
+                                              cnt, out, variant, s);
 }
 
 // the merge alone, for a scan that fills the slots itself (w2b_kernels_evalcodes.hip)

@@ -16,14 +16,10 @@
 // the k best (top-k, in LDS).  gridDim.y splits the rows so that the device is full; the partial results meet in a
 // 64-bit atomic max (top-1) or in k_bits_merge (top-k).  Rows are visited in ascending order and a later row has to be
 // strictly better, so equal scores resolve to the lowest row exactly as the answer list demands.
-#include "w2b_internal.h"
-
-#include <type_traits>
+// (BT1, BTK, bits_key and dispatch_nw: w2b_eval_bits.hpp, shared with the scan of signed sums.)
+#include "w2b_eval_bits.hpp"
 
 namespace {
-
-constexpr int BT1 = 256;   // lanes (questions) per workgroup, top-1
-constexpr int BTK = 128;   // ... top-k: k * BTK keys of 8 bytes in LDS, 64 KiB at k = 64
 
 // planes of `nq` questions, P[w][nqp] = sg and P[nw + w][nqp] = m3 for the 32-bit half w (question-minor: a wave's loads coalesce)
 __global__ void k_bits_planes(const uint32_t *__restrict__ B, int nw, int dim, int nq, long long nqp,
@@ -86,10 +82,6 @@ struct Planes {
     return a1 + 2 * a3;
   }
 };
-
-__device__ __forceinline__ unsigned long long bits_key(uint32_t c, uint32_t acc, int row) {
-  return ((unsigned long long)(c - 2 * acc) << 32) | (uint32_t)~row;      // I > 0: orders like the fp32 path's key
-}
 
 template <int NW>
 __global__ void __launch_bounds__(BT1)
@@ -188,17 +180,7 @@ k_bits_merge(const unsigned long long *__restrict__ slots, int n, int k, unsigne
   }
 }
 
-// the kernel instance for a row of `nw` 32-bit halves: registers up to 32 halves (1024 columns), memory beyond
-template <typename F>
-hipError_t dispatch_nw(int nw, F &&f) {
-  switch (nw) {
-#define W2B_NW(n) case n: return f(std::integral_constant<int, n>());
-    W2B_NW(2) W2B_NW(4) W2B_NW(6) W2B_NW(8) W2B_NW(10) W2B_NW(12) W2B_NW(14) W2B_NW(16)
-    W2B_NW(18) W2B_NW(20) W2B_NW(22) W2B_NW(24) W2B_NW(26) W2B_NW(28) W2B_NW(30) W2B_NW(32)
-#undef W2B_NW
-    default: return f(std::integral_constant<int, 0>());
-  }
-}
+constexpr int kMaxNW = 32;   // planes in registers up to 32 halves (1024 columns), in memory beyond
 
 }  // namespace
 
@@ -232,11 +214,18 @@ hipError_t w2b_launch_bits_top1(const uint32_t *B, int words, int dim, const uin
   int splits = 1, rpb = 1;
   w2b_bits_layout(words, nq, 0, 0, &splits, &rpb);
   const dim3 grid((unsigned)((nq + BT1 - 1) / BT1), (unsigned)splits);
-  return dispatch_nw(nw, [&](auto n) {
+  return dispatch_nw<kMaxNW>(nw, [&](auto n) {
     constexpr int NW = decltype(n)::value;
     hipLaunchKernelGGL((k_bits_top1<NW>), grid, dim3(BT1), 0, s, B, words, nw, dim, P, nqp, nq, b1, b2, b3, rpb, best);
     return hipGetLastError();
   });
+}
+
+hipError_t w2b_launch_bits_merge(const unsigned long long *slots, int n, int k, int nq, unsigned long long *out,
+                                 hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_bits_merge, dim3((unsigned)nq), dim3(64), 0, s, slots, n, k, out);
+  return hipGetLastError();
 }
 
 hipError_t w2b_launch_bits_topk(const uint32_t *B, int words, int dim, const uint32_t *P, long long nqp, int nq,
@@ -246,13 +235,12 @@ hipError_t w2b_launch_bits_topk(const uint32_t *B, int words, int dim, const uin
   const int nw = (dim + 63) / 64 * 2;
   const dim3 grid((unsigned)((nq + BTK - 1) / BTK), (unsigned)splits);
   const size_t lds = (size_t)k * BTK * sizeof(unsigned long long);
-  hipError_t e = dispatch_nw(nw, [&](auto n) {
+  hipError_t e = dispatch_nw<kMaxNW>(nw, [&](auto n) {
     constexpr int NW = decltype(n)::value;
     hipLaunchKernelGGL((k_bits_topk<NW>), grid, dim3(BTK), lds, s, B, words, nw, dim, P, nqp, nq, b1, b2, b3,
                        rows_per_split, k, slots);
     return hipGetLastError();
   });
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_bits_merge, dim3((unsigned)nq), dim3(64), 0, s, slots, splits * k, k, out);
-  return hipGetLastError();
+  return w2b_launch_bits_merge(slots, splits * k, k, nq, out, s);
 }

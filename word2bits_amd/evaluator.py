@@ -131,6 +131,37 @@ class Evaluator:
         """The k nearest rows of each row in `rows` (the row itself excluded): topk(rows, rows, rows, k)."""
         return self._scan(self._L.w2b_eval_neighbors, (rows,), int(k))
 
+    def combine(self, rows, signs, k):
+        """The signed multi-word question (w2b_eval_combine): `rows` and `signs` are int arrays [nq, nt], nt <= 7, a sign
+        is +1, -1 or 0 (slot unused, its row ignored).  Returns (rows int32 [nq, k], scores float32 [nq, k]) in the order
+        of topk; every used row is excluded from its question's answers.  fp32 and bits handles."""
+        rows, signs = np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(signs, np.int8)
+        if rows.ndim != 2 or rows.shape != signs.shape:
+            raise ValueError("rows and signs must both be [nq, nt]")
+        nq, nt = rows.shape
+        k = int(k)
+        best, bestd = np.empty((nq, max(k, 0)), np.int32), np.empty((nq, max(k, 0)), np.float32)
+        _lib.check(self._L.w2b_eval_combine(self._h, nq, nt, rows.ctypes.data_as(_lib.i32p), signs.ctypes.data_as(_lib.i8p),
+                                            k, best.ctypes.data_as(_lib.i32p), bestd.ctypes.data_as(_lib.f32p)))
+        return best, bestd
+
+    def most_similar(self, positive, negative, k):
+        """gensim's most_similar for a batch: `positive` and `negative` are lists of row lists, one per question (either may
+        be empty for a question, not both).  A question's slots are its positives, then its negatives, padded with sign 0."""
+        if len(positive) != len(negative):
+            raise ValueError("one list of positive and one of negative rows per question")
+        nt = max([len(p) + len(n) for p, n in zip(positive, negative)] + [1])
+        rows, signs = np.zeros((len(positive), nt), np.int32), np.zeros((len(positive), nt), np.int8)
+        for q, (p, n) in enumerate(zip(positive, negative)):
+            rows[q, :len(p) + len(n)] = list(p) + list(n)
+            signs[q, :len(p)] = 1
+            signs[q, len(p):len(p) + len(n)] = -1
+        return self.combine(rows, signs, k)
+
+    def combine_text(self, queries, k):
+        """stdout of `nearest FILE k ... signed < queries` as bytes: every line is 1 to 7 tokens +WORD, -WORD or WORD."""
+        return self._text(self._L.w2b_eval_combine_text, queries, int(k))
+
     def nearest_text(self, queries, k):
         """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
         return self._text(self._L.w2b_eval_nearest_text, queries, int(k))
