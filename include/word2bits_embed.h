@@ -1,0 +1,106 @@
+/*
+ * word2bits_embed.h -- C ABI of the packed embedding layer: row lookup and bag pooling on the MI355X, straight from the
+ * bit-packed table of a 1-bit or 2-bit model (the .w2bp layout of include/word2bits_corpus.h).
+ *
+ * The consumer of a packed model that is not the evaluator: a downstream model asks for the rows of a batch of token ids,
+ * or for their sum / mean per sentence ("bag").  The rows stay packed on the device, [rows][w2b_packed_words_per_row(dim,
+ * bitlevel)] 64-bit words, 1/32 (1/16) of the float table; no float table is ever built, on either side.  The kernels are in
+ * word2bits_amd/csrc/w2b_kernels_embed.hip, the host side in w2b_embed.cpp.
+ *
+ * No CPU fallback: W2B_ENOGPU when no device is visible (the *_host functions below are the tests' twins of the kernels,
+ * as w2b_bits_scores_host is for the bits kernels).  Error codes and w2b_last_error() are those of word2bits_hip.h.
+ *
+ * ---- semantics -----------------------------------------------------------------------------------------------------
+ * Table.  `packed` is [rows][w2b_packed_words_per_row(dim, bitlevel)]: per 64 columns one word of SIGN bits (set =
+ *   negative) and, at bitlevel 2, one word of MAGNITUDE bits (set = 0.75, clear = 0.25).  bitlevel is 1 or 2, anything
+ *   else is W2B_EUNSUPPORTED.  1 <= rows <= 0x7FFFFF00, 1 <= dim <= 2^24, else W2B_EINVAL.
+ * Lookup.  out[i][0 .. dim) is row ids[i] exactly as w2b_unpack_quantized delivers it: the float32 patterns +-0x3EAAAAAB
+ *   (1/3) at bitlevel 1 and +-0.25, +-0.75 at bitlevel 2.  An id < 0 is padding: its output row is +0.0 throughout.
+ *   The kernel assembles every value from the bits with integer operations -- there is no float arithmetic on this path,
+ *   so the patterns are exact by construction.  Output rows are dense, [n][dim], without padding.
+ * Bag.  offsets is [n_bags + 1], non-decreasing, offsets[0] == 0, offsets[n_bags] == n_ids; bag b is
+ *   ids[offsets[b] .. offsets[b + 1]).  Per column a, the integer T[a] = sum of t_r[a] over the bag's ids r >= 0, where
+ *   t = +-1 at bitlevel 1 and t in {+-1, +-3} at bitlevel 2 (the codes of word2bits_eval.h: value = t / 4).  Padding ids
+ *   contribute nothing.  Then, in float32, every operation rounded to nearest on its own:
+ *       sum  = (float)T[a] * q       q = 0x3EAAAAAB at bitlevel 1, 0.25f at bitlevel 2: ONE multiply, rounded once
+ *       mean = sum / (float)m        m = the number of ids >= 0 in the bag: ONE correctly rounded division
+ *   A bag with m == 0 is +0.0.  A bag longer than W2B_EMBED_MAX_BAG ids is W2B_EINVAL: with at most 2^22 ids,
+ *   |T| <= 3 * 2^22 < 2^24, so the conversion (float)T is exact, and so is (float)m.  Integer adds commute: the result
+ *   does not depend on how the kernels split a bag.
+ * Output dtypes.  W2B_EMBED_BF16 and W2B_EMBED_F16 are the float32 result above rounded to nearest even (16-bit
+ *   patterns).  .25 and .75 are exact in both; 1/3 becomes 0x3EAB in bf16 and 0x3555 in f16.
+ *
+ * ---- out of scope --------------------------------------------------------------------------------------------------
+ * Gradients or training through the lookup (the table is read-only); bitlevels other than 1 and 2; a handle built from
+ * a live trainer (w2b_export_packed + w2b_embed_create does it in two calls); float input files.
+ */
+#ifndef WORD2BITS_EMBED_H
+#define WORD2BITS_EMBED_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct w2b_embed w2b_embed;
+#define W2B_EMBED_F32 0
+#define W2B_EMBED_BF16 1
+#define W2B_EMBED_F16 2
+#define W2B_EMBED_SUM 0
+#define W2B_EMBED_MEAN 1
+#define W2B_EMBED_MAX_BAG (1 << 22)
+
+/* A bit-packed .w2bp, read without expanding it; `threshold` caps the rows as in w2b_eval_load_bits (0 = off).  What is
+ * wrong with the file is reported before a device is asked for: W2B_EIO "Input file not found" when it cannot be opened,
+ * W2B_EINVAL when it is not a W2BP1 file (the reference's float format is not read here), W2B_EIO when it is damaged. */
+int w2b_embed_load(const char *w2bp_file, int64_t threshold, int32_t device, w2b_embed **out);
+/* The same from packed rows in host memory (w2b_export_packed, w2b_pack_quantized); such a handle has no words. */
+int w2b_embed_create(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int32_t device, w2b_embed **out);
+void w2b_embed_free(w2b_embed *e);
+int64_t w2b_embed_rows(const w2b_embed *e);
+int64_t w2b_embed_dim(const w2b_embed *e);
+int32_t w2b_embed_bitlevel(const w2b_embed *e);
+const char *w2b_embed_word(const w2b_embed *e, int64_t row);      /* NULL on a handle made by _create */
+int64_t w2b_embed_search(const w2b_embed *e, const char *word);   /* exact bytes, first match; -1 if absent */
+
+/* Host in, host out: validated before anything is launched.  W2B_EINVAL, with the cause in w2b_last_error(), when an id
+ * is >= rows, offsets is not as stated above, a bag is longer than W2B_EMBED_MAX_BAG, dtype or mode is not one of the
+ * constants, n or a count is negative; then nothing is launched and `out` is untouched.  n == 0 (n_bags == 0) is W2B_OK.
+ * out is [n][dim] ([n_bags][dim]) of float (F32) or uint16_t patterns (BF16, F16).  Large calls run in chunks, so the
+ * device staging of the host form stays bounded (64 MiB of output, 2^22 ids or one bag); it is separate from the
+ * buffers of w2b_embed_reserve. */
+int w2b_embed_lookup(w2b_embed *e, int64_t n, const int32_t *ids, int32_t dtype, void *out);
+int w2b_embed_bag(w2b_embed *e, int64_t n_ids, const int32_t *ids, int64_t n_bags, const int64_t *offsets,
+                  int32_t mode, int32_t dtype, void *out);
+
+/* Device form: operands in library-owned device buffers, asynchronous on the handle's stream.
+ * w2b_embed_reserve hands the buffers out: ids_dev = int64[max_ids] (torch's index type), offsets_dev =
+ * int64[max_bags + 1], out_dev = [max(max_ids, max_bags)][dim] of `dtype`.  A later call may grow them; earlier pointers
+ * are then stale (a call that asks for no more than is there returns the same pointers).  The caller fills ids_dev /
+ * offsets_dev (and makes sure its own stream has finished doing so: the handle's stream waits for nobody), launches, and
+ * reads out_dev after w2b_embed_synchronize.  W2B_EINVAL when n, n_ids, n_bags or dtype exceed what was reserved.
+ * No content of the staging buffers makes a kernel read or write outside its buffers:
+ *   an id >= rows gives a zero row (lookup) or contributes nothing, m included (bag), and is counted;
+ *   bag bounds are clamped into [0, n_ids] with start <= end; a clamped bag, or one longer than W2B_EMBED_MAX_BAG, is
+ *   pooled over its first W2B_EMBED_MAX_BAG ids and counted once.
+ * w2b_embed_bad_ids synchronises, returns that device counter and resets it. */
+int w2b_embed_reserve(w2b_embed *e, int64_t max_ids, int64_t max_bags, int32_t dtype,
+                      void **ids_dev, void **offsets_dev, void **out_dev);
+int w2b_embed_lookup_device(w2b_embed *e, int64_t n, int32_t dtype);
+int w2b_embed_bag_device(w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype);
+int w2b_embed_synchronize(w2b_embed *e);
+int w2b_embed_bad_ids(w2b_embed *e, int64_t *count);             /* syncs, returns and resets */
+/* Device time (HIP events on the handle's stream) and number of lookup / bag calls launched (host-form chunks count one
+ * each) since creation or the last call; synchronises.  bytes = the packed words those launches read (ids x words per row
+ * x 8, padding ids included) plus the output bytes they wrote. */
+int w2b_embed_timing_read(w2b_embed *e, double *kernel_ms, int64_t *launches, double *bytes);
+
+/* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form. */
+int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
+                          int64_t n, const int32_t *ids, float *out);
+int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                       const int32_t *ids, int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -338,6 +338,35 @@ int w2b_exchange_delta(w2b_trainer *t, int64_t chunk, void **buf_dev, int64_t *e
 int w2b_exchange_apply(w2b_trainer *t, int64_t chunk, float scale);
 int w2b_exchange_end(w2b_trainer *t, int64_t word_count_all_replicas);
 
+/* ---- the packed embedding layer --------------------------------------------------------------------------------------
+ * Row lookup and bag pooling straight from a bit-packed table: include/word2bits_embed.h has the types, the constants and
+ * the semantics in full, and is the header a consumer includes.  This header is the list of everything the library
+ * exports (bindings and the ABI test enumerate it), so the entry points are repeated here as bare prototypes; a unit that
+ * includes both headers (csrc/w2b_embed.cpp does) has the compiler check that the two agree. */
+struct w2b_embed;
+int w2b_embed_load(const char *w2bp_file, int64_t threshold, int32_t device, struct w2b_embed **out);
+int w2b_embed_create(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int32_t device, struct w2b_embed **out);
+void w2b_embed_free(struct w2b_embed *e);
+int64_t w2b_embed_rows(const struct w2b_embed *e);
+int64_t w2b_embed_dim(const struct w2b_embed *e);
+int32_t w2b_embed_bitlevel(const struct w2b_embed *e);
+const char *w2b_embed_word(const struct w2b_embed *e, int64_t row);
+int64_t w2b_embed_search(const struct w2b_embed *e, const char *word);
+int w2b_embed_lookup(struct w2b_embed *e, int64_t n, const int32_t *ids, int32_t dtype, void *out);
+int w2b_embed_bag(struct w2b_embed *e, int64_t n_ids, const int32_t *ids, int64_t n_bags, const int64_t *offsets,
+                  int32_t mode, int32_t dtype, void *out);
+int w2b_embed_reserve(struct w2b_embed *e, int64_t max_ids, int64_t max_bags, int32_t dtype, void **ids_dev,
+                      void **offsets_dev, void **out_dev);
+int w2b_embed_lookup_device(struct w2b_embed *e, int64_t n, int32_t dtype);
+int w2b_embed_bag_device(struct w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype);
+int w2b_embed_synchronize(struct w2b_embed *e);
+int w2b_embed_bad_ids(struct w2b_embed *e, int64_t *count);
+int w2b_embed_timing_read(struct w2b_embed *e, double *kernel_ms, int64_t *launches, double *bytes);
+int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
+                          const int32_t *ids, float *out);
+int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                       const int32_t *ids, int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
+
 #ifdef __cplusplus
 }
 #endif

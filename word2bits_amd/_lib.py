@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/word2bits_hip.h, word2bits_corpus.h and word2bits_eval.h.
+"""ctypes binding of the C ABI in include/word2bits_hip.h, word2bits_corpus.h, word2bits_eval.h and word2bits_embed.h.
 
 The shared library is built in-tree by word2bits_amd/csrc/Makefile (hipcc, gfx950).  Importing
 this module fails loudly when it is missing: there is no Python/CPU fallback for the hot path.
@@ -160,6 +160,25 @@ SIGNATURES = {
     "w2b_eval_is_codes": (C.c_int32, [vp]),
     "w2b_eval_get_codes": (C.c_int, [vp, u64p]),
     "w2b_codes_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p, f32p]),
+    # include/word2bits_embed.h
+    "w2b_embed_load": (C.c_int, [C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp)]),
+    "w2b_embed_create": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(vp)]),
+    "w2b_embed_free": (None, [vp]),
+    "w2b_embed_rows": (C.c_int64, [vp]),
+    "w2b_embed_dim": (C.c_int64, [vp]),
+    "w2b_embed_bitlevel": (C.c_int32, [vp]),
+    "w2b_embed_word": (C.c_char_p, [vp, C.c_int64]),
+    "w2b_embed_search": (C.c_int64, [vp, C.c_char_p]),
+    "w2b_embed_lookup": (C.c_int, [vp, C.c_int64, i32p, C.c_int32, vp]),
+    "w2b_embed_bag": (C.c_int, [vp, C.c_int64, i32p, C.c_int64, i64p, C.c_int32, C.c_int32, vp]),
+    "w2b_embed_reserve": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "w2b_embed_lookup_device": (C.c_int, [vp, C.c_int64, C.c_int32]),
+    "w2b_embed_bag_device": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "w2b_embed_synchronize": (C.c_int, [vp]),
+    "w2b_embed_bad_ids": (C.c_int, [vp, i64p]),
+    "w2b_embed_timing_read": (C.c_int, [vp, f64p, i64p, f64p]),
+    "w2b_embed_lookup_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, f32p]),
+    "w2b_embed_bag_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int64, i64p, C.c_int32, f32p]),
 }
 
 _lib = None

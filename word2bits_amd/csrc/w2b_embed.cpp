@@ -1,0 +1,478 @@
+// w2b_embed.cpp -- host side of include/word2bits_embed.h: the handle, the .w2bp loader, validation, the device staging
+// (one set of buffers handed to the caller by w2b_embed_reserve, a separate bounded one for the host form), the chunking
+// of host-form calls, timing, and the host twins of the kernels in w2b_kernels_embed.hip.  The table stays packed on the
+// device; no float table exists on either side and there is no CPU fallback (the *_host twins are for tests).
+#include "../../include/word2bits_embed.h"
+#include "../../include/word2bits_corpus.h"
+#include "../../include/word2bits_hip.h"
+#include "w2b_internal.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace {
+constexpr int64_t kHostOutBytes = 64ll << 20;     // output staging of one host-form chunk
+constexpr int64_t kHostIds = 1ll << 22;           // ids of one host-form chunk (a single bag may be this long)
+constexpr size_t kMaxPending = 256;               // event pairs kept before they are folded into the sums
+
+int efail(int code, const std::string &msg) { return w2b_internal_fail(code, msg.c_str()); }
+#define EHIP(x)                                                                                   \
+  do {                                                                                            \
+    hipError_t e_ = (x);                                                                          \
+    if (e_ != hipSuccess) return efail(W2B_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+int elem_size(int32_t dtype) { return dtype == W2B_EMBED_F32 ? 4 : (dtype == W2B_EMBED_BF16 || dtype == W2B_EMBED_F16) ? 2 : 0; }
+
+// device staging of one form
+struct Staging {
+  long long *ids = nullptr, *offsets = nullptr;
+  void *out = nullptr, *scratch = nullptr;
+  int64_t cap_ids = 0, cap_bags = -1, out_bytes = 0, scratch_bytes = 0;
+};
+struct Pending { hipEvent_t a, b; };
+}  // namespace
+
+struct w2b_embed {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t rows = 0, dim = 0, wpr = 0;
+  int bitlevel = 0;
+  bool has_words = false;
+  std::vector<std::string> names;
+  std::unordered_map<std::string, int64_t> first;
+  uint64_t *T = nullptr;                     // [rows][wpr], the file's layout
+  unsigned long long *bad = nullptr;         // device counter
+  Staging user, host;
+  std::vector<Pending> pending;
+  double kernel_ms = 0, bytes = 0;
+  int64_t launches = 0;
+};
+
+namespace {
+void free_staging(Staging &s) {
+  if (s.ids) (void)hipFree(s.ids);
+  if (s.offsets) (void)hipFree(s.offsets);
+  if (s.out) (void)hipFree(s.out);
+  if (s.scratch) (void)hipFree(s.scratch);
+  s = Staging();
+}
+
+void embed_release(w2b_embed *e) {
+  if (!e) return;
+  (void)hipSetDevice(e->device);
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  for (Pending &p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
+  free_staging(e->user);
+  free_staging(e->host);
+  if (e->T) (void)hipFree(e->T);
+  if (e->bad) (void)hipFree(e->bad);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  delete e;
+}
+struct EmbedRelease { void operator()(w2b_embed *e) const { embed_release(e); } };
+using EmbedPtr = std::unique_ptr<w2b_embed, EmbedRelease>;
+
+// ------------------------------------------------------------------------------------ validation (host form and twins)
+int check_shape(int64_t rows, int64_t dim, int32_t bitlevel, int64_t min_rows, const char *who) {
+  if (rows < min_rows || rows > 0x7FFFFF00ll || dim < 1 || dim > (1 << 24))
+    return efail(W2B_EINVAL, std::string(who) + ": unsupported rows / dim");
+  if (w2b_packed_words_per_row(dim, bitlevel) < 0)
+    return efail(W2B_EUNSUPPORTED, std::string(who) + ": bitlevel must be 1 or 2");
+  return W2B_OK;
+}
+
+int check_ids(int64_t rows, int64_t n, const int32_t *ids, const char *who) {
+  if (n < 0) return efail(W2B_EINVAL, std::string(who) + ": negative id count");
+  if (n > 0 && !ids) return efail(W2B_EINVAL, std::string(who) + ": null ids");
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] >= rows) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "%s: ids[%lld] = %d is not below rows = %lld", who, (long long)i, (int)ids[i], (long long)rows);
+      return efail(W2B_EINVAL, msg);
+    }
+  return W2B_OK;
+}
+
+int check_bags(int64_t n_ids, int64_t n_bags, const int64_t *offsets, int32_t mode, const char *who) {
+  const std::string w(who);
+  if (n_bags < 0 || n_bags > 0x7FFFFF00ll) return efail(W2B_EINVAL, w + ": bad bag count");
+  if (mode != W2B_EMBED_SUM && mode != W2B_EMBED_MEAN) return efail(W2B_EINVAL, w + ": mode is neither W2B_EMBED_SUM nor W2B_EMBED_MEAN");
+  if (!offsets) return n_bags == 0 && n_ids == 0 ? W2B_OK : efail(W2B_EINVAL, w + ": null offsets");
+  if (offsets[0] != 0) return efail(W2B_EINVAL, w + ": offsets[0] is not 0");
+  for (int64_t b = 0; b < n_bags; b++) {
+    if (offsets[b + 1] < offsets[b]) return efail(W2B_EINVAL, w + ": offsets decrease at bag " + std::to_string(b));
+    if (offsets[b + 1] - offsets[b] > W2B_EMBED_MAX_BAG)
+      return efail(W2B_EINVAL, w + ": bag " + std::to_string(b) + " is longer than W2B_EMBED_MAX_BAG");
+  }
+  if (offsets[n_bags] != n_ids) return efail(W2B_EINVAL, w + ": offsets[n_bags] is not n_ids");
+  return W2B_OK;
+}
+
+// ------------------------------------------------------------------------------------ device side of the handle
+int device_visible(int32_t device, const char *who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return efail(W2B_ENOGPU, std::string(who) + ": no HIP device visible (the embedding has no CPU fallback)");
+  if (device < 0 || device >= ndev) return efail(W2B_EINVAL, std::string(who) + ": bad device index");
+  return W2B_OK;
+}
+
+// `bits` = [rows][wpr] packed words in host memory, possibly unaligned (inside a file image)
+int embed_finish(EmbedPtr e, const unsigned char *bits, w2b_embed **out) {
+  EHIP(hipSetDevice(e->device));
+  EHIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  const size_t bytes = (size_t)e->rows * (size_t)e->wpr * 8;
+  if (hipMalloc(&e->T, bytes) != hipSuccess || hipMalloc(&e->bad, 8) != hipSuccess)
+    return efail(W2B_ENOMEM, "w2b_embed: device allocation failed");
+  EHIP(hipMemcpy(e->T, bits, bytes, hipMemcpyHostToDevice));
+  EHIP(hipMemset(e->bad, 0, 8));
+  *out = e.release();
+  return W2B_OK;
+}
+
+template <class P>
+int grow(w2b_embed *e, P *&p, int64_t &have, int64_t want_bytes, int64_t new_have) {
+  EHIP(hipStreamSynchronize(e->stream));          // nothing in flight may still use the old buffer
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  have = 0;
+  void *q = nullptr;
+  if (hipMalloc(&q, (size_t)(want_bytes > 0 ? want_bytes : 8)) != hipSuccess)
+    return efail(W2B_ENOMEM, "w2b_embed: device allocation failed");
+  p = (P *)q;
+  have = new_have;
+  return W2B_OK;
+}
+
+// buffers for max_ids ids, max_bags bags (< 0: none) and out_bytes of output; only ever grows
+int ensure(w2b_embed *e, Staging &s, int64_t max_ids, int64_t max_bags, int64_t out_bytes) {
+  if (max_ids > s.cap_ids || !s.ids)
+    if (int rc = grow(e, s.ids, s.cap_ids, max_ids * 8, max_ids)) return rc;
+  if (max_bags > s.cap_bags || (max_bags >= 0 && !s.offsets))
+    if (int rc = grow(e, s.offsets, s.cap_bags, (max_bags + 1) * 8, max_bags)) return rc;
+  out_bytes = (out_bytes + 15) / 16 * 16;
+  if (out_bytes > s.out_bytes || !s.out)
+    if (int rc = grow(e, s.out, s.out_bytes, out_bytes, out_bytes)) return rc;
+  if (s.cap_bags > 0) {
+    int cap = 0;
+    const int64_t need = w2b_embed_bag_scratch(s.cap_ids, s.cap_bags, (int)e->dim, &cap);
+    if (need > s.scratch_bytes)
+      if (int rc = grow(e, s.scratch, s.scratch_bytes, need, need)) return rc;
+  }
+  return W2B_OK;
+}
+
+int fold_pending(w2b_embed *e) {
+  EHIP(hipStreamSynchronize(e->stream));
+  for (Pending &p : e->pending) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) e->kernel_ms += ms;
+    (void)hipEventDestroy(p.a);
+    (void)hipEventDestroy(p.b);
+  }
+  e->pending.clear();
+  return W2B_OK;
+}
+
+// one timed launch on the handle's stream
+template <class Launch>
+int timed(w2b_embed *e, double bytes, Launch &&launch) {
+  if (e->pending.size() >= kMaxPending)
+    if (int rc = fold_pending(e)) return rc;
+  Pending p{nullptr, nullptr};
+  if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) {
+    if (p.a) (void)hipEventDestroy(p.a);
+    return efail(W2B_EHIP, "w2b_embed: hipEventCreate failed");
+  }
+  hipError_t he = hipEventRecord(p.a, e->stream);
+  if (he == hipSuccess) he = launch();
+  if (he == hipSuccess) he = hipEventRecord(p.b, e->stream);
+  if (he != hipSuccess) {
+    (void)hipEventDestroy(p.a);
+    (void)hipEventDestroy(p.b);
+    return efail(W2B_EHIP, std::string("w2b_embed launch: ") + hipGetErrorString(he));
+  }
+  e->pending.push_back(p);
+  e->launches++;
+  e->bytes += bytes;
+  return W2B_OK;
+}
+
+int launch_lookup(w2b_embed *e, Staging &s, int64_t n, int32_t dtype) {
+  const double bytes = (double)n * (double)e->wpr * 8 + (double)n * (double)e->dim * elem_size(dtype);
+  return timed(e, bytes, [&] {
+    return w2b_launch_embed_lookup(e->T, e->rows, (int)e->dim, e->bitlevel, s.ids, n, dtype, s.out, e->bad, e->stream);
+  });
+}
+
+int launch_bag(w2b_embed *e, Staging &s, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype) {
+  const double bytes = (double)n_ids * (double)e->wpr * 8 + (double)n_bags * (double)e->dim * elem_size(dtype);
+  return timed(e, bytes, [&] {
+    return w2b_launch_embed_bag(e->T, e->rows, (int)e->dim, e->bitlevel, s.ids, n_ids, s.offsets, n_bags, mode, dtype, s.out,
+                                e->bad, s.scratch, e->stream);
+  });
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------ constructors and accessors
+extern "C" int w2b_embed_load(const char *w2bp_file, int64_t threshold, int32_t device, w2b_embed **out) {
+  if (!w2bp_file || !out) return efail(W2B_EINVAL, "w2b_embed_load: null argument");
+  *out = nullptr;
+  FILE *f = fopen(w2bp_file, "rb");
+  if (!f) return efail(W2B_EIO, "Input file not found");
+  fseek(f, 0, SEEK_END);
+  const long long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  std::vector<unsigned char> d(n > 0 ? (size_t)n : 0);
+  const bool ok = n <= 0 || fread(d.data(), 1, (size_t)n, f) == (size_t)n;
+  fclose(f);
+  if (!ok) return efail(W2B_EIO, "w2b_embed_load: short read");
+  if (!w2b_internal_is_packed(d.data(), d.size()))
+    return efail(W2B_EINVAL, "w2b_embed_load: not a W2BP1 bit-packed file (float files are not read here)");
+  EmbedPtr e(new w2b_embed);
+  int64_t dim = 0;
+  int bitlevel = 0;
+  size_t pos = 0;
+  if (w2b_internal_parse_packed_head(d.data(), d.size(), e->names, &dim, &bitlevel, &pos) != W2B_OK)
+    return efail(W2B_EIO, "w2b_embed_load: damaged bit-packed file");
+  if (threshold > 0 && (int64_t)e->names.size() > threshold) e->names.resize((size_t)threshold);
+  e->rows = (int64_t)e->names.size();
+  e->dim = dim;
+  e->bitlevel = bitlevel;
+  e->device = device;
+  if (int rc = check_shape(e->rows, dim, bitlevel, 1, "w2b_embed_load")) return rc;
+  e->wpr = w2b_packed_words_per_row(dim, bitlevel);
+  if (int rc = device_visible(device, "w2b_embed_load")) return rc;
+  e->has_words = true;
+  for (int64_t r = 0; r < e->rows; r++) e->first.emplace(e->names[(size_t)r], r);     // the first row wins
+  return embed_finish(std::move(e), d.data() + pos, out);
+}
+
+extern "C" int w2b_embed_create(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int32_t device,
+                                w2b_embed **out) {
+  if (!packed || !out) return efail(W2B_EINVAL, "w2b_embed_create: null argument");
+  *out = nullptr;
+  if (int rc = check_shape(rows, dim, bitlevel, 1, "w2b_embed_create")) return rc;
+  if (int rc = device_visible(device, "w2b_embed_create")) return rc;
+  EmbedPtr e(new w2b_embed);
+  e->rows = rows;
+  e->dim = dim;
+  e->bitlevel = bitlevel;
+  e->device = device;
+  e->wpr = w2b_packed_words_per_row(dim, bitlevel);
+  return embed_finish(std::move(e), (const unsigned char *)packed, out);
+}
+
+extern "C" void w2b_embed_free(w2b_embed *e) { embed_release(e); }
+extern "C" int64_t w2b_embed_rows(const w2b_embed *e) { return e ? e->rows : 0; }
+extern "C" int64_t w2b_embed_dim(const w2b_embed *e) { return e ? e->dim : 0; }
+extern "C" int32_t w2b_embed_bitlevel(const w2b_embed *e) { return e ? e->bitlevel : 0; }
+extern "C" const char *w2b_embed_word(const w2b_embed *e, int64_t row) {
+  return e && e->has_words && row >= 0 && row < e->rows ? e->names[(size_t)row].c_str() : nullptr;
+}
+extern "C" int64_t w2b_embed_search(const w2b_embed *e, const char *word) {
+  if (!e || !word) return -1;
+  const auto it = e->first.find(word);
+  return it == e->first.end() ? -1 : it->second;
+}
+
+// ------------------------------------------------------------------------------------ host form
+extern "C" int w2b_embed_lookup(w2b_embed *e, int64_t n, const int32_t *ids, int32_t dtype, void *out) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_lookup: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_lookup: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (int rc = check_ids(e->rows, n, ids, "w2b_embed_lookup")) return rc;
+  if (n == 0) return W2B_OK;
+  if (!out) return efail(W2B_EINVAL, "w2b_embed_lookup: null output");
+  EHIP(hipSetDevice(e->device));
+  const int64_t row_bytes = e->dim * es;
+  int64_t chunk = kHostOutBytes / row_bytes;
+  chunk = chunk < 1 ? 1 : (chunk > kHostIds ? kHostIds : chunk);
+  std::vector<long long> wide;
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    const int64_t c = n - i0 < chunk ? n - i0 : chunk;
+    if (int rc = ensure(e, e->host, c, -1, c * row_bytes)) return rc;
+    wide.assign(ids + i0, ids + i0 + c);
+    EHIP(hipMemcpyAsync(e->host.ids, wide.data(), (size_t)c * 8, hipMemcpyHostToDevice, e->stream));
+    if (int rc = launch_lookup(e, e->host, c, dtype)) return rc;
+    EHIP(hipMemcpyAsync((char *)out + i0 * row_bytes, e->host.out, (size_t)(c * row_bytes), hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+  }
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_bag(w2b_embed *e, int64_t n_ids, const int32_t *ids, int64_t n_bags, const int64_t *offsets,
+                             int32_t mode, int32_t dtype, void *out) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_bag: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_bag: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (int rc = check_ids(e->rows, n_ids, ids, "w2b_embed_bag")) return rc;
+  if (int rc = check_bags(n_ids, n_bags, offsets, mode, "w2b_embed_bag")) return rc;
+  if (n_bags == 0) return W2B_OK;
+  if (!out) return efail(W2B_EINVAL, "w2b_embed_bag: null output");
+  EHIP(hipSetDevice(e->device));
+  const int64_t row_bytes = e->dim * es;
+  int64_t max_bags = kHostOutBytes / row_bytes;
+  if (max_bags < 1) max_bags = 1;
+  std::vector<long long> wide, off;
+  for (int64_t b0 = 0; b0 < n_bags;) {
+    int64_t b1 = b0 + 1;                                   // bags b0 .. b1 - 1: at least one, then while they fit
+    while (b1 < n_bags && b1 - b0 < max_bags && offsets[b1 + 1] - offsets[b0] <= kHostIds) b1++;
+    const int64_t i0 = offsets[b0], ci = offsets[b1] - i0, cb = b1 - b0;
+    if (int rc = ensure(e, e->host, ci > 0 ? ci : 1, cb, cb * row_bytes)) return rc;
+    wide.assign(ids + i0, ids + i0 + ci);
+    off.resize((size_t)cb + 1);
+    for (int64_t b = 0; b <= cb; b++) off[(size_t)b] = offsets[b0 + b] - i0;
+    if (ci > 0) EHIP(hipMemcpyAsync(e->host.ids, wide.data(), (size_t)ci * 8, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(e->host.offsets, off.data(), (size_t)(cb + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    if (int rc = launch_bag(e, e->host, ci, cb, mode, dtype)) return rc;
+    EHIP(hipMemcpyAsync((char *)out + b0 * row_bytes, e->host.out, (size_t)(cb * row_bytes), hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+    b0 = b1;
+  }
+  return W2B_OK;
+}
+
+// ------------------------------------------------------------------------------------ device form
+extern "C" int w2b_embed_reserve(w2b_embed *e, int64_t max_ids, int64_t max_bags, int32_t dtype, void **ids_dev,
+                                 void **offsets_dev, void **out_dev) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_reserve: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (max_ids < 0 || max_bags < 0 || max_bags > 0x7FFFFF00ll || max_ids > (1ll << 40))
+    return efail(W2B_EINVAL, "w2b_embed_reserve: bad sizes");
+  EHIP(hipSetDevice(e->device));
+  const int64_t out_rows = max_ids > max_bags ? max_ids : max_bags;
+  if (int rc = ensure(e, e->user, max_ids, max_bags, out_rows * e->dim * es)) return rc;
+  if (ids_dev) *ids_dev = e->user.ids;
+  if (offsets_dev) *offsets_dev = e->user.offsets;
+  if (out_dev) *out_dev = e->user.out;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_lookup_device(w2b_embed *e, int64_t n, int32_t dtype) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_lookup_device: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_lookup_device: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (n < 0) return efail(W2B_EINVAL, "w2b_embed_lookup_device: negative id count");
+  if (n == 0) return W2B_OK;
+  if (!e->user.ids || !e->user.out || n > e->user.cap_ids || n * e->dim * es > e->user.out_bytes)
+    return efail(W2B_EINVAL, "w2b_embed_lookup_device: more than w2b_embed_reserve has set aside");
+  EHIP(hipSetDevice(e->device));
+  return launch_lookup(e, e->user, n, dtype);
+}
+
+extern "C" int w2b_embed_bag_device(w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_bag_device: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_bag_device: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (mode != W2B_EMBED_SUM && mode != W2B_EMBED_MEAN)
+    return efail(W2B_EINVAL, "w2b_embed_bag_device: mode is neither W2B_EMBED_SUM nor W2B_EMBED_MEAN");
+  if (n_ids < 0 || n_bags < 0) return efail(W2B_EINVAL, "w2b_embed_bag_device: negative count");
+  if (n_bags == 0) return W2B_OK;
+  const Staging &s = e->user;
+  if (!s.ids || !s.offsets || !s.out || !s.scratch || n_ids > s.cap_ids || n_bags > s.cap_bags ||
+      n_bags * e->dim * es > s.out_bytes)
+    return efail(W2B_EINVAL, "w2b_embed_bag_device: more than w2b_embed_reserve has set aside");
+  EHIP(hipSetDevice(e->device));
+  return launch_bag(e, e->user, n_ids, n_bags, mode, dtype);
+}
+
+extern "C" int w2b_embed_synchronize(w2b_embed *e) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_synchronize: null handle");
+  EHIP(hipSetDevice(e->device));
+  EHIP(hipStreamSynchronize(e->stream));
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_bad_ids(w2b_embed *e, int64_t *count) {
+  if (!e || !count) return efail(W2B_EINVAL, "w2b_embed_bad_ids: null argument");
+  EHIP(hipSetDevice(e->device));
+  EHIP(hipStreamSynchronize(e->stream));
+  unsigned long long c = 0;
+  EHIP(hipMemcpy(&c, e->bad, 8, hipMemcpyDeviceToHost));
+  EHIP(hipMemset(e->bad, 0, 8));
+  *count = (int64_t)c;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_timing_read(w2b_embed *e, double *kernel_ms, int64_t *launches, double *bytes) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_timing_read: null handle");
+  EHIP(hipSetDevice(e->device));
+  if (int rc = fold_pending(e)) return rc;
+  if (kernel_ms) *kernel_ms = e->kernel_ms;
+  if (launches) *launches = e->launches;
+  if (bytes) *bytes = e->bytes;
+  e->kernel_ms = 0;
+  e->launches = 0;
+  e->bytes = 0;
+  return W2B_OK;
+}
+
+// ------------------------------------------------------------------------------------ host twins
+static inline float bits_f32(uint32_t b) { float x; memcpy(&x, &b, 4); return x; }
+
+extern "C" int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
+                                     const int32_t *ids, float *out) {
+  if (!packed) return efail(W2B_EINVAL, "w2b_embed_lookup_host: null table");
+  if (int rc = check_shape(rows, dim, bitlevel, 0, "w2b_embed_lookup_host")) return rc;
+  if (int rc = check_ids(rows, n, ids, "w2b_embed_lookup_host")) return rc;
+  if (n == 0) return W2B_OK;
+  if (!out) return efail(W2B_EINVAL, "w2b_embed_lookup_host: null output");
+  const int64_t wpr = w2b_packed_words_per_row(dim, bitlevel);
+  for (int64_t i = 0; i < n; i++) {
+    float *o = out + i * dim;
+    if (ids[i] < 0) {
+      for (int64_t c = 0; c < dim; c++) o[c] = 0.f;
+      continue;
+    }
+    const uint64_t *row = packed + (int64_t)ids[i] * wpr;
+    for (int64_t c = 0; c < dim; c++) {
+      const uint64_t *blk = row + (c >> 6) * bitlevel;
+      const uint32_t s = (uint32_t)(blk[0] >> (c & 63)) & 1u;
+      const uint32_t mag = bitlevel == 1 ? 0x3EAAAAABu : (((blk[1] >> (c & 63)) & 1u) ? 0x3F400000u : 0x3E800000u);
+      o[c] = bits_f32(mag | (s << 31));
+    }
+  }
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                                  const int32_t *ids, int64_t n_bags, const int64_t *offsets, int32_t mode, float *out) {
+  if (!packed) return efail(W2B_EINVAL, "w2b_embed_bag_host: null table");
+  if (int rc = check_shape(rows, dim, bitlevel, 0, "w2b_embed_bag_host")) return rc;
+  if (int rc = check_ids(rows, n_ids, ids, "w2b_embed_bag_host")) return rc;
+  if (int rc = check_bags(n_ids, n_bags, offsets, mode, "w2b_embed_bag_host")) return rc;
+  if (n_bags == 0) return W2B_OK;
+  if (!out) return efail(W2B_EINVAL, "w2b_embed_bag_host: null output");
+  const int64_t wpr = w2b_packed_words_per_row(dim, bitlevel);
+  const float q = bitlevel == 1 ? bits_f32(0x3EAAAAABu) : 0.25f;
+  std::vector<int32_t> T((size_t)dim);
+  for (int64_t b = 0; b < n_bags; b++) {
+    std::fill(T.begin(), T.end(), 0);
+    int32_t m = 0;
+    for (int64_t i = offsets[b]; i < offsets[b + 1]; i++) {
+      if (ids[i] < 0) continue;
+      m++;
+      const uint64_t *row = packed + (int64_t)ids[i] * wpr;
+      for (int64_t c = 0; c < dim; c++) {
+        const uint64_t *blk = row + (c >> 6) * bitlevel;
+        const int s = (int)((blk[0] >> (c & 63)) & 1u);
+        const int mag = bitlevel == 2 && ((blk[1] >> (c & 63)) & 1u) ? 3 : 1;
+        T[(size_t)c] += s ? -mag : mag;
+      }
+    }
+    float *o = out + b * dim;
+    for (int64_t c = 0; c < dim; c++) {
+      const float sum = (float)T[(size_t)c] * q;             // one float32 multiply (no contraction: -ffp-contract=off)
+      o[c] = mode == W2B_EMBED_MEAN ? (m > 0 ? sum / (float)m : 0.f) : sum;
+    }
+  }
+  return W2B_OK;
+}

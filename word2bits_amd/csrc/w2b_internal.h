@@ -196,6 +196,16 @@ hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const fl
                                  int nq, const int *b1, const int *b2, const int *b3, int k, unsigned long long *best,
                                  unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
                                  unsigned long long *out, hipStream_t s);
+// the packed embedding layer (w2b_kernels_embed.hip; include/word2bits_embed.h).  T = the packed table [rows][wpr], ids /
+// offsets = int64 device buffers, `bad` = the device counter of ignored ids and clamped bags.  A bag launch needs
+// w2b_embed_bag_scratch(...) bytes of device scratch (it zeroes them itself).
+#define W2B_EMBED_SPLIT 1024        // ids of a bag that one workgroup pools; longer bags are split into segments of this length
+hipError_t w2b_launch_embed_lookup(const uint64_t *T, long long rows, int dim, int bitlevel, const long long *ids, long long n,
+                                   int dtype, void *out, unsigned long long *bad, hipStream_t s);
+long long w2b_embed_bag_scratch(long long n_ids, long long n_bags, int dim, int *cap_out);
+hipError_t w2b_launch_embed_bag(const uint64_t *T, long long rows, int dim, int bitlevel, const long long *ids, long long n_ids,
+                                const long long *offsets, long long n_bags, int mode, int dtype, void *out,
+                                unsigned long long *bad, void *scratch, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

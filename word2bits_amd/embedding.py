@@ -1,0 +1,186 @@
+"""ctypes / torch front of the packed embedding layer (include/word2bits_embed.h).
+
+    emb = PackedEmbedding("vectors.w2bp")                       # the table stays packed on the device: 1 or 2 bits a value
+    rows = emb.lookup([3, 17, -1])                              # numpy float32 [3, dim]; id < 0 is padding (a zero row)
+    sent = emb.bag(ids, offsets, mode="mean")                   # numpy [n_bags, dim]; bag b = ids[offsets[b]:offsets[b+1]]
+    x = emb.torch_lookup(token_ids, dtype=torch.bfloat16)       # torch tensor on the device, ids from any device
+    s = emb.torch_bag(token_ids, offsets, mode="sum")
+
+Lookup and pooling run on the MI355X (w2b_kernels_embed.hip); there is no CPU path in this module.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
+MODES = {"sum": 0, "mean": 1}
+MAX_BAG = 1 << 22
+
+
+def _dtype_code(dtype):
+    name = str(dtype).replace("torch.", "")
+    if name not in DTYPES:
+        raise ValueError("dtype must be float32, bfloat16 or float16")
+    return DTYPES[name]
+
+
+def _mode_code(mode):
+    if mode not in MODES:
+        raise ValueError("mode must be 'sum' or 'mean'")
+    return MODES[mode]
+
+
+class PackedEmbedding:
+    """A read-only embedding table of a 1-bit or 2-bit model, bit-packed on the device.  Either `path` (a .w2bp file;
+    `threshold` caps the rows) or `packed` (uint64 [rows, words_per_row] in the .w2bp layout, e.g. Trainer.export_packed())
+    with `dim` and `bitlevel`."""
+
+    def __init__(self, path=None, packed=None, dim=None, bitlevel=None, threshold=0, device=0):
+        self._h = C.c_void_p()
+        self._L = _lib.lib()
+        self.device = int(device)
+        if (path is None) == (packed is None):
+            raise ValueError("give either path or packed")
+        if path is not None:
+            _lib.check(self._L.w2b_embed_load(str(path).encode(), int(threshold), self.device, C.byref(self._h)))
+        else:
+            if dim is None or bitlevel is None:
+                raise ValueError("packed rows need dim and bitlevel")
+            packed = np.ascontiguousarray(packed, np.uint64)
+            wpr = int(self._L.w2b_packed_words_per_row(int(dim), int(bitlevel)))
+            if wpr > 0 and (packed.ndim != 2 or packed.shape[1] != wpr):
+                raise ValueError("packed must be [rows, %d] for dim %d at bitlevel %d" % (wpr, dim, bitlevel))
+            _lib.check(self._L.w2b_embed_create(packed.ctypes.data_as(_lib.u64p), packed.shape[0], int(dim), int(bitlevel),
+                                                self.device, C.byref(self._h)))
+        self.rows = int(self._L.w2b_embed_rows(self._h))
+        self.dim = int(self._L.w2b_embed_dim(self._h))
+        self.bitlevel = int(self._L.w2b_embed_bitlevel(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.w2b_embed_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def word(self, row):
+        """The word of `row` (bytes), None on a handle made from packed rows."""
+        return self._L.w2b_embed_word(self._h, int(row))
+
+    def search(self, word):
+        """The first row whose word is exactly `word` (bytes or str), -1 if there is none."""
+        return int(self._L.w2b_embed_search(self._h, word if isinstance(word, bytes) else str(word).encode()))
+
+    # ---- host form: numpy in, numpy out
+    @staticmethod
+    def _out(shape, code):
+        return np.empty(shape, (np.float32, np.uint16, np.float16)[code])
+
+    def lookup(self, ids, dtype="float32"):
+        """Rows of `ids` (int array, any shape; < 0 = padding): numpy ids.shape + (dim,).  float16 comes as np.float16,
+        bfloat16 as np.uint16 bit patterns."""
+        code = _dtype_code(dtype)
+        ids = np.ascontiguousarray(ids, np.int32)
+        out = self._out(ids.shape + (self.dim,), code)
+        _lib.check(self._L.w2b_embed_lookup(self._h, ids.size, ids.ctypes.data_as(_lib.i32p), code,
+                                            C.c_void_p(out.ctypes.data)))
+        return out
+
+    def bag(self, ids, offsets, mode="sum", dtype="float32"):
+        """Sum or mean of the rows of every bag: numpy [len(offsets) - 1, dim]."""
+        code, m = _dtype_code(dtype), _mode_code(mode)
+        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        offsets = np.ascontiguousarray(offsets, np.int64).ravel()
+        if offsets.size < 1:
+            raise ValueError("offsets has n_bags + 1 entries")
+        out = self._out((offsets.size - 1, self.dim), code)
+        _lib.check(self._L.w2b_embed_bag(self._h, ids.size, ids.ctypes.data_as(_lib.i32p), offsets.size - 1,
+                                         offsets.ctypes.data_as(_lib.i64p), m, code, C.c_void_p(out.ctypes.data)))
+        return out
+
+    # ---- device form: library-owned staging, viewed by torch
+    def reserve(self, max_ids, max_bags=0, dtype="float32"):
+        """(ids_dev, offsets_dev, out_dev) addresses of the library's staging buffers (w2b_embed_reserve)."""
+        p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        _lib.check(self._L.w2b_embed_reserve(self._h, int(max_ids), int(max_bags), _dtype_code(dtype), *map(C.byref, p)))
+        return tuple(x.value for x in p)
+
+    def lookup_device(self, n, dtype="float32"):
+        _lib.check(self._L.w2b_embed_lookup_device(self._h, int(n), _dtype_code(dtype)))
+
+    def bag_device(self, n_ids, n_bags, mode="sum", dtype="float32"):
+        _lib.check(self._L.w2b_embed_bag_device(self._h, int(n_ids), int(n_bags), _mode_code(mode), _dtype_code(dtype)))
+
+    def synchronize(self):
+        _lib.check(self._L.w2b_embed_synchronize(self._h))
+
+    def bad_ids(self):
+        """Ids >= rows and clamped bags that the device form has ignored since the last call (synchronises, resets)."""
+        n = C.c_int64()
+        _lib.check(self._L.w2b_embed_bad_ids(self._h, C.byref(n)))
+        return n.value
+
+    def _view(self, ptr, count, typestr):
+        """torch view (no copy) of `count` elements of a library-owned device buffer (as Trainer.model_tensor)"""
+        import torch
+
+        class _View:
+            __cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(_View(), device=torch.device("cuda", self.device))
+
+    def staging(self, max_ids, max_bags=0, dtype="float32"):
+        """torch views of the staging buffers: ids int64 [max_ids], offsets int64 [max_bags + 1], out [max(max_ids,
+        max_bags), dim] of `dtype`; valid until a later call reserves more."""
+        import torch
+        code = _dtype_code(dtype)
+        ids_p, off_p, out_p = self.reserve(max_ids, max_bags, dtype)
+        nout = max(int(max_ids), int(max_bags))
+        out = self._view(out_p, max(nout * self.dim, 1), ("<f4", "<i2", "<f2")[code])
+        if code == 1:
+            out = out.view(torch.bfloat16)
+        return (self._view(ids_p, max(int(max_ids), 1), "<i8")[:int(max_ids)],
+                self._view(off_p, int(max_bags) + 1, "<i8"), out[:nout * self.dim].view(nout, self.dim))
+
+    def _finish(self, out, copy, what):
+        self.synchronize()
+        bad = self.bad_ids()
+        if bad:
+            raise _lib.W2bError(_lib.W2B_EINVAL, "%s: %d ids >= rows or bag bounds outside the ids" % (what, bad))
+        return out.clone() if copy else out
+
+    def torch_lookup(self, ids, dtype=None, copy=True):
+        """Rows of `ids` (torch integer tensor on any device): tensor ids.shape + (dim,) on this handle's device.
+        copy=False returns the view of the library's buffer, valid until the next call on this handle."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        n = ids.numel()
+        ids_t, _, out = self.staging(n, 0, dtype)
+        if n:
+            ids_t.copy_(ids.reshape(-1))
+            torch.cuda.synchronize()                  # the library's stream does not wait for torch's
+            self.lookup_device(n, dtype)
+        return self._finish(out[:n].view(tuple(ids.shape) + (self.dim,)), copy, "torch_lookup")
+
+    def torch_bag(self, ids, offsets, mode="sum", dtype=None, copy=True):
+        """Sum or mean per bag (torch integer tensors on any device; offsets has n_bags + 1 entries): [n_bags, dim]."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        n, nb = ids.numel(), offsets.numel() - 1
+        if nb < 0:
+            raise ValueError("offsets has n_bags + 1 entries")
+        ids_t, off_t, out = self.staging(n, nb, dtype)
+        if nb:
+            if n:
+                ids_t.copy_(ids.reshape(-1))
+            off_t.copy_(offsets.reshape(-1))
+            torch.cuda.synchronize()
+            self.bag_device(n, nb, mode, dtype)
+        return self._finish(out[:nb], copy, "torch_bag")
+
+    def timing(self):
+        """(kernel ms, launches, bytes moved: packed words read + output written) since the last call."""
+        ms, n, b = C.c_double(), C.c_int64(), C.c_double()
+        _lib.check(self._L.w2b_embed_timing_read(self._h, C.byref(ms), C.byref(n), C.byref(b)))
+        return ms.value, n.value, b.value
