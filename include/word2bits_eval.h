@@ -83,7 +83,7 @@ int w2b_eval_neighbors(w2b_eval *e, int64_t nq, const int32_t *rows, int32_t k, 
  *     (float)I / (float)size.  Slots (+b2, -b1, +b3) again equal w2b_eval_topk exactly.
  *   codes handle: W2B_EINVAL ("not available in codes mode").  Deliberately: the 2-bit scan keeps three accumulator tiles
  *     per (question, row) next to 104-152 registers of unpacked rows, and a per-question number of terms does not fit that
- *     shape without another kernel design.
+ *     shape without another kernel design.  (w2b_eval_bag below is that design for sums without signs.)
  * W2B_EINVAL, with the cause in w2b_last_error(): nt outside 1..W2B_EVAL_MAX_TERMS, k outside 1..W2B_EVAL_MAX_K, a sign
  * other than -1, 0, +1, a used slot's row outside [0, words), a question without a used slot.
  * w2b_eval_timing_read counts these launches like the top-k ones, and w2b_eval_set_topk_scratch bounds their scratch. */
@@ -208,6 +208,53 @@ int w2b_eval_get_codes(w2b_eval *e, uint64_t *out);
  * score_out[words] = the float score.  Either output may be NULL. */
 int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
                           int32_t *J_out, float *score_out);
+
+/* ---- bag questions: the rows nearest to a pooled bag of rows, on both packed modes ----------------------------------
+ * "Which words are nearest to this sentence, this ten-word phrase, this document?"  A question is a BAG of rows, pooled as
+ * w2b_embed_bag pools it in SUM mode (include/word2bits_embed.h): the unnormalised integer vector
+ *     T[a] = sum over the bag's ids r >= 0 of t_r[a],   t = +-1 on a bits handle, t in {+-1, +-3} on a codes handle
+ * -- the same row several times adds; |T[a]| <= 3 * W2B_EVAL_MAX_BAG = 12288 -- and scored against every row c by
+ *     J(c) = sum_a T[a] * t_c[a]  over the `size` columns, exact,  |J| <= 9 * 4096 * size.
+ * A handle with 9 * 4096 * size >= 2^31 (size > 58254) is W2B_EINVAL.  A bits or a codes handle is required; an fp32 handle is
+ * W2B_EINVAL.  The scan runs on the i8 matrix cores in both modes (word2bits_amd/csrc/w2b_kernels_evalbag.hip).
+ *   bags: offsets is [nq + 1], non-decreasing, offsets[0] == 0, offsets[nq] == n_ids; question q is
+ *     ids[offsets[q] .. offsets[q + 1]).  An id < 0 is padding and contributes nothing; an id >= w2b_eval_words(e) is
+ *     W2B_EINVAL; a bag of more than W2B_EVAL_MAX_BAG ids, padding included, is W2B_EINVAL.  nq == 0 is W2B_OK.
+ *   bits handle: answers are the rows with J > 0, by J descending, equal J in ascending row order; the score is
+ *     (float)J / (float)size, one correctly rounded division.  A bag of m <= 7 ids with exclude_own = 1 therefore returns bit
+ *     for bit what w2b_eval_combine returns for the same rows with signs all +1.
+ *   codes handle: N_T = sum_a T[a]^2 (an int64), wq = (float)(1.0 / sqrt((double)N_T)) -- the double square root and the
+ *     double division each correctly rounded, the result rounded to float: the expression of w(r) -- and
+ *         score = ((float)J * wq) * w(c),
+ *     the conversion rounded to nearest even, both multiplies rounded on their own, nothing contracted.  Answers are the rows
+ *     with score > 0, by score descending, equal float scores in ascending row order: the codes key, score bits << 32 | ~row.
+ *     A one-id bag [r] has N_T = N(r): with exclude_own = 1 it returns bit for bit what w2b_eval_neighbors returns for r.
+ *   empty questions: a bag with no id >= 0, or with T zero in every column, has the empty list: row -1 / score 0 throughout.
+ *   exclude_own: 1 = every row that stands in the bag is excluded from that question's answers, as w2b_eval_combine does;
+ *     0 = nothing is excluded (document -> words, where the document's own words are wanted); anything else is W2B_EINVAL.
+ *   output: 1 <= k <= W2B_EVAL_MAX_K; best / bestd are [nq][k] in the shape of w2b_eval_topk: a short list ends in row -1 /
+ *     score 0, bestd may be NULL.
+ * Everything is validated before anything is launched -- what does not depend on the handle (k, exclude_own, the offsets, the
+ * bag lengths) first, then the handle, then the ids -- with the cause in w2b_last_error(); on error best / bestd are untouched.
+ * w2b_eval_set_topk_scratch bounds the scratch of a launch (the operands, 2 * 32 * ceil(size / 32) bytes per question, plus
+ * the selection slots); here a chunk is never smaller than 32 questions, and results never depend on it.
+ * w2b_eval_timing_read counts these launches (operands + scan + merge), macs = 2 x questions x rows x size. */
+#define W2B_EVAL_MAX_BAG 4096
+int w2b_eval_bag(w2b_eval *e, int64_t n_ids, const int32_t *ids, int64_t nq, const int64_t *offsets,
+                 int32_t exclude_own, int32_t k, int32_t *best, float *bestd);
+/* The text form of `./nearest ... bag`: every non-empty line is one bag of 1 to W2B_EVAL_MAX_BAG words, upper-cased and looked
+ * up as in w2b_eval_nearest_text; the answer has the format of w2b_eval_nearest_text.  Error lines:
+ * "<head>: not in vocabulary: <WORD>\n" (the first such word) and "<head>: expected 1 to 4096 words\n".  All valid lines are
+ * scored in one w2b_eval_bag batch. */
+int w2b_eval_bag_text(w2b_eval *e, const char *queries, int64_t len, int32_t exclude_own, int32_t k,
+                      char **out, int64_t *out_len);
+/* Host twin of the bag kernels (pure C, no device): ONE bag ids[0..n) of packed[words][bitlevel * ceil(dim / 64)] scored
+ * against EVERY row c, the bag's own rows included: J_out[words] = J(c), score_out[words] = the float score with the
+ * semantics above for bitlevel 1 (bits) or 2 (codes); all scores are 0 when T is zero in every column.  Either output may be
+ * NULL.  W2B_EINVAL as w2b_eval_bag has it: a bitlevel other than 1 or 2, n outside 0..W2B_EVAL_MAX_BAG, an id >= words,
+ * dim > 58254. */
+int w2b_bag_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel,
+                        int64_t n, const int32_t *ids, int32_t *J_out, float *score_out);
 
 #ifdef __cplusplus
 }

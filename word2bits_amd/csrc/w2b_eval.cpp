@@ -2,12 +2,14 @@
 // machine and the stdout transcript of the reference evaluator (ref src/compute-accuracy.c:80-188), around the
 // GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
 // w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
-// adds to the first two.  No arithmetic on scores happens here and there is no CPU fallback
-// (w2b_codes_scores_host is the tests' twin of the codes kernels).
+// adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms.  No arithmetic on scores happens
+// here (one exception: the bag question's weight 1 / sqrt(N_T), built from the integer the device sums) and there is no CPU
+// fallback (w2b_codes_scores_host and w2b_bag_scores_host are the tests' twins of the kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -61,6 +63,9 @@ struct w2b_eval {
   int32_t *terms = nullptr;
   uint32_t *P4 = nullptr;                               // [4 * 2 * wpr][cap_t]
   int64_t cap_t = 0;
+  // w2b_eval_bag: the chunk's bags (weights, ids, bounds, own rows) and the questions' digit planes
+  void *bag_buf = nullptr, *bag_T = nullptr;
+  size_t bag_bytes = 0, bag_T_bytes = 0;
   unsigned long long *best = nullptr;
   int64_t cap_q = 0;
   double kernel_ms = 0;                                 // score-kernel time since the last timing_read
@@ -83,6 +88,8 @@ static void eval_release(w2b_eval *e) {
   if (e->b123) (void)hipFree(e->b123);
   if (e->terms) (void)hipFree(e->terms);
   if (e->P4) (void)hipFree(e->P4);
+  if (e->bag_buf) (void)hipFree(e->bag_buf);
+  if (e->bag_T) (void)hipFree(e->bag_T);
   if (e->best) (void)hipFree(e->best);
   if (e->tk_buf) (void)hipFree(e->tk_buf);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -574,6 +581,65 @@ extern "C" int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int6
   return W2B_OK;
 }
 
+namespace {
+constexpr int64_t kBagMaxSize = 58254;   // the largest size with 9 * 4096 * size < 2^31
+
+// what w2b_eval_bag and its host twin refuse in one bag (null: nothing)
+const char *bad_bag(int64_t n, const int32_t *ids, int64_t words) {
+  if (n < 0 || n > W2B_EVAL_MAX_BAG) return "a bag holds at most 4096 ids";
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] >= words) return "bag id out of range";
+  return nullptr;
+}
+
+// wq of the header from N_T; a question whose vector is zero weighs nothing
+inline float bag_weight(unsigned long long nt) { return nt ? (float)(1.0 / sqrt((double)nt)) : 0.f; }
+}  // namespace
+
+// Host twin of the bag kernels: T from the unpacked rows, J in 64 bits, the float steps of the header one at a time (this
+// file is built with -ffp-contract=off, and the function says so again).
+extern "C" int w2b_bag_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n,
+                                   const int32_t *ids, int32_t *J_out, float *score_out) {
+#pragma clang fp contract(off)
+  const std::string who = "w2b_bag_scores_host";
+  if (!packed || words < 0 || dim < 1 || (n > 0 && !ids)) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (dim > kBagMaxSize) return efail(W2B_EINVAL, who + ": size must be at most 58254 (9 * 4096 * size < 2^31)");
+  if (const char *why = bad_bag(n, ids, words)) return efail(W2B_EINVAL, who + ": " + why);
+  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
+  auto t_of = [&](const uint64_t *r, int64_t a) -> int32_t {
+    const uint64_t bit = 1ull << (a & 63);
+    if (bitlevel == 1) return (r[a >> 6] & bit) ? -1 : 1;
+    return ((r[2 * (a >> 6) + 1] & bit) ? 3 : 1) * ((r[2 * (a >> 6)] & bit) ? -1 : 1);
+  };
+  std::vector<int32_t> T((size_t)dim, 0);
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] >= 0)
+      for (int64_t a = 0; a < dim; a++) T[(size_t)a] += t_of(packed + (int64_t)ids[i] * wpr, a);
+  unsigned long long nt = 0;
+  for (int64_t a = 0; a < dim; a++) nt += (unsigned long long)((int64_t)T[(size_t)a] * T[(size_t)a]);
+  const float wq = bag_weight(nt);
+  const std::vector<float> wt = bitlevel == 2 ? codes_weights(dim) : std::vector<float>();
+  for (int64_t c = 0; c < words; c++) {
+    const uint64_t *rc = packed + c * wpr;
+    int64_t j = 0, n3 = 0;
+    for (int64_t a = 0; a < dim; a++) {
+      const int32_t t = t_of(rc, a);
+      j += (int64_t)T[(size_t)a] * t;
+      n3 += t == 3 || t == -3;
+    }
+    if (J_out) J_out[c] = (int32_t)j;
+    if (!score_out) continue;
+    if (bitlevel == 1) {
+      score_out[c] = (float)(int32_t)j / (float)dim;
+    } else {
+      const float pj = (float)(int32_t)j * wq;
+      score_out[c] = pj * wt[(size_t)n3];
+    }
+  }
+  return W2B_OK;
+}
+
 extern "C" void w2b_eval_free(w2b_eval *e) { eval_release(e); }
 extern "C" int64_t w2b_eval_words(const w2b_eval *e) { return e ? e->words : 0; }
 extern "C" int64_t w2b_eval_size(const w2b_eval *e) { return e ? e->size : 0; }
@@ -626,6 +692,17 @@ static int eval_reserve_terms(w2b_eval *e, int64_t np) {
   if (hipMalloc(&e->terms, (size_t)np * W2B_EVAL_XSTRIDE * 8) != hipSuccess) return W2B_ENOMEM;
   if (e->bits && hipMalloc(&e->P4, (size_t)np * (size_t)e->wpr * 32) != hipSuccess) return W2B_ENOMEM;
   e->cap_t = np;
+  return W2B_OK;
+}
+
+// one of the two per-call buffers of w2b_eval_bag
+static int eval_reserve_bag(void **buf, size_t *have, size_t need) {
+  if (need <= *have) return W2B_OK;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *have = 0;
+  if (hipMalloc(buf, need) != hipSuccess) return W2B_ENOMEM;
+  *have = need;
   return W2B_OK;
 }
 
@@ -866,6 +943,86 @@ struct ScanBits {
   float score(unsigned long long key) const { return (float)(int32_t)(key >> 32) / (float)e->size; }   // one correctly rounded division
 };
 
+struct EventPair;
+
+// The bags of w2b_eval_bag.  A chunk's ids go up as they are, its bounds rebased to the chunk's first id; with `exclude`
+// also every question's own rows, sorted and without repeats, and their bounds.  One device buffer, in this order:
+// N_T [np32] (64-bit), wq [np32], bounds [n + 1], own bounds [n + 1], ids, own rows (np32 = n rounded up to 32).
+struct Bags {
+  const int32_t *ids;
+  const int64_t *offsets;
+  bool exclude;
+  std::vector<int32_t> h_off, h_xoff, h_x;      // what the asynchronous copies read
+  unsigned long long *d_nt = nullptr;
+  float *d_wq = nullptr;
+  int32_t *d_off = nullptr, *d_xoff = nullptr, *d_ids = nullptr, *d_x = nullptr;
+  int64_t np32 = 0;
+  int upload(w2b_eval *e, int64_t q0, int64_t n, int64_t) {
+    const int64_t i0 = offsets[q0], m = offsets[q0 + n] - i0;
+    h_off.resize((size_t)n + 1);
+    for (int64_t q = 0; q <= n; q++) h_off[(size_t)q] = (int32_t)(offsets[q0 + q] - i0);
+    h_xoff.assign(1, 0);
+    h_x.clear();
+    if (exclude)
+      for (int64_t q = 0; q < n; q++) {
+        const size_t at = h_x.size();
+        for (int64_t i = offsets[q0 + q]; i < offsets[q0 + q + 1]; i++)
+          if (ids[i] >= 0) h_x.push_back(ids[i]);
+        std::sort(h_x.begin() + (long)at, h_x.end());
+        h_x.erase(std::unique(h_x.begin() + (long)at, h_x.end()), h_x.end());
+        h_xoff.push_back((int32_t)h_x.size());
+      }
+    np32 = (n + 31) / 32 * 32;
+    const size_t ints = 2 * ((size_t)n + 1) + (size_t)m + h_x.size();
+    if (eval_reserve_bag(&e->bag_buf, &e->bag_bytes, (size_t)np32 * 12 + ints * 4) != W2B_OK)
+      return efail(W2B_ENOMEM, "w2b_eval_bag: device allocation failed");
+    d_nt = (unsigned long long *)e->bag_buf;
+    d_wq = (float *)(d_nt + np32);
+    d_off = (int32_t *)(d_wq + np32);
+    d_xoff = d_off + n + 1;
+    d_ids = d_xoff + n + 1;
+    d_x = d_ids + m;
+    EHIP(hipMemcpyAsync(d_off, h_off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    if (m > 0) EHIP(hipMemcpyAsync(d_ids, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+    if (exclude) {
+      EHIP(hipMemcpyAsync(d_xoff, h_xoff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+      if (!h_x.empty()) EHIP(hipMemcpyAsync(d_x, h_x.data(), h_x.size() * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    return W2B_OK;
+  }
+};
+
+// The bag question on a bits or a codes handle (include/word2bits_eval.h, "bag questions"): two digit planes per question,
+// the i8 scan, the selection state and the merge of the codes scan.  A chunk is sized so that its operands and its
+// selection state stay within the budget, never below one 32-question tile.
+struct ScanBag {
+  w2b_eval *e;
+  int32_t k;
+  TopkScratch t;
+  int64_t chunk, kk;
+  const unsigned long long *keys = nullptr;
+  ScanBag(w2b_eval *e_, int32_t k_) : e(e_), k(k_), kk(k_) {
+    t.k = k;
+    w2b_codes_topk_layout(e->words, (int)e->size, k, &t.nunits, &t.cap);
+    (void)t.chunk(0);                                                   // (sets per_q)
+    const int64_t per_q = t.per_q + 64 * ((e->size + 31) / 32);
+    const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+    chunk = budget / per_q / 32 * 32;
+    if (chunk < 32) chunk = 32;
+    if (chunk > kChunkQ) chunk = kChunkQ;
+  }
+  size_t scratch(int64_t n) const { return t.bytes(n); }
+  int before(int64_t n, int64_t np, const Bags &d);
+  hipError_t timed(int64_t n, int64_t, const Bags &d) {
+    return w2b_launch_bag_scan((const uint32_t *)e->B, (int)e->words, (int)e->size, e->codes ? 2 : 1, e->wrow, e->bag_T, d.d_wq,
+                               (int)n, d.d_x, d.exclude ? d.d_xoff : nullptr, k, t.bound, t.bkt, t.slots, t.cnt, t.merged,
+                               e->stream);
+  }
+  float score(unsigned long long key) const {
+    return e->codes ? f32_score(key) : (float)(int32_t)(key >> 32) / (float)e->size;   // bits: one correctly rounded division
+  }
+};
+
 struct EventPair {   // the two ends of a timed window
   hipEvent_t t[2] = {nullptr, nullptr};
   hipError_t create() {
@@ -879,10 +1036,42 @@ struct EventPair {   // the two ends of a timed window
       if (x) (void)hipEventDestroy(x);
   }
 };
+
+// The operands are built ahead of the scan's window, in a window of their own that is added to the kernel time: on a codes
+// handle the host has to see N_T between the two (wq = 1 / sqrt(N_T) in correctly rounded double operations, the
+// expression of w(r), which the host also builds).
+int ScanBag::before(int64_t n, int64_t, const Bags &d) {
+  const size_t tbytes = w2b_bag_operand_bytes((int)e->size, n);
+  if (eval_reserve_bag(&e->bag_T, &e->bag_T_bytes, tbytes) != W2B_OK) return efail(W2B_ENOMEM, "w2b_eval_bag: device allocation failed");
+  EHIP(hipMemsetAsync(e->tk_buf, 0, t.place(e->tk_buf, n), e->stream));
+  keys = t.merged;
+  EHIP(hipMemsetAsync(e->bag_T, 0, tbytes, e->stream));
+  EHIP(hipMemsetAsync(d.d_nt, 0, (size_t)d.np32 * 12, e->stream));     // N_T and wq
+  EventPair ev;
+  EHIP(ev.create());
+  EHIP(hipEventRecord(ev.t[0], e->stream));
+  EHIP(w2b_launch_bag_operands((const uint32_t *)e->B, (int)e->size, e->codes ? 2 : 1, (int)n, d.d_ids, d.d_off, e->bag_T, d.d_nt,
+                               e->stream));
+  EHIP(hipEventRecord(ev.t[1], e->stream));
+  std::vector<unsigned long long> nt((size_t)n, 0ull);
+  if (e->codes) EHIP(hipMemcpyAsync(nt.data(), d.d_nt, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+  EHIP(hipStreamSynchronize(e->stream));
+  float ms = 0;
+  EHIP(hipEventElapsedTime(&ms, ev.t[0], ev.t[1]));
+  e->kernel_ms += ms;
+  if (e->codes) {
+    std::vector<float> wq((size_t)n);
+    for (int64_t q = 0; q < n; q++) wq[(size_t)q] = bag_weight(nt[(size_t)q]);
+    EHIP(hipMemcpy(d.d_wq, wq.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  return W2B_OK;
+}
 }  // namespace
 
+// `terms` = accumulator tiles per (question, row) for the multiply-add count; 0 = what the handle's three-row scan has
 template <class Scan, class In>
-static int eval_scan_chunks(w2b_eval *e, Scan &&m, In in, int64_t nq, int32_t *best, float *bestd, const std::string &who) {
+static int eval_scan_chunks(w2b_eval *e, Scan &&m, In in, int64_t nq, int32_t *best, float *bestd, const std::string &who,
+                            double terms = 0) {
   std::vector<unsigned long long> keys;
   for (int64_t q0 = 0; q0 < nq; q0 += m.chunk) {
     const int64_t n = (nq - q0 < m.chunk) ? nq - q0 : m.chunk;
@@ -905,7 +1094,7 @@ static int eval_scan_chunks(w2b_eval *e, Scan &&m, In in, int64_t nq, int32_t *b
     if (le != hipSuccess) return efail(W2B_EHIP, who + ": " + hipGetErrorString(le));
     e->kernel_ms += ms;
     e->launches++;
-    e->macs += (e->codes ? 3.0 : 1.0) * (double)n * (double)e->words * (double)e->size;   // algorithmic: padding is not work
+    e->macs += (terms > 0 ? terms : e->codes ? 3.0 : 1.0) * (double)n * (double)e->words * (double)e->size;   // algorithmic: padding is not work
     for (int64_t i = 0; i < n * m.kk; i++) {
       const unsigned long long key = keys[(size_t)i];
       best[q0 * m.kk + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
@@ -954,6 +1143,30 @@ extern "C" int w2b_eval_combine(w2b_eval *e, int64_t nq, int32_t nt, const int32
   const Terms in{xr.data(), xs.data()};
   if (e->bits) return eval_scan_chunks(e, ScanBits(e, nq, k), in, nq, best, bestd, who);
   return eval_scan_chunks(e, ScanCombine(e, k), in, nq, best, bestd, who);
+}
+
+// The bag question: every check first -- those that need no handle, then the handle, then the ids -- and then the chunks.
+extern "C" int w2b_eval_bag(w2b_eval *e, int64_t n_ids, const int32_t *ids, int64_t nq, const int64_t *offsets,
+                            int32_t exclude_own, int32_t k, int32_t *best, float *bestd) {
+  const std::string who = "w2b_eval_bag";
+  if (nq < 0 || n_ids < 0 || (nq > 0 && (!offsets || !best)) || (n_ids > 0 && !ids)) return efail(W2B_EINVAL, who + ": bad argument");
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  if (exclude_own != 0 && exclude_own != 1) return efail(W2B_EINVAL, who + ": exclude_own must be 0 or 1");
+  if (nq == 0 ? n_ids != 0 : (offsets[0] != 0 || offsets[nq] != n_ids))
+    return efail(W2B_EINVAL, who + ": offsets must start at 0 and end at n_ids");
+  for (int64_t q = 0; q < nq; q++) {
+    if (offsets[q + 1] < offsets[q] || offsets[q + 1] > n_ids) return efail(W2B_EINVAL, who + ": offsets must not decrease");
+    if (offsets[q + 1] - offsets[q] > W2B_EVAL_MAX_BAG) return efail(W2B_EINVAL, who + ": a bag holds at most 4096 ids");
+  }
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": needs a bits or a codes handle");
+  if (e->size > kBagMaxSize) return efail(W2B_EINVAL, who + ": size must be at most 58254 (9 * 4096 * size < 2^31)");
+  for (int64_t i = 0; i < n_ids; i++)
+    if (ids[i] >= e->words) return efail(W2B_EINVAL, who + ": bag id out of range");
+  if (nq == 0) return W2B_OK;
+  EHIP(hipSetDevice(e->device));
+  Bags in{ids, offsets, exclude_own == 1};
+  return eval_scan_chunks(e, ScanBag(e, k), std::move(in), nq, best, bestd, who, 2.0);
 }
 
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
@@ -1251,6 +1464,47 @@ extern "C" int w2b_eval_combine_text(w2b_eval *e, const char *queries, int64_t l
     if (rc != W2B_OK) return rc;
   }
   return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_combine_text", out, out_len);
+}
+
+// the bag form: every non-empty line is one bag of 1 to W2B_EVAL_MAX_BAG words
+extern "C" int w2b_eval_bag_text(w2b_eval *e, const char *queries, int64_t len, int32_t exclude_own, int32_t k, char **out,
+                                 int64_t *out_len) {
+  if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_bag_text: bad argument");
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_bag_text: k must be 1..64");
+  if (exclude_own != 0 && exclude_own != 1) return efail(W2B_EINVAL, "w2b_eval_bag_text: exclude_own must be 0 or 1");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, "w2b_eval_bag_text: needs a bits or a codes handle");
+  *out = nullptr;
+  std::vector<QueryLine> lines;
+  std::vector<int32_t> ids;
+  std::vector<int64_t> offsets(1, 0);
+  std::vector<std::string> tok;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
+    if (tok.empty()) continue;
+    QueryLine ln{joined(tok), std::string(), -1};
+    if (tok.size() > W2B_EVAL_MAX_BAG) ln.error = "expected 1 to 4096 words";
+    const size_t at = ids.size();
+    for (size_t i = 0; i < tok.size() && ln.error.empty(); i++) {
+      const int64_t row = w2b_eval_lookup(e, tok[i].c_str());
+      if (row == e->words) ln.error = "not in vocabulary: " + tok[i];
+      ids.push_back((int32_t)row);
+    }
+    if (ln.error.empty()) {
+      ln.q = (int64_t)offsets.size() - 1;
+      offsets.push_back((int64_t)ids.size());
+    } else {
+      ids.resize(at);
+    }
+    lines.push_back(ln);
+  }
+  const size_t nq = offsets.size() - 1;
+  std::vector<int32_t> best(nq * (size_t)k);
+  std::vector<float> bestd(nq * (size_t)k);
+  if (nq > 0) {
+    const int rc = w2b_eval_bag(e, (int64_t)ids.size(), ids.data(), (int64_t)nq, offsets.data(), exclude_own, k, best.data(),
+                                bestd.data());
+    if (rc != W2B_OK) return rc;
+  }
+  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_bag_text", out, out_len);
 }
 
 extern "C" void w2b_eval_free_text(char *text) { free(text); }

@@ -196,6 +196,20 @@ hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const fl
                                  int nq, const int *b1, const int *b2, const int *b3, int k, unsigned long long *best,
                                  unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
                                  unsigned long long *out, hipStream_t s);
+// The bag question on bit-packed rows (w2b_kernels_evalbag.hip; include/word2bits_eval.h, "bag questions").  bitlevel 1: B =
+// the 1-bit rows (nw = 2 * ceil(dim / 64) halves), 2: the 2-bit rows and wrow as above.  ids / off = the chunk's bags, off
+// [nq + 1] rebased to ids[0]; T = the two digit planes of the pooled vectors in fragment order (w2b_bag_operand_bytes, ZEROED
+// by the caller), NT[nq] (zeroed; bitlevel 2 only) receives sum_a T[a]^2.  The scan: Wq = the questions' weights [32 *
+// ceil(nq / 32)] (bitlevel 2; 0 = no answers), xrows / xoff = every question's own rows, ascending without repeats, and
+// their bounds [nq + 1], or xoff = nullptr when nothing is excluded; bound / bkt / keys / cnt = the zeroed selection state
+// sized by w2b_codes_topk_layout, out[q * k + j] the j-th best key (score bits << 32 | ~row; bitlevel 1: score bits = J).
+size_t w2b_bag_operand_bytes(int dim, long long nq);
+hipError_t w2b_launch_bag_operands(const uint32_t *B, int dim, int bitlevel, int nq, const int *ids, const int *off, void *T,
+                                   unsigned long long *NT, hipStream_t s);
+hipError_t w2b_launch_bag_scan(const uint32_t *B, int words, int dim, int bitlevel, const float *wrow, const void *T,
+                               const float *Wq, int nq, const int *xrows, const int *xoff, int k, unsigned long long *bound,
+                               unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt, unsigned long long *out,
+                               hipStream_t s);
 // the packed embedding layer (w2b_kernels_embed.hip; include/word2bits_embed.h).  T = the packed table [rows][wpr], ids /
 // offsets = int64 device buffers, `bad` = the device counter of ignored ids and clamped bags.  A bag launch needs
 // w2b_embed_bag_scratch(...) bytes of device scratch (it zeroes them itself).

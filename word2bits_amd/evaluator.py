@@ -6,8 +6,10 @@
     ev = Evaluator("vectors.w2bp", bits=True)                        # 1-bit model kept packed: the exact integer scan
     rows, scores = ev.neighbors([ev.lookup(b"KING")], 10)
     ev = Evaluator("vectors2.w2bp", codes=True)                      # 2-bit model kept packed: the i8 matrix-core scan
+    rows, scores = ev.bag([3, 17, 4, 9, 9], [0, 2, 5], 10)           # two bags of rows pooled: nearest to each sum
 
-The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip);
+The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip,
+w2b_kernels_evalbag.hip);
 there is no CPU path in this module.
 """
 import ctypes as C
@@ -161,6 +163,22 @@ class Evaluator:
     def combine_text(self, queries, k):
         """stdout of `nearest FILE k ... signed < queries` as bytes: every line is 1 to 7 tokens +WORD, -WORD or WORD."""
         return self._text(self._L.w2b_eval_combine_text, queries, int(k))
+
+    def bag(self, ids, offsets, k, exclude_own=True):
+        """The bag question (w2b_eval_bag; bits and codes handles): question q is the rows ids[offsets[q]:offsets[q + 1]]
+        pooled into one integer vector -- any number of rows up to 4096, an id < 0 is padding, a repeated row adds.  Returns
+        (rows int32 [nq, k], scores float32 [nq, k]) in the order of topk.  `exclude_own=True` keeps the bag's own rows out of
+        its answers (as combine does); False asks for them too (the words nearest to a document, its own included)."""
+        ids, offsets = np.ascontiguousarray(ids, np.int32).ravel(), np.ascontiguousarray(offsets, np.int64).ravel()
+        nq, k = max(len(offsets) - 1, 0), int(k)
+        best, bestd = np.empty((nq, max(k, 0)), np.int32), np.empty((nq, max(k, 0)), np.float32)
+        _lib.check(self._L.w2b_eval_bag(self._h, len(ids), ids.ctypes.data_as(_lib.i32p), nq, offsets.ctypes.data_as(_lib.i64p),
+                                        int(exclude_own), k, best.ctypes.data_as(_lib.i32p), bestd.ctypes.data_as(_lib.f32p)))
+        return best, bestd
+
+    def bag_text(self, queries, k, exclude_own=True):
+        """stdout of `nearest FILE k ... bits|codes bag < queries` as bytes: every line is one bag of 1 to 4096 words."""
+        return self._text(self._L.w2b_eval_bag_text, queries, int(exclude_own), int(k))
 
     def nearest_text(self, queries, k):
         """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
