@@ -115,6 +115,16 @@ float w2bo_keep_prob(long long cn, float sample, long long train_words) {
 
 /* ------------------------------------------------------------------ one centre word */
 
+/* For the tests: the regularisation terms (reg * sum q^2, ref :445 and :471) that single-worker runs (num_threads == 1, so
+ * nobody races on it) have booked into the losses they returned since the last reset -- the part of an epoch loss that
+ * -reg is responsible for, which the loss alone does not show. */
+static double reg_booked;
+double w2bo_reg_terms(int reset) {
+  double r = reg_booked;
+  if (reset) reg_booked = 0;
+  return r;
+}
+
 /* ref :426-503, with the context rows and the target rows already chosen. */
 double w2bo_center_update(w2bo_model *m, const int *ctx, int cw, const int *targets,
                           const int *labels, int nt, float alpha, float *scratch) {
@@ -137,6 +147,7 @@ double w2bo_center_update(w2bo_model *m, const int *ctx, int cw, const int *targ
     }
     rl = reg * rl;
     loss += -rl;
+    if (m->num_threads == 1) reg_booked += rl;
   }
   for (long long c = 0; c < D; c++) havg[c] /= cw;
   /* phase B, ref :450-492 */
@@ -157,6 +168,7 @@ double w2bo_center_update(w2bo_model *m, const int *ctx, int cw, const int *targ
       float dp = (float)(f * pow(-1, 1 - label));
       float ll = logf(w2bo_sigmoid(dp));
       loss += ll - rl;
+      if (m->num_threads == 1) reg_booked += rl;
     }
     for (long long c = 0; c < D; c++) herr[c] += g * w2bo_quantize(row[c], bl);
     for (long long c = 0; c < D; c++) row[c] += g * havg[c] - 2 * alpha * reg * row[c];

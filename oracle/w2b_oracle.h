@@ -63,6 +63,11 @@ double w2bo_center_update(w2bo_model *m, const int *ctx, int cw,
                           const int *targets, const int *labels, int nt,
                           float alpha, float *scratch);
 
+/* Test support: the sum of the regularisation terms (reg * sum q^2) that runs
+ * with num_threads == 1 have booked into their losses since the last call with
+ * reset != 0. */
+double w2bo_reg_terms(int reset);
+
 /* A batch of explicit tuples, applied strictly in order (serial semantics).
  * ctx_off is CSR [n+1]; neg is [n*negative] with -1 meaning "skipped draw"
  * (target == word, src/word2bits.cpp:458).  Returns summed loss. */

@@ -4,7 +4,7 @@ w2b_device.hpp load_col/store_col; the `MM + 8` instantiations of the sentence-r
 Three layers:
   1. the bit-exact parity tests of the small-table form re-run with w2b_tuning.force_row_desc = 1 (selects the
      large-table form on any table size; `./word2bits -row-desc 1`) -- tuple form, plain worker kernel,
-     sentence-resident kernel;
+     sentence-resident kernel (also with -reg and the generic quantizer: tests/test_gpu_resident_flags.py);
   2. a genuine > 2 GiB table (V = 700 000 x D = 800: 2.24 GB per table) -- collision-free tuple batch against the
      oracle on the touched rows (bit-exact in parity mode, rounding-tight in the fast mode), every other row still
      holding its InitNet bits, and sentence-resident == plain worker kernel bit for bit on the whole 4.5 GB model;
@@ -19,6 +19,7 @@ import word2bits_amd as w2b
 from w2b_testlib import OracleState
 
 import test_gpu_exact
+import test_gpu_resident_flags
 import test_gpu_worker
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +57,16 @@ def test_resident_equals_plain_single_worker_row_desc(gpu, row_desc, D, window, 
 def test_resident_equals_plain_many_workers_row_desc(gpu, row_desc, threads, size, window, bitlevel, tmp_path):
     test_gpu_worker.test_sentence_resident_kernel_equals_plain_kernel_many_workers(gpu, threads, size, window, bitlevel,
                                                                                    tmp_path)
+
+
+@pytest.mark.parametrize("D,window,negative,bitlevel,hot", [(200, 8, 24, 1, 0), (768, 12, 5, 1, 0)])
+def test_resident_equals_plain_with_regularisation_row_desc(gpu, row_desc, D, window, negative, bitlevel, hot):
+    test_gpu_resident_flags.test_resident_equals_plain_with_regularisation(gpu, D, window, negative, bitlevel, hot)
+
+
+@pytest.mark.parametrize("D,window,negative,bitlevel,reg", [(64, 2, 3, 4, 0.0), (200, 8, 24, 4, 1e-3)])
+def test_resident_equals_plain_generic_quantizer_row_desc(gpu, row_desc, D, window, negative, bitlevel, reg):
+    test_gpu_resident_flags.test_resident_equals_plain_generic_quantizer(gpu, D, window, negative, bitlevel, reg)
 
 
 # ------------------------------------------------------------------------------- helpers for genuine big tables

@@ -5,7 +5,8 @@ producer wavefront and lets an adder wavefront issue the lossless adds to the fr
 SCHEDULE of the same arithmetic: the window average is summed in window order, the error in target order, the dot product
 uses the plain kernel's tree, repeated target rows are taken again after their first update.  So with one worker -- and
 with several workers that never share a row -- it must leave the plain kernel's bits: u, v, word count, alpha, epoch loss.
-The plain kernel in turn is pinned to the oracle / the unmodified reference (tests/test_gpu_exact.py, test_gpu_worker.py)."""
+The plain kernel in turn is pinned to the oracle / the unmodified reference (tests/test_gpu_exact.py, test_gpu_worker.py) -- with
+-reg != 0 and bitlevel 4 / 8 as well (test_gpu_worker.py test_single_worker_short_horizon_tight_reg_and_generic_quantizer)."""
 import os
 import subprocess
 
@@ -70,7 +71,8 @@ def test_row_group_kernel_equals_plain_kernel_single_worker(gpu, D, window, nega
 @pytest.mark.parametrize("D,bitlevel,knobs", [(200, 1, dict()), (400, 2, dict(atomic_rank=149, atomic_rank_u=149)), (800, 0, dict())])
 def test_row_group_kernel_with_regularisation(gpu, D, bitlevel, knobs):
     """-reg != 0: the delta of a context row depends on the row (the data wavefronts do those adds themselves) and the
-    reg * sum q^2 terms of the loss are summed per group -- values bit-identical, loss up to the order of the additions"""
+    reg * sum q^2 terms of the loss are summed per group -- values bit-identical, loss up to the order of the additions.  (The
+    plain kernel meets the oracle with -reg at these row widths in test_gpu_worker.py.)"""
     V, n = 150, 5000
     rng = np.random.default_rng(5)
     ids = token_stream(rng, V, n)

@@ -28,11 +28,11 @@ def drift(a, b):
     return float(np.abs(a - b).mean()), float(np.mean(np.signbit(a) != np.signbit(b)))
 
 
-def setup(V, ids, D, window, negative, bitlevel, sample, iters, num_threads=1, fma=False):
+def setup(V, ids, D, window, negative, bitlevel, sample, iters, num_threads=1, fma=False, reg=0.0):
     cn = counts_of(ids, V)
     tw = int(cn.sum())
     o = OracleState(cn, D, window=window, negative=negative, bitlevel=bitlevel, num_threads=num_threads,
-                    iters=iters, sample=sample, table_size=50000, fma=fma)
+                    iters=iters, sample=sample, reg=reg, table_size=50000, fma=fma)
     o.m.train_words = tw
     return cn, tw, o
 
@@ -48,26 +48,33 @@ def setup(V, ids, D, window, negative, bitlevel, sample, iters, num_threads=1, f
 def test_single_worker_short_horizon_tight(gpu, bitlevel, sample, D, window, negative, window_cache):
     """3000 positions over a 5000-word vocabulary: rows are rarely revisited, so the worker form
     (on-device sentence reader / window / negative draws / alpha) must track the oracle closely."""
+    short_horizon_tight(bitlevel, sample, D, window, negative, window_cache)
+
+
+def short_horizon_tight(bitlevel, sample, D, window, negative, window_cache, reg=0.0, kernel=None):
     V, n = 5000, 3000
     rng = np.random.default_rng(4)
     ids = token_stream(rng, V, n)
-    cn, tw, o = setup(V, ids, D, window, negative, bitlevel, sample, 1)
-    _, _, y = setup(V, ids, D, window, negative, bitlevel, sample, 1, fma=True)
-    t = w2b.Trainer(V, D, window, negative, bitlevel, num_threads=1, iter=1, sample=sample, train_words=tw,
+    cn, tw, o = setup(V, ids, D, window, negative, bitlevel, sample, 1, reg=reg)
+    _, _, y = setup(V, ids, D, window, negative, bitlevel, sample, 1, fma=True, reg=reg)
+    t = w2b.Trainer(V, D, window, negative, bitlevel, num_threads=1, iter=1, sample=sample, reg=reg, train_words=tw,
                     window_cache=window_cache)
     t.set_model(o.u, o.v)
     t.set_vocab_counts(cn, 50000)
     t.set_corpus(ids)
     t.set_shards(np.zeros(1, np.int64))
+    assert kernel is None or t.worker_kernel_name() == kernel
     lo = o.train_epoch_tokens(ids, np.zeros(1, np.int64))
     y.train_epoch_tokens(ids, np.zeros(1, np.int64))
     lg = t.train_epoch(positions_per_launch=501)
     fin, wca, alpha, _ = t.epoch_status()
     assert fin and wca == o.m.word_count_actual and np.float32(alpha) == np.float32(o.m.alpha)
     u, v = t.get_model()
+    print("SHORT b=%d D=%d reg=%g wc=%d: loss gpu %.6f oracle %.6f" % (bitlevel, D, reg, window_cache, lg, lo))
     for got, ref, yard in ((u, o.u, y.u), (v, o.v, y.v)):
         gm, gs = drift(got, ref)
         ym, ys = drift(yard, ref)
+        print("SHORT   drift gpu %.3g / %.3g  fma build %.3g / %.3g" % (gm, gs, ym, ys))
         # no farther than 3x the reference's own FMA build; the floor covers the case where the yardstick
         # run happened to see no level flip at all (a single flip of a quantized level moves ~1e-3 mean)
         floor = 1e-5 if bitlevel == 0 else 2e-3
@@ -75,6 +82,47 @@ def test_single_worker_short_horizon_tight(gpu, bitlevel, sample, D, window, neg
         assert gs <= 3 * ys + 2e-3, (gs, ys)
     assert lg == pytest.approx(lo, rel=2e-3)
     t.close()
+    o.loss = lo
+    return o
+
+
+LOSS_REL_TIGHT = 2e-3        # the epoch-loss tolerance of short_horizon_tight
+RAISED = (1e-2, 3e-2)        # -reg at which the regularisation terms are at least 100 x that tolerance of the epoch loss
+
+
+@pytest.mark.parametrize("bitlevel,sample,D,window,negative,reg", [
+    (1, 0.0, 200, 8, 24, 1e-3),
+    (2, 0.0, 100, 3, 7, 1e-3),
+    (0, 1e-3, 200, 8, 24, 1e-3),
+    (4, 0.0, 64, 5, 5, 0.0),
+    (8, 1e-3, 200, 8, 24, 1e-3),
+    # every -reg case again with -reg raised until the loss check can see the terms (below): one per quantizer form
+    (1, 0.0, 200, 8, 24, 1e-2),
+    (2, 0.0, 100, 3, 7, 3e-2),
+    (0, 1e-3, 200, 8, 24, 3e-2),
+    (8, 1e-3, 200, 8, 24, 3e-2),
+])
+@pytest.mark.parametrize("window_cache", [True, False])
+def test_single_worker_short_horizon_tight_reg_and_generic_quantizer(gpu, bitlevel, sample, D, window, negative, reg, window_cache):
+    """test_single_worker_short_horizon_tight with -reg != 0 and with the run-time quantizer (bitlevel 4 and 8): BOTH worker
+    kernels meet the oracle directly here, so the bit-for-bit comparisons between them (test_gpu_resident_flags.py,
+    test_gpu_groups.py) hang on a pinned anchor for these flags too.  Same yardstick: integer bookkeeping exact, values no
+    farther from the bit-reference than 3x its own FMA build (plus the floors), epoch loss to 2e-3.
+
+    What the loss check sees of the regularisation is the share of the oracle's epoch loss that the terms reg * sum q^2 make
+    up -- the oracle counts what it books (w2bo_reg_terms).  At -reg 1e-3 that share is 4.2 / 1.5 / 3.7 / 3.6 % (bitlevel
+    1 / 2 / 0 / 8): 8-21 x the tolerance, so the loss shows an error of 5-13 % of the terms there and the values carry the
+    rest; those cases only print it.  Each has a twin at the same shape with -reg raised (1e-2 at bitlevel 1, 3e-2 at the
+    others: 31 / 29 / 51 / 51 %), where the share is ASSERTED to be at least 100 x the tolerance: a term booked 1 % wrong
+    moves the loss out of it.  The drift yardstick holds as it stands there, the FMA build runs with the same -reg."""
+    o = short_horizon_tight(bitlevel, sample, D, window, negative, window_cache, reg=reg,
+                            kernel="resident" if window_cache else "plain")
+    if reg:
+        share = o.reg_terms / abs(o.loss)
+        print("SHORT   regularisation terms %.6g = %.3g of the oracle's epoch loss" % (o.reg_terms, share))
+        assert 0.0 < share < 1.0
+        if reg in RAISED:
+            assert share >= 100 * LOSS_REL_TIGHT
 
 
 @pytest.mark.parametrize("bitlevel,sample,D,window,negative", [

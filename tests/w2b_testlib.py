@@ -79,6 +79,8 @@ def oracle(fma=False):
     L.w2bo_center_update.restype = C.c_double
     L.w2bo_center_update.argtypes = [C.POINTER(OracleModel), c_i32p, C.c_int, c_i32p, c_i32p, C.c_int,
                                      C.c_float, c_f32p]
+    L.w2bo_reg_terms.restype = C.c_double
+    L.w2bo_reg_terms.argtypes = [C.c_int]
     L.w2bo_train_tuples.restype = C.c_double
     L.w2bo_train_tuples.argtypes = [C.POINTER(OracleModel), C.c_longlong, c_i32p, c_i32p, c_i32p, c_i32p,
                                     C.c_float]
@@ -155,8 +157,85 @@ class OracleState:
         ids = np.ascontiguousarray(ids, np.int32)
         starts = np.ascontiguousarray(starts, np.int64)
         ov = None if overrides is None else np.ascontiguousarray(overrides, np.int32)
-        return self.L.w2bo_train_epoch_tokens(C.byref(self.m), iptr(ids), len(ids), lptr(starts),
+        self.L.w2bo_reg_terms(1)
+        loss = self.L.w2bo_train_epoch_tokens(C.byref(self.m), iptr(ids), len(ids), lptr(starts),
                                               None if ov is None else iptr(ov), len(starts))
+        self.reg_terms = self.L.w2bo_reg_terms(1)      # of this epoch, one worker only: what -reg booked into `loss`
+        return loss
+
+
+# ----------------------------------------------------------------------------- what a worker visits
+
+def walk(ids, cn, window, negative, sample, table_size=50000, max_sentence=1000):
+    """Host restatement of what ONE reference worker (thread id 0) visits on a token stream (ref :368-509: sub-sampling,
+    window draw, negative draws -- the LCG ledger, no arithmetic on rows).  Returns (positions trained, positions whose
+    context list holds a word twice, context rows visited, target rows visited)."""
+    L = oracle()
+    cn = np.ascontiguousarray(cn, np.int64)
+    tw, nv = int(cn.sum()), len(cn)
+    table = np.zeros(table_size, np.int32)
+    if negative > 0:
+        L.w2bo_build_unigram_table(lptr(cn), nv, iptr(table), table_size)
+    table = table.tolist()
+    keep = [float(L.w2bo_keep_prob(int(c), sample, tw)) if sample > 0 else 2.0 for c in cn.tolist()]
+    toks = ids.tolist()
+    A, Cc, M = 25214903917, 11, (1 << 64) - 1
+    rng, pos, n = 0, 0, len(toks)
+    sen, spos = [], 0
+    trained = dups = rows_u = rows_v = 0
+    while True:
+        if not sen:
+            eof = False
+            while True:
+                if pos >= n:
+                    eof = True
+                    break
+                w = toks[pos]
+                pos += 1
+                if w == 0:
+                    break
+                if sample > 0:
+                    rng = (rng * A + Cc) & M
+                    if keep[w] < (rng & 0xFFFF) / 65536.0:
+                        continue
+                sen.append(w)
+                if len(sen) >= max_sentence:
+                    break
+            spos = 0
+            if eof:
+                break
+        rng = (rng * A + Cc) & M
+        b = rng % window
+        word = sen[spos] if sen else 0
+        ctx = [sen[c] for c in range(spos - window + b, spos + window - b + 1) if c != spos and 0 <= c < len(sen)]
+        if ctx:
+            nt = 1
+            for _ in range(negative):
+                rng = (rng * A + Cc) & M
+                t = table[(rng >> 16) % table_size]
+                if t == 0:
+                    t = rng % (nv - 1) + 1
+                nt += t != word
+            trained += 1
+            dups += len(set(ctx)) < len(ctx)
+            rows_u += len(ctx)
+            rows_v += nt
+        spos += 1
+        if spos >= len(sen):
+            sen = []
+    return trained, dups, rows_u, rows_v
+
+
+def row_sumsq_floor(bitlevel, *tables):
+    """smallest sum of q^2 over a row (row 0, "</s>", is never visited) among the given tables"""
+    L = oracle()
+    lo = np.inf
+    for tab in tables:
+        x = np.ascontiguousarray(tab[1:], np.float32)
+        q = np.empty_like(x)
+        L.w2bo_quantize_array(fptr(x), fptr(q), x.size, bitlevel)
+        lo = min(lo, float((q.astype(np.float64) ** 2).sum(axis=1).min()))
+    return lo
 
 
 # ----------------------------------------------------------------------------- corpora
