@@ -6,7 +6,10 @@ SCHEDULE of the same arithmetic: the window average is summed in window order, t
 uses the plain kernel's tree, repeated target rows are taken again after their first update.  So with one worker -- and
 with several workers that never share a row -- it must leave the plain kernel's bits: u, v, word count, alpha, epoch loss.
 The plain kernel in turn is pinned to the oracle / the unmodified reference (tests/test_gpu_exact.py, test_gpu_worker.py) -- with
--reg != 0 and bitlevel 4 / 8 as well (test_gpu_worker.py test_single_worker_short_horizon_tight_reg_and_generic_quantizer)."""
+-reg != 0 and bitlevel 4 / 8 as well (test_gpu_worker.py test_single_worker_short_horizon_tight_reg_and_generic_quantizer), and so
+is the row-group kernel itself (the "against the ORACLE, directly" tests below).  The flags and shapes this file leaves out
+(compute_loss off, -reg beyond three cells, windows above 8 at two and four wavefronts per row, row lengths that leave a
+wavefront idle, the refreshed read copies bit for bit) are in tests/test_gpu_groups_flags.py."""
 import os
 import subprocess
 
@@ -15,7 +18,7 @@ import pytest
 
 import word2bits_amd as w2b
 from w2b_testlib import ROOT, zipf_ids, write_disjoint_shard_corpus
-from test_gpu_worker import token_stream, counts_of
+from test_gpu_worker import token_stream, counts_of, short_horizon_tight, REG_AND_GENERIC_CASES, RAISED, LOSS_REL_TIGHT
 
 pytestmark = pytest.mark.gpu
 
@@ -200,6 +203,22 @@ def test_row_group_kernel_single_worker_short_horizon_against_oracle(gpu, bitlev
         assert gs <= 3 * ys + 2e-3, (gs, ys)
     assert lg == pytest.approx(lo, rel=2e-3)
     t.close()
+
+
+@pytest.mark.parametrize("bitlevel,sample,D,window,negative,reg", REG_AND_GENERIC_CASES)
+def test_row_group_kernel_short_horizon_tight_reg_and_generic_quantizer(gpu, bitlevel, sample, D, window, negative, reg):
+    """test_gpu_worker.py test_single_worker_short_horizon_tight_reg_and_generic_quantizer with the row-group kernel selected: with
+    -reg != 0 and with the run-time quantizer (bitlevel 4 / 8) this kernel meets the oracle itself, not only through its bit
+    comparisons with the plain kernel.  The same function, so the same yardstick (integer bookkeeping exact, values within 3x
+    the oracle's own FMA build plus the floors, epoch loss to 2e-3) and the same share assertions: the regularisation terms
+    the oracle booked are a real part of its loss, and at the raised -reg values at least 100 x the loss tolerance."""
+    o = short_horizon_tight(bitlevel, sample, D, window, negative, False, reg=reg, row_groups=True, kernel="groups")
+    if reg:
+        share = o.reg_terms / abs(o.loss)
+        print("GROUPS SHORT   regularisation terms %.6g = %.3g of the oracle's epoch loss" % (o.reg_terms, share))
+        assert 0.0 < share < 1.0
+        if reg in RAISED:
+            assert share >= 100 * LOSS_REL_TIGHT
 
 
 @pytest.mark.parametrize("bitlevel,sample,D,window,negative", [

@@ -51,14 +51,14 @@ def test_single_worker_short_horizon_tight(gpu, bitlevel, sample, D, window, neg
     short_horizon_tight(bitlevel, sample, D, window, negative, window_cache)
 
 
-def short_horizon_tight(bitlevel, sample, D, window, negative, window_cache, reg=0.0, kernel=None):
+def short_horizon_tight(bitlevel, sample, D, window, negative, window_cache, reg=0.0, kernel=None, row_groups=None):
     V, n = 5000, 3000
     rng = np.random.default_rng(4)
     ids = token_stream(rng, V, n)
     cn, tw, o = setup(V, ids, D, window, negative, bitlevel, sample, 1, reg=reg)
     _, _, y = setup(V, ids, D, window, negative, bitlevel, sample, 1, fma=True, reg=reg)
     t = w2b.Trainer(V, D, window, negative, bitlevel, num_threads=1, iter=1, sample=sample, reg=reg, train_words=tw,
-                    window_cache=window_cache)
+                    window_cache=window_cache, row_groups=row_groups)
     t.set_model(o.u, o.v)
     t.set_vocab_counts(cn, 50000)
     t.set_corpus(ids)
@@ -90,7 +90,7 @@ LOSS_REL_TIGHT = 2e-3        # the epoch-loss tolerance of short_horizon_tight
 RAISED = (1e-2, 3e-2)        # -reg at which the regularisation terms are at least 100 x that tolerance of the epoch loss
 
 
-@pytest.mark.parametrize("bitlevel,sample,D,window,negative,reg", [
+REG_AND_GENERIC_CASES = [      # (bitlevel, sample, D, window, negative, reg); test_gpu_groups.py runs them with the row-group kernel
     (1, 0.0, 200, 8, 24, 1e-3),
     (2, 0.0, 100, 3, 7, 1e-3),
     (0, 1e-3, 200, 8, 24, 1e-3),
@@ -101,7 +101,10 @@ RAISED = (1e-2, 3e-2)        # -reg at which the regularisation terms are at lea
     (2, 0.0, 100, 3, 7, 3e-2),
     (0, 1e-3, 200, 8, 24, 3e-2),
     (8, 1e-3, 200, 8, 24, 3e-2),
-])
+]
+
+
+@pytest.mark.parametrize("bitlevel,sample,D,window,negative,reg", REG_AND_GENERIC_CASES)
 @pytest.mark.parametrize("window_cache", [True, False])
 def test_single_worker_short_horizon_tight_reg_and_generic_quantizer(gpu, bitlevel, sample, D, window, negative, reg, window_cache):
     """test_single_worker_short_horizon_tight with -reg != 0 and with the run-time quantizer (bitlevel 4 and 8): BOTH worker

@@ -166,10 +166,12 @@ class OracleState:
 
 # ----------------------------------------------------------------------------- what a worker visits
 
-def walk(ids, cn, window, negative, sample, table_size=50000, max_sentence=1000):
+def walk(ids, cn, window, negative, sample, table_size=50000, max_sentence=1000, dup_words=None):
     """Host restatement of what ONE reference worker (thread id 0) visits on a token stream (ref :368-509: sub-sampling,
     window draw, negative draws -- the LCG ledger, no arithmetic on rows).  Returns (positions trained, positions whose
-    context list holds a word twice, context rows visited, target rows visited)."""
+    context list holds a word twice, context rows visited, target rows visited).  `dup_words`, a dict, is filled with
+    {word: positions whose context list holds THAT word more than once} -- which rows the order-dependent update of
+    ref :494-503 really meets."""
     L = oracle()
     cn = np.ascontiguousarray(cn, np.int64)
     tw, nv = int(cn.sum()), len(cn)
@@ -218,6 +220,9 @@ def walk(ids, cn, window, negative, sample, table_size=50000, max_sentence=1000)
                 nt += t != word
             trained += 1
             dups += len(set(ctx)) < len(ctx)
+            if dup_words is not None and len(set(ctx)) < len(ctx):
+                for w in {w for w in ctx if ctx.count(w) > 1}:
+                    dup_words[w] = dup_words.get(w, 0) + 1
             rows_u += len(ctx)
             rows_v += nt
         spos += 1
