@@ -256,6 +256,59 @@ int w2b_eval_bag_text(w2b_eval *e, const char *queries, int64_t len, int32_t exc
 int w2b_bag_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel,
                         int64_t n, const int32_t *ids, int32_t *J_out, float *score_out);
 
+/* ---- vector questions: the rows nearest to a float vector, on all three handle kinds --------------------------------------
+ * "Which words are nearest to this vector?" -- word2vec's `distance`, gensim's similar_by_vector -- for a vector that the
+ * caller computed itself: a hidden state, a projected sentence, an average with its own weights, a vector of another model of
+ * the same width.  Every other question of this header is spelled in row ids; this one is `size` floats, and a packed table is
+ * never expanded to answer it.
+ *   input: x[q][0 .. size) is question q, in host memory.  Every value must be finite and either 0 or have 2^-60 <= |x| <=
+ *     2^60; anything else is W2B_EINVAL, naming the question and the column.  The reason: within that range no product,
+ *     partial sum or weight below is subnormal, and none overflows, for any `size` the handles allow (the terms x[a] * t are
+ *     multiples of 2^-83 of at most 3 * 2^60, so a partial sum is 0 or between 2^-83 and 2^86; sum x^2 is 0 or between 2^-120
+ *     and 2^144) -- so the result does not depend on how an instruction treats subnormals.  normalize is 0 or 1, k is in 1 ..
+ *     W2B_EVAL_MAX_K, nq == 0 is W2B_OK.  Nothing is excluded from the answers: there are no "own rows".
+ *   query weight: nx = sum_a (double)x[a] * (double)x[a] in column order, the products exact in double, every add rounded on
+ *     its own.  normalize == 1: wx = (float)(1.0 / sqrt(nx)) -- the double square root and the double division each correctly
+ *     rounded, the result rounded to float: the expression of w(r) in codes mode; normalize == 0: wx = 1.0f.  A question with
+ *     nx == 0 has the empty list (row -1 / score 0 throughout), whatever normalize is.  wx is built on the host, as w2b_eval_bag
+ *     builds wq.
+ *   fp32 handle: vec[a] = x[a] * wx, one float32 multiply per column (exact when wx is 1), and the score of row c is the chain
+ *     that w2b_eval_topk runs on that vec, in the handle's `fused` mode and w2b_eval_set_kernel variant.  So with normalize = 0
+ *     and x equal to (M[b2] - M[b1]) + M[b3] computed in float32 the scores are bit for bit those of w2b_eval_topk(b1, b2, b3).
+ *   bits and codes handles: S(c) in float32 is  acc = +0;  for a = 0 .. size - 1: acc = fmaf(x[a], (float)t_c[a], acc)  -- strictly
+ *     sequential in a, one accumulator per (question, row); t = +-1 on a bits handle, t in {+-1, +-3} on a codes handle;
+ *     (float)t is exact, so on bits rows every step is one rounded add -- and
+ *         score = (S * wx) * w(c),
+ *     both multiplies rounded on their own, nothing contracted.  w(c) on a codes handle is the table of codes mode; on a bits
+ *     handle it is the constant (float)(1.0 / sqrt((double)size)), the same expression.  The scan runs on the f32 matrix cores,
+ *     whose accumulators are exactly such chains, with the row operand decoded from the packed bits in registers
+ *     (word2bits_amd/csrc/w2b_kernels_evalvec.hip).
+ *   answers: the rows with score > 0, by score descending, equal float scores in ascending row order -- the codes key, score
+ *     bits << 32 | ~row -- on all three handle kinds.  best / bestd are [nq][k] in the shape of w2b_eval_topk: a short list ends
+ *     in row -1 / score 0, bestd may be NULL.
+ * Everything is validated before anything is launched -- k, normalize and nq first (so a NULL handle with a bad k is W2B_EINVAL
+ * for the k, as in w2b_eval_bag; the text form checks k and normalize before its handle too), then the handle, then the values -- with the cause in w2b_last_error(); on error best / bestd
+ * are untouched.
+ * w2b_eval_set_topk_scratch bounds the scratch of a launch (the uploaded vectors and their operands, about 8 * size bytes per
+ * question, plus the selection slots); a chunk is never smaller than 32 questions (fp32 handle: 128, as w2b_eval_topk), and
+ * results never depend on it.  w2b_eval_timing_read counts these launches (packed handles: operands + scan + merge), macs =
+ * questions x rows x size. */
+int w2b_eval_vectors(w2b_eval *e, int64_t nq, const float *x /* [nq][size], host */, int32_t normalize,
+                     int32_t k, int32_t *best, float *bestd);
+/* The text form of `./nearest ... vector`: every non-empty line is `size` numbers separated by white space, each parsed with
+ * strtof in the C locale.  The head of an answer is "vector <i>", where i counts the non-empty lines from 1; the answer has the
+ * format of w2b_eval_nearest_text.  Error lines: "vector <i>: expected <size> numbers\n" (another count, or a token that is
+ * no number) and "vector <i>: value out of range\n" (a value that w2b_eval_vectors refuses).  All valid lines are scored in
+ * one w2b_eval_vectors batch. */
+int w2b_eval_vectors_text(w2b_eval *e, const char *queries, int64_t len, int32_t normalize, int32_t k,
+                          char **out, int64_t *out_len);
+/* Host twin of the vector kernels (pure C, explicit fmaf, no device): ONE question x[dim] scored against EVERY row c of
+ * packed[words][bitlevel * ceil(dim / 64)], bitlevel 1 (the bits semantics above) or 2 (codes): S_out[words] = S(c),
+ * score_out[words] = the float score; all scores are 0 when nx == 0.  Either output may be NULL.  W2B_EINVAL as
+ * w2b_eval_vectors has it for the values (naming the column) and normalize, and for a bitlevel other than 1 or 2. */
+int w2b_vector_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel,
+                           const float *x /* [dim] */, int32_t normalize, float *S_out, float *score_out);
+
 #ifdef __cplusplus
 }
 #endif

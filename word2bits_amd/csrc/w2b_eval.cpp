@@ -2,9 +2,11 @@
 // machine and the stdout transcript of the reference evaluator (ref src/compute-accuracy.c:80-188), around the
 // GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
 // w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
-// adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms.  No arithmetic on scores happens
-// here (one exception: the bag question's weight 1 / sqrt(N_T), built from the integer the device sums) and there is no CPU
-// fallback (w2b_codes_scores_host and w2b_bag_scores_host are the tests' twins of the kernels).
+// adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms, w2b_kernels_evalvec.hip
+// the float-vector question on them.  No arithmetic on scores happens here (the exceptions are question weights: the bag
+// question's 1 / sqrt(N_T), built from the integer the device sums, and the vector question's wx with the fp32 handle's
+// vec = x * wx) and there is no CPU fallback (w2b_codes_scores_host, w2b_bag_scores_host and w2b_vector_scores_host are
+// the tests' twins of the kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
@@ -15,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <locale.h>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -63,7 +66,8 @@ struct w2b_eval {
   int32_t *terms = nullptr;
   uint32_t *P4 = nullptr;                               // [4 * 2 * wpr][cap_t]
   int64_t cap_t = 0;
-  // w2b_eval_bag: the chunk's bags (weights, ids, bounds, own rows) and the questions' digit planes
+  // w2b_eval_bag: the chunk's bags (weights, ids, bounds, own rows) and the questions' digit planes; w2b_eval_vectors on a
+  // packed handle: the chunk's weights and vectors, and their operands in fragment order
   void *bag_buf = nullptr, *bag_T = nullptr;
   size_t bag_bytes = 0, bag_T_bytes = 0;
   unsigned long long *best = nullptr;
@@ -640,6 +644,65 @@ extern "C" int w2b_bag_scores_host(const uint64_t *packed, int64_t words, int64_
   return W2B_OK;
 }
 
+namespace {
+// what w2b_eval_vectors and its host twin refuse in one question: the first column whose value is not finite, or neither 0
+// nor of a magnitude in 2^-60 .. 2^60 (-1: none)
+int64_t bad_vector_value(const float *x, int64_t dim) {
+  for (int64_t a = 0; a < dim; a++) {
+    const float m = fabsf(x[a]);
+    if (!(m == 0.f || (m >= 0x1p-60f && m <= 0x1p60f))) return a;       // (NaN fails every comparison)
+  }
+  return -1;
+}
+const char *const kVectorRange = "a value must be finite and either 0 or of a magnitude in 2^-60 .. 2^60";
+
+// wx of the header: nx in double, column by column; a question whose vector is zero weighs nothing
+float vector_weight(const float *x, int64_t dim, int32_t normalize) {
+#pragma clang fp contract(off)
+  double nx = 0.0;
+  for (int64_t a = 0; a < dim; a++) {
+    const double sq = (double)x[a] * (double)x[a];
+    nx = nx + sq;
+  }
+  if (nx == 0.0) return 0.f;
+  return normalize ? (float)(1.0 / sqrt(nx)) : 1.0f;
+}
+}  // namespace
+
+// Host twin of the vector kernels: the fmaf chain of the header in column order, then the two multiplies one at a time (this
+// file is built with -ffp-contract=off, and the function says so again).
+extern "C" int w2b_vector_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, const float *x,
+                                      int32_t normalize, float *S_out, float *score_out) {
+#pragma clang fp contract(off)
+  const std::string who = "w2b_vector_scores_host";
+  if (!packed || !x || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (normalize != 0 && normalize != 1) return efail(W2B_EINVAL, who + ": normalize must be 0 or 1");
+  const int64_t bad = bad_vector_value(x, dim);
+  if (bad >= 0) return efail(W2B_EINVAL, who + ": column " + std::to_string(bad) + ": " + kVectorRange);
+  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
+  const float wx = vector_weight(x, dim, normalize);
+  const std::vector<float> wt = bitlevel == 2 ? codes_weights(dim) : std::vector<float>();
+  const float wbits = (float)(1.0 / sqrt((double)dim));
+  for (int64_t c = 0; c < words; c++) {
+    const uint64_t *rc = packed + c * wpr;
+    float acc = 0.f;
+    int64_t n3 = 0;
+    for (int64_t a = 0; a < dim; a++) {
+      const uint64_t bit = 1ull << (a & 63);
+      float t = 1.f;
+      if (bitlevel == 2 && (rc[2 * (a >> 6) + 1] & bit)) t = 3.f, n3++;
+      if (rc[bitlevel * (a >> 6)] & bit) t = -t;
+      acc = fmaf(x[a], t, acc);
+    }
+    if (S_out) S_out[c] = acc;
+    if (!score_out) continue;
+    const float ps = acc * wx;
+    score_out[c] = ps * (bitlevel == 2 ? wt[(size_t)n3] : wbits);
+  }
+  return W2B_OK;
+}
+
 extern "C" void w2b_eval_free(w2b_eval *e) { eval_release(e); }
 extern "C" int64_t w2b_eval_words(const w2b_eval *e) { return e ? e->words : 0; }
 extern "C" int64_t w2b_eval_size(const w2b_eval *e) { return e ? e->size : 0; }
@@ -1023,6 +1086,93 @@ struct ScanBag {
   }
 };
 
+// The questions of w2b_eval_vectors: x [nq][size] on the host and their weights wx [nq].  A packed handle gets a chunk's
+// weights [w2b_vec_weight_slots(n)] and vectors [n][size] in one device buffer; an fp32 handle gets vec = x * wx, one float32
+// multiply per column, which ScanVectorsF::before copies into the zeroed query matrix, and a list of rows to exclude that
+// names no row (W2B_EVAL_XSTRIDE times -1 per question).
+struct Vectors {
+  const float *x;
+  const float *wx;
+  std::vector<float> h_w, h_vec;                // what the asynchronous copies read
+  float *d_w = nullptr, *d_x = nullptr;
+  int32_t *d_none = nullptr;
+  int upload(w2b_eval *e, int64_t q0, int64_t n, int64_t np) {
+#pragma clang fp contract(off)
+    const int64_t size = e->size;
+    if (e->bits || e->codes) {
+      const int64_t slots = w2b_vec_weight_slots(n);
+      if (eval_reserve_bag(&e->bag_buf, &e->bag_bytes, (size_t)(slots + n * size) * 4) != W2B_OK)
+        return efail(W2B_ENOMEM, "w2b_eval_vectors: device allocation failed");
+      d_w = (float *)e->bag_buf;
+      d_x = d_w + slots;
+      h_w.assign((size_t)slots, 0.f);
+      std::copy(wx + q0, wx + q0 + n, h_w.begin());
+      EHIP(hipMemcpyAsync(d_w, h_w.data(), (size_t)slots * 4, hipMemcpyHostToDevice, e->stream));
+      EHIP(hipMemcpyAsync(d_x, x + q0 * size, (size_t)(n * size) * 4, hipMemcpyHostToDevice, e->stream));
+      return W2B_OK;
+    }
+    if (eval_reserve_terms(e, np) != W2B_OK) return efail(W2B_ENOMEM, "w2b_eval_vectors: device allocation failed");
+    d_none = e->terms;
+    EHIP(hipMemsetAsync(d_none, 0xFF, (size_t)n * W2B_EVAL_XSTRIDE * 4, e->stream));
+    h_vec.resize((size_t)(n * size));
+    for (int64_t q = 0; q < n; q++)
+      for (int64_t a = 0; a < size; a++) h_vec[(size_t)(q * size + a)] = x[(q0 + q) * size + a] * wx[q0 + q];
+    return W2B_OK;
+  }
+};
+
+// fp32 rows: the uploaded query vectors, then the list form of the top-k scan with nothing to exclude
+struct ScanVectorsF : ScanTopK {
+  using ScanTopK::ScanTopK;
+  int before(int64_t n, int64_t np, const Vectors &d) {
+    if (int rc = clear(n, np)) return rc;
+    EHIP(hipMemcpy2DAsync(e->Q, (size_t)e->ld * 4, d.h_vec.data(), (size_t)e->size * 4, (size_t)e->size * 4, (size_t)n,
+                          hipMemcpyHostToDevice, e->stream));
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const Vectors &d) {
+    return w2b_launch_eval_topk_list(e->Q, e->M, (int)n, (int)e->words, (int)e->size, (int)e->ld, e->fused, d.d_none, k, t.bound,
+                                     t.bkt, t.slots, t.cnt, t.merged, e->variant, e->stream);
+  }
+};
+
+// The vector question on a bits or a codes handle (include/word2bits_eval.h, "vector questions"): the operands in fragment
+// order, the f32 matrix-core scan on the packed rows, the selection state and the merge of the codes scan.  A chunk is sized
+// so that its vectors, their operands and its selection state stay within the budget, never below one 32-question tile.
+struct ScanVectors {
+  w2b_eval *e;
+  int32_t k;
+  TopkScratch t;
+  int64_t chunk, kk;
+  const unsigned long long *keys = nullptr;
+  ScanVectors(w2b_eval *e_, int32_t k_) : e(e_), k(k_), kk(k_) {
+    t.k = k;
+    w2b_vec_topk_layout(e->words, k, &t.nunits, &t.cap);
+    (void)t.chunk(0);                                                   // (sets per_q)
+    const int64_t per_q = t.per_q + 4 * e->size + 32 * ((e->size + 7) / 8) + 4;
+    const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+    chunk = budget / per_q / 32 * 32;
+    if (chunk < 32) chunk = 32;
+    if (chunk > kChunkQ) chunk = kChunkQ;
+  }
+  size_t scratch(int64_t n) const { return t.bytes(n); }
+  int before(int64_t n, int64_t, const Vectors &) {
+    if (eval_reserve_bag(&e->bag_T, &e->bag_T_bytes, w2b_vec_operand_bytes((int)e->size, n)) != W2B_OK)
+      return efail(W2B_ENOMEM, "w2b_eval_vectors: device allocation failed");
+    EHIP(hipMemsetAsync(e->tk_buf, 0, t.place(e->tk_buf, n), e->stream));
+    keys = t.merged;
+    return W2B_OK;
+  }
+  hipError_t timed(int64_t n, int64_t, const Vectors &d) {
+    const hipError_t le = w2b_launch_vec_operands(d.d_x, (int)e->size, (int)n, e->bag_T, e->stream);
+    if (le != hipSuccess) return le;
+    return w2b_launch_vec_scan(e->B, (int)e->words, (int)e->size, e->codes ? 2 : 1, e->wrow,
+                               (float)(1.0 / sqrt((double)e->size)), e->bag_T, d.d_w, (int)n, k, t.bound, t.bkt, t.slots, t.cnt,
+                               t.merged, e->stream);
+  }
+  float score(unsigned long long key) const { return f32_score(key); }
+};
+
 struct EventPair {   // the two ends of a timed window
   hipEvent_t t[2] = {nullptr, nullptr};
   hipError_t create() {
@@ -1167,6 +1317,28 @@ extern "C" int w2b_eval_bag(w2b_eval *e, int64_t n_ids, const int32_t *ids, int6
   EHIP(hipSetDevice(e->device));
   Bags in{ids, offsets, exclude_own == 1};
   return eval_scan_chunks(e, ScanBag(e, k), std::move(in), nq, best, bestd, who, 2.0);
+}
+
+// The vector question: what does not depend on the handle first, then the handle, then the values; the weights; the chunks.
+extern "C" int w2b_eval_vectors(w2b_eval *e, int64_t nq, const float *x, int32_t normalize, int32_t k, int32_t *best,
+                                float *bestd) {
+  const std::string who = "w2b_eval_vectors";
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  if (normalize != 0 && normalize != 1) return efail(W2B_EINVAL, who + ": normalize must be 0 or 1");
+  if (nq < 0 || (nq > 0 && (!x || !best))) return efail(W2B_EINVAL, who + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  for (int64_t q = 0; q < nq; q++) {
+    const int64_t bad = bad_vector_value(x + q * e->size, e->size);
+    if (bad >= 0)
+      return efail(W2B_EINVAL, who + ": question " + std::to_string(q) + ", column " + std::to_string(bad) + ": " + kVectorRange);
+  }
+  if (nq == 0) return W2B_OK;
+  std::vector<float> wx((size_t)nq);
+  for (int64_t q = 0; q < nq; q++) wx[(size_t)q] = vector_weight(x + q * e->size, e->size, normalize);
+  EHIP(hipSetDevice(e->device));
+  Vectors in{x, wx.data()};
+  if (e->bits || e->codes) return eval_scan_chunks(e, ScanVectors(e, k), std::move(in), nq, best, bestd, who, 1.0);
+  return eval_scan_chunks(e, ScanVectorsF(e, k), std::move(in), nq, best, bestd, who, 1.0);
 }
 
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
@@ -1505,6 +1677,48 @@ extern "C" int w2b_eval_bag_text(w2b_eval *e, const char *queries, int64_t len, 
     if (rc != W2B_OK) return rc;
   }
   return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_bag_text", out, out_len);
+}
+
+// the vector form: every non-empty line is `size` numbers
+extern "C" int w2b_eval_vectors_text(w2b_eval *e, const char *queries, int64_t len, int32_t normalize, int32_t k, char **out,
+                                     int64_t *out_len) {
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_vectors_text: k must be 1..64");
+  if (normalize != 0 && normalize != 1) return efail(W2B_EINVAL, "w2b_eval_vectors_text: normalize must be 0 or 1");
+  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_vectors_text: bad argument");
+  if (!e) return efail(W2B_EINVAL, "w2b_eval_vectors_text: null handle");
+  *out = nullptr;
+  static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+  if (!c_locale) return efail(W2B_ENOMEM, "w2b_eval_vectors_text: no C locale");
+  std::vector<QueryLine> lines;
+  std::vector<float> x, row((size_t)e->size);
+  std::vector<std::string> tok;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
+    if (tok.empty()) continue;
+    QueryLine ln{"vector " + std::to_string(lines.size() + 1), std::string(), -1};
+    bool numbers = (int64_t)tok.size() == e->size;
+    for (size_t i = 0; i < tok.size() && numbers; i++) {
+      char *end = nullptr;
+      row[i] = strtof_l(tok[i].c_str(), &end, c_locale);
+      numbers = end == tok[i].c_str() + tok[i].size();
+    }
+    if (!numbers) {
+      ln.error = "expected " + std::to_string(e->size) + " numbers";
+    } else if (bad_vector_value(row.data(), e->size) >= 0) {
+      ln.error = "value out of range";
+    } else {
+      ln.q = (int64_t)(x.size() / (size_t)e->size);
+      x.insert(x.end(), row.begin(), row.end());
+    }
+    lines.push_back(ln);
+  }
+  const size_t nq = x.size() / (size_t)e->size;
+  std::vector<int32_t> best(nq * (size_t)k);
+  std::vector<float> bestd(nq * (size_t)k);
+  if (nq > 0) {
+    const int rc = w2b_eval_vectors(e, (int64_t)nq, x.data(), normalize, k, best.data(), bestd.data());
+    if (rc != W2B_OK) return rc;
+  }
+  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_vectors_text", out, out_len);
 }
 
 extern "C" void w2b_eval_free_text(char *text) { free(text); }

@@ -210,6 +210,20 @@ hipError_t w2b_launch_bag_scan(const uint32_t *B, int words, int dim, int bitlev
                                const float *Wq, int nq, const int *xrows, const int *xoff, int k, unsigned long long *bound,
                                unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt, unsigned long long *out,
                                hipStream_t s);
+// The float-vector question on bit-packed rows (w2b_kernels_evalvec.hip; include/word2bits_eval.h, "vector questions").  B =
+// the packed rows as 64-bit words, [words][bitlevel * ceil(dim / 64)]; x = the questions [nq][dim] on the device; X = their
+// operands in fragment order (w2b_vec_operand_bytes; the operand kernel writes every byte of it).  The scan: wrow as above
+// (bitlevel 2) or wconst = the weight of every 1-bit row; Wx = the questions' weights [w2b_vec_weight_slots(nq)], 0 for a
+// question without answers and in the slots past nq; bound / bkt / keys / cnt = the zeroed selection state sized by
+// w2b_vec_topk_layout, out[q * k + j] the j-th best key (score bits << 32 | ~row).
+size_t w2b_vec_operand_bytes(int dim, long long nq);
+long long w2b_vec_weight_slots(long long nq);
+void w2b_vec_topk_layout(long long words, int k, int *nunits, int *cap);
+hipError_t w2b_launch_vec_operands(const float *x, int dim, int nq, void *X, hipStream_t s);
+hipError_t w2b_launch_vec_scan(const uint64_t *B, int words, int dim, int bitlevel, const float *wrow, float wconst,
+                               const void *X, const float *Wx, int nq, int k, unsigned long long *bound,
+                               unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt, unsigned long long *out,
+                               hipStream_t s);
 // the packed embedding layer (w2b_kernels_embed.hip; include/word2bits_embed.h).  T = the packed table [rows][wpr], ids /
 // offsets = int64 device buffers, `bad` = the device counter of ignored ids and clamped bags.  A bag launch needs
 // w2b_embed_bag_scratch(...) bytes of device scratch (it zeroes them itself).

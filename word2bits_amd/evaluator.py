@@ -7,9 +7,10 @@
     rows, scores = ev.neighbors([ev.lookup(b"KING")], 10)
     ev = Evaluator("vectors2.w2bp", codes=True)                      # 2-bit model kept packed: the i8 matrix-core scan
     rows, scores = ev.bag([3, 17, 4, 9, 9], [0, 2, 5], 10)           # two bags of rows pooled: nearest to each sum
+    rows, scores = ev.vectors(hidden, 10)                            # float vectors [nq, size] of one's own: nearest to each
 
 The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip,
-w2b_kernels_evalbag.hip);
+w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip);
 there is no CPU path in this module.
 """
 import ctypes as C
@@ -179,6 +180,26 @@ class Evaluator:
     def bag_text(self, queries, k, exclude_own=True):
         """stdout of `nearest FILE k ... bits|codes bag < queries` as bytes: every line is one bag of 1 to 4096 words."""
         return self._text(self._L.w2b_eval_bag_text, queries, int(exclude_own), int(k))
+
+    def vectors(self, x, k, normalize=True):
+        """The vector question (w2b_eval_vectors; every handle kind): `x` is float32 [nq, size] (or one vector [size]), vectors
+        the caller computed itself.  Returns (rows int32 [nq, k], scores float32 [nq, k]) in the order of topk; nothing is
+        excluded.  `normalize=True` scores by cosine (x scaled by 1 / |x|), False leaves x as it is.  Every value must be
+        finite and 0 or of a magnitude in 2^-60 .. 2^60."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2 or x.shape[1] != self.size:
+            raise ValueError("x must be [nq, %d]" % self.size)
+        nq, k = x.shape[0], int(k)
+        best, bestd = np.empty((nq, max(k, 0)), np.int32), np.empty((nq, max(k, 0)), np.float32)
+        _lib.check(self._L.w2b_eval_vectors(self._h, nq, x.ctypes.data_as(_lib.f32p), int(normalize), k,
+                                            best.ctypes.data_as(_lib.i32p), bestd.ctypes.data_as(_lib.f32p)))
+        return best, bestd
+
+    def vectors_text(self, queries, k, normalize=True):
+        """stdout of `nearest FILE k ... vector < queries` as bytes: every line is `size` numbers."""
+        return self._text(self._L.w2b_eval_vectors_text, queries, int(normalize), int(k))
 
     def nearest_text(self, queries, k):
         """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
