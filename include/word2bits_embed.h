@@ -29,6 +29,28 @@
  *   does not depend on how the kernels split a bag.
  * Output dtypes.  W2B_EMBED_BF16 and W2B_EMBED_F16 are the float32 result above rounded to nearest even (16-bit
  *   patterns).  .25 and .75 are exact in both; 1/3 becomes 0x3EAB in bf16 and 0x3555 in f16.
+ * Weighted bag (w2b_embed_bag_weighted*; torch's per_sample_weights).  Table, ids, offsets, padding, W2B_EMBED_MAX_BAG,
+ *   dtypes and modes as for the bag; in addition weights is float32 [n_ids], one per id POSITION.  The weight of a
+ *   padding id is ignored and may hold anything.  The weight of an id >= 0 must be finite and either 0 or
+ *   2^-60 <= |w| <= 2^60, else W2B_EINVAL: within that range every term and every partial sum is 0 or between 2^-83
+ *   and 2^84 (as for the queries of w2b_eval_vectors), nothing is subnormal and nothing overflows, so the result does
+ *   not depend on how an instruction treats subnormals.
+ *   A float sum depends on its order, so the order is part of the contract.  Per bag and per column a, with t_r[a] the
+ *   integer code above ((float)t is exact): the bag's positions, padding included, are cut into SEGMENTS of
+ *   W2B_EMBED_WSEG consecutive positions counted from the bag's start.
+ *       segment s:  P_s = +0;  for the positions i of s in order with ids[i] >= 0:  P_s = fmaf(w_i, (float)t_ids[i][a], P_s)
+ *                   one fused multiply-add per id, strictly sequential, one accumulator per (bag, column)
+ *       bag:        S = +0;  for s in order:  S = S + P_s          each ONE float32 add, rounded on its own
+ *       sum  = S * q                                               ONE multiply, q as above
+ *       mean = sum / (float)m                                      ONE correctly rounded division; m = the number of
+ *                                                                  ids >= 0, as in the unweighted mean -- NOT the sum
+ *                                                                  of the weights; m == 0 gives +0.0
+ *   A bag of at most W2B_EMBED_WSEG positions is therefore one chain.  BF16 / F16 are that float32 result rounded to
+ *   nearest even.  The segment rule is what lets a long bag be spread over the device without float atomics and still
+ *   have ONE defined result: whichever path pools a bag (its own workgroup, its segments on many workgroups, or one
+ *   workgroup walking all its segments when the list of long bags is full), the result is the one above, bit for bit.
+ *   Two consequences: with every weight 1.0f all partial sums are integers below 2^24, so sum / mean equal
+ *   w2b_embed_bag bit for bit; scaling every weight by 2^s (staying in range) scales sum and mean exactly.
  *
  * ---- out of scope --------------------------------------------------------------------------------------------------
  * Gradients or training through the lookup (the table is read-only); bitlevels other than 1 and 2; a handle built from
@@ -48,6 +70,7 @@ typedef struct w2b_embed w2b_embed;
 #define W2B_EMBED_SUM 0
 #define W2B_EMBED_MEAN 1
 #define W2B_EMBED_MAX_BAG (1 << 22)
+#define W2B_EMBED_WSEG 1024
 
 /* A bit-packed .w2bp, read without expanding it; `threshold` caps the rows as in w2b_eval_load_bits (0 = off).  What is
  * wrong with the file is reported before a device is asked for: W2B_EIO "Input file not found" when it cannot be opened,
@@ -94,11 +117,32 @@ int w2b_embed_bad_ids(w2b_embed *e, int64_t *count);             /* syncs, retur
  * x 8, padding ids included) plus the output bytes they wrote. */
 int w2b_embed_timing_read(w2b_embed *e, double *kernel_ms, int64_t *launches, double *bytes);
 
+/* Weighted bag, the semantics above.  Host form: validated before anything is launched, the checks of w2b_embed_bag
+ * unchanged; weights == NULL with n_ids > 0 is W2B_EINVAL, and so is the first refused weight on an id >= 0, whose index
+ * w2b_last_error() names; then `out` is untouched.  n_bags == 0 is W2B_OK.  Large calls are chunked by whole bags as
+ * w2b_embed_bag chunks them, the weights staged beside the ids.
+ * Device form: w2b_embed_reserve_weights hands out weights_dev = float[max_ids], a buffer of its own beside the three of
+ * w2b_embed_reserve: its pointer goes stale only when the weights buffer itself grows (a call that asks for no more than
+ * is there returns the same pointer), and growing the others leaves it valid.  The caller fills ids_dev, weights_dev and
+ * offsets_dev and launches; out_dev is that of w2b_embed_reserve.  W2B_EINVAL when n_ids exceeds what either reserve call
+ * provided, or n_bags / dtype what w2b_embed_reserve provided.  No content of the staging makes a kernel read or write
+ * outside its buffers: the clamping rules of the unweighted device form apply, and a weight that the host form would
+ * refuse, on an id that is otherwise valid, makes that id contribute nothing (m included) and is counted once in
+ * w2b_embed_bad_ids.  w2b_embed_timing_read counts these launches; their bytes include 4 per id for the weights. */
+int w2b_embed_bag_weighted(w2b_embed *e, int64_t n_ids, const int32_t *ids, const float *weights,
+                           int64_t n_bags, const int64_t *offsets, int32_t mode, int32_t dtype, void *out);
+int w2b_embed_reserve_weights(w2b_embed *e, int64_t max_ids, void **weights_dev);   /* float[max_ids] */
+int w2b_embed_bag_weighted_device(w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype);
+
 /* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form. */
 int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                           int64_t n, const int32_t *ids, float *out);
 int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
                        const int32_t *ids, int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
+/* the weighted bag: explicit fmaf per id, the segments and the steps exactly as stated above */
+int w2b_embed_bag_weighted_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
+                                int64_t n_ids, const int32_t *ids, const float *weights,
+                                int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
 
 #ifdef __cplusplus
 }

@@ -366,6 +366,13 @@ int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int
                           const int32_t *ids, float *out);
 int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
                        const int32_t *ids, int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
+int w2b_embed_bag_weighted(struct w2b_embed *e, int64_t n_ids, const int32_t *ids, const float *weights, int64_t n_bags,
+                           const int64_t *offsets, int32_t mode, int32_t dtype, void *out);
+int w2b_embed_reserve_weights(struct w2b_embed *e, int64_t max_ids, void **weights_dev);
+int w2b_embed_bag_weighted_device(struct w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype);
+int w2b_embed_bag_weighted_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                                const int32_t *ids, const float *weights, int64_t n_bags, const int64_t *offsets,
+                                int32_t mode, float *out);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,12 @@ F.embedding_bag on its own resident copy of the table, torch.cuda.Event time.  E
 are timed in turn, `--repeats` rounds (so that a drift of the machine falls on all of them alike); medians.  `bytes` is
 what timing() counts: packed words read + output written.  One JSON line on stdout (and in --out).
 
-    python tools/embed_bench.py --out profiles/embed_bench.json"""
+--weighted times the weighted leg instead, on the same shapes: the weighted sum over the 32-id bags (per_sample_weights, SIF-like
+weights a / (a + p(w)) of the Zipf ranks) beside F.embedding_bag(..., mode="sum", per_sample_weights=...) on the float table and
+beside the unweighted bag kernel on the same ids.
+
+    python tools/embed_bench.py --out profiles/embed_bench.json
+    python tools/embed_bench.py --weighted --out profiles/embed_bench_weighted.json"""
 import argparse
 import json
 import os
@@ -30,6 +35,7 @@ def main():
     ap.add_argument("--dims", type=int, nargs="*", default=[800, 200])
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--weighted", action="store_true", help="the weighted-bag leg instead of lookup / mean")
     ap.add_argument("--out")
     a = ap.parse_args()
     torch.cuda.init()                                        # torch's runtime first, then the library's (tests/conftest.py)
@@ -43,6 +49,9 @@ def main():
     off_np = (np.arange(n_bags + 1, dtype=np.int64) * a.bag)
     n_bag_ids = int(off_np[-1])
     ids_t, off_t = torch.from_numpy(ids_np).to(dev), torch.from_numpy(off_np).to(dev)
+    pw = p / p.sum()
+    w_np = (1e-3 / (1e-3 + pw[ids_np])).astype(np.float32)                            # SIF: a / (a + p(w)), a = 1e-3
+    w_t = torch.from_numpy(w_np).to(dev)
     res = {"shape": {"rows": a.rows, "ids": a.ids, "bag": a.bag, "ids_distribution": "zipf(1)"}, "warmup": a.warmup,
            "repeats": a.repeats, "roof_gbs": ROOF_GBS, "device": torch.cuda.get_device_name(0), "cases": {}}
 
@@ -65,6 +74,8 @@ def main():
             s_ids, s_off, _ = emb.staging(a.ids, n_bags, "float32")
             s_ids.copy_(ids_t)
             s_off.copy_(off_t)
+            if a.weighted:
+                emb.staging_weights(a.ids).copy_(w_t)
             torch.cuda.synchronize()
             ours_mem = free0 - torch.cuda.mem_get_info()[0]
             free1 = torch.cuda.mem_get_info()[0]
@@ -84,6 +95,8 @@ def main():
                     keep.clear()
                     return torch_ms(lambda: keep.setdefault("x", fn())), None
                 return run
+            pairs = (("lookup_f32", "torch_index_select_f32"), ("lookup_bf16", "torch_index_select_to_bf16"),
+                     ("bag_mean_f32", "torch_embedding_bag_mean_f32"))
             cases = {
                 "lookup_f32": ours(lambda: emb.lookup_device(a.ids, "float32")),
                 "torch_index_select_f32": theirs(lambda: torch.index_select(table, 0, ids_t)),
@@ -93,13 +106,31 @@ def main():
                 "torch_embedding_bag_mean_f32": theirs(lambda: F.embedding_bag(ids_t[:n_bag_ids], table, off_t, mode="mean",
                                                                                include_last_offset=True)),
             }
-            # same answers, or the times compare nothing (2-bit sums are exact in float32; the mean is one division)
-            emb.lookup_device(a.ids, "float32")
-            emb.synchronize()
+            if a.weighted:
+                pairs = (("bag_weighted_sum_f32", "torch_embedding_bag_weighted_sum_f32"), ("bag_weighted_sum_f32", "bag_sum_f32"))
+                cases = {
+                    "bag_weighted_sum_f32": ours(lambda: emb.bag_weighted_device(n_bag_ids, n_bags, "sum", "float32")),
+                    "torch_embedding_bag_weighted_sum_f32": theirs(lambda: F.embedding_bag(
+                        ids_t[:n_bag_ids], table, off_t, mode="sum", per_sample_weights=w_t[:n_bag_ids], include_last_offset=True)),
+                    "bag_sum_f32": ours(lambda: emb.bag_device(n_bag_ids, n_bags, "sum", "float32")),
+                }
             out = emb.staging(a.ids, n_bags, "float32")[2]
-            step = 100_000
-            for i in range(0, a.ids, step):
-                assert torch.equal(out[i:i + step].view(torch.int32), table[ids_t[i:i + step]].view(torch.int32))
+            if a.weighted:
+                # the same sums up to the order and the rounding of the float operations: |sum| < 32, some sixty roundings of
+                # at most 2^-20 each on the two sides
+                emb.bag_weighted_device(n_bag_ids, n_bags, "sum", "float32")
+                emb.synchronize()
+                want = F.embedding_bag(ids_t[:n_bag_ids], table, off_t, mode="sum", per_sample_weights=w_t[:n_bag_ids],
+                                       include_last_offset=True)
+                assert torch.allclose(out[:n_bags], want, rtol=0, atol=2.0 ** -13)
+                del want
+            else:
+                # same answers, or the times compare nothing (2-bit sums are exact in float32; the mean is one division)
+                emb.lookup_device(a.ids, "float32")
+                emb.synchronize()
+                step = 100_000
+                for i in range(0, a.ids, step):
+                    assert torch.equal(out[i:i + step].view(torch.int32), table[ids_t[i:i + step]].view(torch.int32))
             assert emb.bad_ids() == 0
             for fn in cases.values():
                 for _ in range(a.warmup):
@@ -121,9 +152,8 @@ def main():
                 if name in nbytes:
                     gbs = nbytes[name] / (statistics.median(r) * 1e-3) / 1e9
                     entry[name].update(bytes=nbytes[name], gbs=gbs, fraction_of_roof=gbs / ROOF_GBS)
-            for o, t in (("lookup_f32", "torch_index_select_f32"), ("lookup_bf16", "torch_index_select_to_bf16"),
-                         ("bag_mean_f32", "torch_embedding_bag_mean_f32")):
-                entry[o]["time_vs_torch"] = entry[o]["median_ms"] / entry[t]["median_ms"]
+            for o, t in pairs:
+                entry[o]["time_vs_torch" if t.startswith("torch") else "time_vs_" + t] = entry[o]["median_ms"] / entry[t]["median_ms"]
             res["cases"]["bitlevel%d_dim%d" % (bitlevel, dim)] = entry
             emb.close()
             del table, out, s_ids, s_off

@@ -185,6 +185,11 @@ SIGNATURES = {
     "w2b_embed_timing_read": (C.c_int, [vp, f64p, i64p, f64p]),
     "w2b_embed_lookup_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, f32p]),
     "w2b_embed_bag_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int64, i64p, C.c_int32, f32p]),
+    "w2b_embed_bag_weighted": (C.c_int, [vp, C.c_int64, i32p, f32p, C.c_int64, i64p, C.c_int32, C.c_int32, vp]),
+    "w2b_embed_reserve_weights": (C.c_int, [vp, C.c_int64, C.POINTER(vp)]),
+    "w2b_embed_bag_weighted_device": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "w2b_embed_bag_weighted_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, f32p, C.c_int64, i64p,
+                                              C.c_int32, f32p]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 // w2b_embed.cpp -- host side of include/word2bits_embed.h: the handle, the .w2bp loader, validation, the device staging
 // (one set of buffers handed to the caller by w2b_embed_reserve, a separate bounded one for the host form), the chunking
-// of host-form calls, timing, and the host twins of the kernels in w2b_kernels_embed.hip.  The table stays packed on the
+// of host-form calls (weighted bags stage their weights beside the ids), timing, and the host twins of the kernels in w2b_kernels_embed.hip.  The table stays packed on the
 // device; no float table exists on either side and there is no CPU fallback (the *_host twins are for tests).
 #include "../../include/word2bits_embed.h"
 #include "../../include/word2bits_corpus.h"
@@ -8,6 +8,7 @@
 #include "w2b_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -34,6 +35,9 @@ struct Staging {
   long long *ids = nullptr, *offsets = nullptr;
   void *out = nullptr, *scratch = nullptr;
   int64_t cap_ids = 0, cap_bags = -1, out_bytes = 0, scratch_bytes = 0;
+  float *weights = nullptr;                  // weighted bags only: a buffer and a scratch of their own
+  void *wscratch = nullptr;
+  int64_t cap_weights = 0, wscratch_bytes = 0;
 };
 struct Pending { hipEvent_t a, b; };
 }  // namespace
@@ -60,6 +64,8 @@ void free_staging(Staging &s) {
   if (s.offsets) (void)hipFree(s.offsets);
   if (s.out) (void)hipFree(s.out);
   if (s.scratch) (void)hipFree(s.scratch);
+  if (s.weights) (void)hipFree(s.weights);
+  if (s.wscratch) (void)hipFree(s.wscratch);
   s = Staging();
 }
 
@@ -111,6 +117,23 @@ int check_bags(int64_t n_ids, int64_t n_bags, const int64_t *offsets, int32_t mo
       return efail(W2B_EINVAL, w + ": bag " + std::to_string(b) + " is longer than W2B_EMBED_MAX_BAG");
   }
   if (offsets[n_bags] != n_ids) return efail(W2B_EINVAL, w + ": offsets[n_bags] is not n_ids");
+  return W2B_OK;
+}
+
+// the first weight on an id >= 0 that is not finite, or neither 0 nor within 2^-60 .. 2^60
+int check_weights(int64_t n, const int32_t *ids, const float *weights, const char *who) {
+  if (n > 0 && !weights) return efail(W2B_EINVAL, std::string(who) + ": null weights");
+  for (int64_t i = 0; i < n; i++) {
+    uint32_t bits;
+    memcpy(&bits, weights + i, 4);
+    const uint32_t a = bits & 0x7FFFFFFFu;
+    if (ids[i] >= 0 && a != 0u && (a < 0x21800000u || a > 0x5D800000u)) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "%s: weights[%lld] = %g is not finite, or neither 0 nor within 2^-60 .. 2^60", who, (long long)i,
+               (double)weights[i]);
+      return efail(W2B_EINVAL, msg);
+    }
+  }
   return W2B_OK;
 }
 
@@ -168,6 +191,20 @@ int ensure(w2b_embed *e, Staging &s, int64_t max_ids, int64_t max_bags, int64_t 
   return W2B_OK;
 }
 
+// the weights buffer for max_ids ids, and the scratch of a weighted launch of n_ids ids in n_bags bags; only ever grow
+int ensure_weighted(w2b_embed *e, Staging &s, int64_t max_ids, int64_t n_ids, int64_t n_bags) {
+  if (max_ids > s.cap_weights || !s.weights)
+    if (int rc = grow(e, s.weights, s.cap_weights, max_ids * 4, max_ids)) return rc;
+  if (n_bags > 0) {
+    int cap = 0;
+    long long segcap = 0, head = 0;
+    const int64_t need = w2b_embed_bagw_scratch(n_ids, n_bags, (int)e->dim, &cap, &segcap, &head);
+    if (need > s.wscratch_bytes)
+      if (int rc = grow(e, s.wscratch, s.wscratch_bytes, need, need)) return rc;
+  }
+  return W2B_OK;
+}
+
 int fold_pending(w2b_embed *e) {
   EHIP(hipStreamSynchronize(e->stream));
   for (Pending &p : e->pending) {
@@ -216,6 +253,14 @@ int launch_bag(w2b_embed *e, Staging &s, int64_t n_ids, int64_t n_bags, int32_t 
   return timed(e, bytes, [&] {
     return w2b_launch_embed_bag(e->T, e->rows, (int)e->dim, e->bitlevel, s.ids, n_ids, s.offsets, n_bags, mode, dtype, s.out,
                                 e->bad, s.scratch, e->stream);
+  });
+}
+
+int launch_bag_weighted(w2b_embed *e, Staging &s, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype) {
+  const double bytes = (double)n_ids * ((double)e->wpr * 8 + 4) + (double)n_bags * (double)e->dim * elem_size(dtype);
+  return timed(e, bytes, [&] {
+    return w2b_launch_embed_bag_weighted(e->T, e->rows, (int)e->dim, e->bitlevel, s.ids, s.weights, n_ids, s.offsets, n_bags,
+                                         mode, dtype, s.out, e->bad, s.wscratch, e->stream);
   });
 }
 }  // namespace
@@ -339,6 +384,43 @@ extern "C" int w2b_embed_bag(w2b_embed *e, int64_t n_ids, const int32_t *ids, in
   return W2B_OK;
 }
 
+extern "C" int w2b_embed_bag_weighted(w2b_embed *e, int64_t n_ids, const int32_t *ids, const float *weights, int64_t n_bags,
+                                      const int64_t *offsets, int32_t mode, int32_t dtype, void *out) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_bag_weighted: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_bag_weighted: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (int rc = check_ids(e->rows, n_ids, ids, "w2b_embed_bag_weighted")) return rc;
+  if (int rc = check_bags(n_ids, n_bags, offsets, mode, "w2b_embed_bag_weighted")) return rc;
+  if (int rc = check_weights(n_ids, ids, weights, "w2b_embed_bag_weighted")) return rc;
+  if (n_bags == 0) return W2B_OK;
+  if (!out) return efail(W2B_EINVAL, "w2b_embed_bag_weighted: null output");
+  EHIP(hipSetDevice(e->device));
+  const int64_t row_bytes = e->dim * es;
+  int64_t max_bags = kHostOutBytes / row_bytes;
+  if (max_bags < 1) max_bags = 1;
+  std::vector<long long> wide, off;
+  for (int64_t b0 = 0; b0 < n_bags;) {                     // the chunks of w2b_embed_bag
+    int64_t b1 = b0 + 1;
+    while (b1 < n_bags && b1 - b0 < max_bags && offsets[b1 + 1] - offsets[b0] <= kHostIds) b1++;
+    const int64_t i0 = offsets[b0], ci = offsets[b1] - i0, cb = b1 - b0;
+    if (int rc = ensure(e, e->host, ci > 0 ? ci : 1, cb, cb * row_bytes)) return rc;
+    if (int rc = ensure_weighted(e, e->host, e->host.cap_ids, ci, cb)) return rc;
+    wide.assign(ids + i0, ids + i0 + ci);
+    off.resize((size_t)cb + 1);
+    for (int64_t b = 0; b <= cb; b++) off[(size_t)b] = offsets[b0 + b] - i0;
+    if (ci > 0) {
+      EHIP(hipMemcpyAsync(e->host.ids, wide.data(), (size_t)ci * 8, hipMemcpyHostToDevice, e->stream));
+      EHIP(hipMemcpyAsync(e->host.weights, weights + i0, (size_t)ci * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    EHIP(hipMemcpyAsync(e->host.offsets, off.data(), (size_t)(cb + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    if (int rc = launch_bag_weighted(e, e->host, ci, cb, mode, dtype)) return rc;
+    EHIP(hipMemcpyAsync((char *)out + b0 * row_bytes, e->host.out, (size_t)(cb * row_bytes), hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+    b0 = b1;
+  }
+  return W2B_OK;
+}
+
 // ------------------------------------------------------------------------------------ device form
 extern "C" int w2b_embed_reserve(w2b_embed *e, int64_t max_ids, int64_t max_bags, int32_t dtype, void **ids_dev,
                                  void **offsets_dev, void **out_dev) {
@@ -382,6 +464,36 @@ extern "C" int w2b_embed_bag_device(w2b_embed *e, int64_t n_ids, int64_t n_bags,
     return efail(W2B_EINVAL, "w2b_embed_bag_device: more than w2b_embed_reserve has set aside");
   EHIP(hipSetDevice(e->device));
   return launch_bag(e, e->user, n_ids, n_bags, mode, dtype);
+}
+
+extern "C" int w2b_embed_reserve_weights(w2b_embed *e, int64_t max_ids, void **weights_dev) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_weights: null handle");
+  if (max_ids < 0 || max_ids > (1ll << 40)) return efail(W2B_EINVAL, "w2b_embed_reserve_weights: bad size");
+  EHIP(hipSetDevice(e->device));
+  Staging &s = e->user;                                    // the scratch for what w2b_embed_reserve has set aside so far
+  const int64_t ids = max_ids < s.cap_ids ? max_ids : s.cap_ids;
+  if (int rc = ensure_weighted(e, s, max_ids, ids, s.cap_bags)) return rc;
+  if (weights_dev) *weights_dev = s.weights;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_bag_weighted_device(w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_bag_weighted_device: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_bag_weighted_device: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (mode != W2B_EMBED_SUM && mode != W2B_EMBED_MEAN)
+    return efail(W2B_EINVAL, "w2b_embed_bag_weighted_device: mode is neither W2B_EMBED_SUM nor W2B_EMBED_MEAN");
+  if (n_ids < 0 || n_bags < 0) return efail(W2B_EINVAL, "w2b_embed_bag_weighted_device: negative count");
+  if (n_bags == 0) return W2B_OK;
+  Staging &s = e->user;
+  if (!s.ids || !s.offsets || !s.out || n_ids > s.cap_ids || n_bags > s.cap_bags || n_bags * e->dim * es > s.out_bytes)
+    return efail(W2B_EINVAL, "w2b_embed_bag_weighted_device: more than w2b_embed_reserve has set aside");
+  if (!s.weights || n_ids > s.cap_weights)
+    return efail(W2B_EINVAL, "w2b_embed_bag_weighted_device: more than w2b_embed_reserve_weights has set aside");
+  EHIP(hipSetDevice(e->device));
+  // the scratch follows the call (it waits for the stream only when it has to grow); the weights buffer stays as it is
+  if (int rc = ensure_weighted(e, s, s.cap_weights, n_ids, n_bags)) return rc;
+  return launch_bag_weighted(e, s, n_ids, n_bags, mode, dtype);
 }
 
 extern "C" int w2b_embed_synchronize(w2b_embed *e) {
@@ -471,6 +583,48 @@ extern "C" int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t 
     float *o = out + b * dim;
     for (int64_t c = 0; c < dim; c++) {
       const float sum = (float)T[(size_t)c] * q;             // one float32 multiply (no contraction: -ffp-contract=off)
+      o[c] = mode == W2B_EMBED_MEAN ? (m > 0 ? sum / (float)m : 0.f) : sum;
+    }
+  }
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_bag_weighted_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                                           const int32_t *ids, const float *weights, int64_t n_bags, const int64_t *offsets,
+                                           int32_t mode, float *out) {
+  if (!packed) return efail(W2B_EINVAL, "w2b_embed_bag_weighted_host: null table");
+  if (int rc = check_shape(rows, dim, bitlevel, 0, "w2b_embed_bag_weighted_host")) return rc;
+  if (int rc = check_ids(rows, n_ids, ids, "w2b_embed_bag_weighted_host")) return rc;
+  if (int rc = check_bags(n_ids, n_bags, offsets, mode, "w2b_embed_bag_weighted_host")) return rc;
+  if (int rc = check_weights(n_ids, ids, weights, "w2b_embed_bag_weighted_host")) return rc;
+  if (n_bags == 0) return W2B_OK;
+  if (!out) return efail(W2B_EINVAL, "w2b_embed_bag_weighted_host: null output");
+  const int64_t wpr = w2b_packed_words_per_row(dim, bitlevel);
+  const float q = bitlevel == 1 ? bits_f32(0x3EAAAAABu) : 0.25f;
+  std::vector<float> P((size_t)dim), S((size_t)dim);
+  for (int64_t b = 0; b < n_bags; b++) {
+    std::fill(S.begin(), S.end(), 0.f);
+    int32_t m = 0;
+    for (int64_t s0 = offsets[b]; s0 < offsets[b + 1]; s0 += W2B_EMBED_WSEG) {      // one segment: one chain per column
+      const int64_t s1 = std::min<int64_t>(s0 + W2B_EMBED_WSEG, offsets[b + 1]);
+      std::fill(P.begin(), P.end(), 0.f);
+      for (int64_t i = s0; i < s1; i++) {
+        if (ids[i] < 0) continue;
+        m++;
+        const float w = weights[i];
+        const uint64_t *row = packed + (int64_t)ids[i] * wpr;
+        for (int64_t c = 0; c < dim; c++) {
+          const uint64_t *blk = row + (c >> 6) * bitlevel;
+          const int sg = (int)((blk[0] >> (c & 63)) & 1u);
+          const int mag = bitlevel == 2 && ((blk[1] >> (c & 63)) & 1u) ? 3 : 1;
+          P[(size_t)c] = fmaf(w, (float)(sg ? -mag : mag), P[(size_t)c]);
+        }
+      }
+      for (int64_t c = 0; c < dim; c++) S[(size_t)c] = S[(size_t)c] + P[(size_t)c];     // one float32 add per segment
+    }
+    float *o = out + b * dim;
+    for (int64_t c = 0; c < dim; c++) {
+      const float sum = S[(size_t)c] * q;                    // one float32 multiply (no contraction: -ffp-contract=off)
       o[c] = mode == W2B_EMBED_MEAN ? (m > 0 ? sum / (float)m : 0.f) : sum;
     }
   }

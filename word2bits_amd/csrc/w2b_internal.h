@@ -234,6 +234,13 @@ long long w2b_embed_bag_scratch(long long n_ids, long long n_bags, int dim, int 
 hipError_t w2b_launch_embed_bag(const uint64_t *T, long long rows, int dim, int bitlevel, const long long *ids, long long n_ids,
                                 const long long *offsets, long long n_bags, int mode, int dtype, void *out,
                                 unsigned long long *bad, void *scratch, hipStream_t s);
+// weighted bags: `weights` = float device buffer beside ids; w2b_embed_bagw_scratch(...) bytes of scratch, of which the
+// launch zeroes the first *head_bytes itself
+long long w2b_embed_bagw_scratch(long long n_ids, long long n_bags, int dim, int *cap_out, long long *segcap_out,
+                                 long long *head_bytes);
+hipError_t w2b_launch_embed_bag_weighted(const uint64_t *T, long long rows, int dim, int bitlevel, const long long *ids,
+                                         const float *weights, long long n_ids, const long long *offsets, long long n_bags,
+                                         int mode, int dtype, void *out, unsigned long long *bad, void *scratch, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

@@ -23,6 +23,7 @@
 // segments of W2B_EMBED_SPLIT ids are spread over all workgroups of a second launch, which add their partial T (and m)
 // into int32 scratch with integer atomics -- integer adds commute, so the result does not depend on the split -- and a
 // third launch converts.  The multiply, the divide and the conversion happen once per output element, after the last add.
+// Weighted bags (k_embed_bagw*): float chains in a fixed order instead of counts; see the comment above them.
 #include <hip/hip_fp16.h>
 
 #include "../../include/word2bits_embed.h"
@@ -225,10 +226,11 @@ __device__ __forceinline__ int bag_total(const BagCols<BL> &c, int k) {
   else return c.m + 2 * c.B[k] - 2 * c.A[k] - 4 * c.C[k];
 }
 
-// T, m -> the output element: one multiply, one division, one conversion
-__device__ __forceinline__ void bag_store(void *out, long long idx, int T, int m, int bitlevel, int mode, int dtype) {
+// T (the integer sum, exact as a float, or the weighted sum S), m -> the output element: one multiply, one division,
+// one conversion
+__device__ __forceinline__ void bag_store(void *out, long long idx, float T, int m, int bitlevel, int mode, int dtype) {
   const float q = bitlevel == 1 ? __uint_as_float(0x3EAAAAABu) : 0.25f;
-  float r = __fmul_rn((float)T, q);
+  float r = __fmul_rn(T, q);
   if (mode == W2B_EMBED_MEAN) r = m > 0 ? __fdiv_rn(r, (float)m) : 0.f;
   if (dtype == W2B_EMBED_F32) {
     reinterpret_cast<float *>(out)[idx] = r;
@@ -270,7 +272,7 @@ __global__ __launch_bounds__(kBagThreads) void k_embed_bag(const uint32_t *__res
 #pragma unroll
       for (int k = 0; k < kBagK; k++) {
         const int col = (cg * (kBagWaves * kBagK) + wave + kBagWaves * k) * 64 + lane;
-        if (k < c.nk && col < dim) bag_store(out, b * (long long)dim + col, bag_total(c, k), c.m, BL, mode, dtype);
+        if (k < c.nk && col < dim) bag_store(out, b * (long long)dim + col, (float)bag_total(c, k), c.m, BL, mode, dtype);
       }
     }
   }
@@ -317,7 +319,232 @@ __global__ __launch_bounds__(kBagThreads) void k_embed_bag_finish(int dim, int b
     const long long b = S.list[j];
     const int m = S.cnt[j];
     for (int col = threadIdx.x; col < dim; col += blockDim.x)
-      bag_store(out, b * (long long)dim + col, S.acc[(long long)j * dim + col], m, bitlevel, mode, dtype);
+      bag_store(out, b * (long long)dim + col, (float)S.acc[(long long)j * dim + col], m, bitlevel, mode, dtype);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- weighted bags
+// (k_embed_bagw, k_embed_bagw_long, k_embed_bagw_finish; the semantics are in the header.)  A float sum has an order, so
+// these kernels keep ONE chain per (bag, column) where the integer kernels count bits: the layout of bag_walk carries over
+// (a wavefront owns 64-column blocks, lane = column, the four waves take different blocks, ids and weights are
+// wave-uniform), and per id and column the code t is put together as a float pattern with integer operations and goes
+// into one __fmaf_rn -- at bitlevel 1, t = +-1, that is a sign flip of w and one add, the same value.  kBagK column chains
+// per lane are independent of each other and hide the latency of the dependent adds.  A padding, ignored or missing id
+// takes the weight +0 (and row 0): fmaf(+0, t, P) = P for every P these chains can hold (P is never -0: it starts at +0
+// and x + (-x) = +0), so no branch is needed.
+// The bag's positions are cut into segments of W2B_EMBED_WSEG; P_s of a segment starts at +0 and the bag's S adds the
+// P_s in order.  A bag of at most one segment is finished by its workgroup.  A longer bag is listed with a range of
+// rows in the float scratch part[segments][dim]; the second launch spreads the segments over all workgroups, each
+// stores its P_s there with plain vector stores (m goes through an integer atomic: integer adds commute), and the
+// third adds them in segment order, one thread per column.  There is no float atomic.  A bag that finds the list or
+// the scratch full is walked segment by segment by its own workgroup: the same operations in the same order.
+struct BagWScratch {
+  int *head, *list, *base, *cnt;      // head[0] = long bags listed, head[2..3] = segment rows handed out (64 bits)
+  float *part;
+  int cap;
+  long long segcap;
+};
+__host__ __device__ inline BagWScratch bagw_scratch(void *p, int cap, long long segcap) {
+  BagWScratch s;
+  s.head = (int *)p;
+  s.list = s.head + 16;
+  s.base = s.list + cap;
+  s.cnt = s.base + cap;
+  s.part = (float *)(s.cnt + cap);
+  s.cap = cap;
+  s.segcap = segcap;
+  return s;
+}
+
+// a weight the host form accepts: finite, and 0 or 2^-60 <= |w| <= 2^60 (on the bits: NaN and inf lie above 2^60)
+__host__ __device__ inline bool bagw_weight_ok(uint32_t bits) {
+  const uint32_t a = bits & 0x7FFFFFFFu;
+  return a == 0u || (a >= 0x21800000u && a <= 0x5D800000u);
+}
+
+template <int BL>
+struct BagWCols {
+  int h[kBagK];            // as BagCols
+  float P[kBagK];          // the chain of the current segment
+  int nk, m;
+};
+template <int BL>
+__device__ __forceinline__ void bagw_cols_init(BagWCols<BL> &c, int cg, int wave, int lane, int cbs) {
+  c.nk = 0;
+  c.m = 0;
+#pragma unroll
+  for (int k = 0; k < kBagK; k++) {
+    const int cb = cg * (kBagWaves * kBagK) + wave + kBagWaves * k;
+    if (cb < cbs) c.nk = k + 1;
+    c.h[k] = (cb < cbs ? cb : 0) * BL * 2 + (lane >> 5);
+    c.P[k] = 0.f;
+  }
+}
+
+// positions [start, end) of one segment, in order, onto the chains c.P (which the caller has set to +0)
+template <int BL>
+__device__ __forceinline__ void bagw_walk(const uint32_t *__restrict__ B32, long long nh, long long rows,
+                                          const long long *__restrict__ ids, const float *__restrict__ weights,
+                                          long long start, long long end, int lane, BagWCols<BL> &c, bool count_bad,
+                                          unsigned long long *bad) {
+  const int bit = lane & 31;
+  int nbad = 0;
+  for (long long i0 = start; i0 < end; i0 += 64) {
+    const bool in = i0 + lane < end;
+    const long long raw = in ? ids[i0 + lane] : -1;
+    const uint32_t wraw = in ? __float_as_uint(weights[i0 + lane]) : 0u;
+    const bool isbad = raw >= rows || (raw >= 0 && !bagw_weight_ok(wraw)), ok = raw >= 0 && !isbad;
+    c.m += (int)__popcll(__ballot(ok));
+    nbad += (int)__popcll(__ballot(isbad));
+    const int myid = ok ? (int)raw : 0;
+    const int myw = ok ? (int)wraw : 0;
+    const int cnt = end - i0 < 64 ? (int)(end - i0) : 64;
+    for (int j = 0; j < cnt; j += 4) {                     // j + 3 <= 63; lanes past the end hold row 0, weight +0
+      const uint32_t *rowp[4];
+      uint32_t w[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        rowp[u] = B32 + (long long)__builtin_amdgcn_readlane(myid, j + u) * nh;
+        w[u] = (uint32_t)__builtin_amdgcn_readlane(myw, j + u);
+      }
+#pragma unroll
+      for (int k = 0; k < kBagK; k++) {
+        if (k < c.nk) {
+          uint32_t sw[4], mw[4];
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            sw[u] = rowp[u][c.h[k]];
+            if constexpr (BL == 2) mw[u] = rowp[u][c.h[k] + 2];
+          }
+#pragma unroll
+          for (int u = 0; u < 4; u++) {                     // in the order of the ids: one chain
+            const uint32_t s = (sw[u] >> bit) & 1u;
+            if constexpr (BL == 1) {
+              c.P[k] = __fadd_rn(c.P[k], __uint_as_float(w[u] ^ (s << 31)));                    // = fmaf(w, +-1, P)
+            } else {
+              const uint32_t t = (0x3F800000u + ((mw[u] >> bit) & 1u) * 0x00C00000u) | (s << 31);   // +-1.0f, +-3.0f
+              c.P[k] = __fmaf_rn(__uint_as_float(w[u]), __uint_as_float(t), c.P[k]);
+            }
+          }
+        }
+      }
+    }
+  }
+  if (count_bad && nbad > 0 && lane == 0) atomicAdd(bad, (unsigned long long)nbad);
+}
+
+template <int BL>
+__global__ __launch_bounds__(kBagThreads) void k_embed_bagw(const uint32_t *__restrict__ B32, long long nh, long long rows, int dim,
+                                                            const long long *__restrict__ ids,
+                                                            const float *__restrict__ weights, long long n_ids,
+                                                            const long long *__restrict__ offsets, long long n_bags, int mode,
+                                                            int dtype, void *__restrict__ out, unsigned long long *bad,
+                                                            void *scratch, int cap, long long segcap) {
+  __shared__ int listed_s;
+  const BagWScratch S = bagw_scratch(scratch, cap, segcap);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cbs = (dim + 63) >> 6;
+  for (long long b = blockIdx.x; b < n_bags; b += gridDim.x) {
+    long long start, end;
+    const bool changed = bag_bounds(offsets, b, n_ids, &start, &end);
+    if (changed && threadIdx.x == 0) atomicAdd(bad, 1ull);
+    const long long nseg = (end - start + W2B_EMBED_WSEG - 1) / W2B_EMBED_WSEG;     // <= 4096
+    if (nseg > 1) {
+      __syncthreads();                                       // (the previous bag's readers of listed_s are done)
+      if (threadIdx.x == 0) {
+        listed_s = 0;
+        const int slot = atomicAdd(S.head, 1);
+        if (slot < cap) {
+          const unsigned long long first = atomicAdd((unsigned long long *)(S.head + 2), (unsigned long long)nseg);
+          listed_s = first + (unsigned long long)nseg <= (unsigned long long)segcap;
+          S.base[slot] = listed_s ? (int)first : 0;
+          S.list[slot] = listed_s ? (int)b : -1;             // -1: no rows left for it; pooled here
+        }
+      }
+      __syncthreads();
+      if (listed_s) continue;                                // k_embed_bagw_long pools it
+    }
+    for (int cg = 0; cg * (kBagWaves * kBagK) < cbs; cg++) {
+      BagWCols<BL> c;
+      bagw_cols_init(c, cg, wave, lane, cbs);
+      float sum[kBagK];
+#pragma unroll
+      for (int k = 0; k < kBagK; k++) sum[k] = 0.f;
+      for (long long s = 0; s < nseg; s++) {
+        const long long s0 = start + s * W2B_EMBED_WSEG;
+        const long long s1 = s0 + W2B_EMBED_WSEG < end ? s0 + W2B_EMBED_WSEG : end;
+        bagw_walk<BL>(B32, nh, rows, ids, weights, s0, s1, lane, c, wave == 0 && cg == 0, bad);
+#pragma unroll
+        for (int k = 0; k < kBagK; k++) {
+          sum[k] = __fadd_rn(sum[k], c.P[k]);
+          c.P[k] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kBagK; k++) {
+        const int col = (cg * (kBagWaves * kBagK) + wave + kBagWaves * k) * 64 + lane;
+        if (k < c.nk && col < dim) bag_store(out, b * (long long)dim + col, sum[k], c.m, BL, mode, dtype);
+      }
+    }
+  }
+}
+
+// the listed long bags: segment s of bag j goes to workgroup (j + s) mod gridDim.x and to row base[j] + s of part
+template <int BL>
+__global__ __launch_bounds__(kBagThreads) void k_embed_bagw_long(const uint32_t *__restrict__ B32, long long nh, long long rows,
+                                                                 int dim, const long long *__restrict__ ids,
+                                                                 const float *__restrict__ weights, long long n_ids,
+                                                                 const long long *__restrict__ offsets,
+                                                                 unsigned long long *bad, void *scratch, int cap,
+                                                                 long long segcap) {
+  const BagWScratch S = bagw_scratch(scratch, cap, segcap);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int cbs = (dim + 63) >> 6;
+  const int nl = S.head[0] < cap ? S.head[0] : cap;
+  const int G = (int)gridDim.x;
+  for (int j = 0; j < nl; j++) {
+    if (S.list[j] < 0) continue;
+    long long start, end;
+    bag_bounds(offsets, S.list[j], n_ids, &start, &end);
+    const long long nseg = (end - start + W2B_EMBED_WSEG - 1) / W2B_EMBED_WSEG;
+    const long long first = S.base[j];                       // first + nseg <= segcap, or the bag were not listed
+    for (long long s = ((int)blockIdx.x - j % G + G) % G; s < nseg; s += G) {
+      const long long s0 = start + s * W2B_EMBED_WSEG;
+      const long long s1 = s0 + W2B_EMBED_WSEG < end ? s0 + W2B_EMBED_WSEG : end;
+      for (int cg = 0; cg * (kBagWaves * kBagK) < cbs; cg++) {
+        BagWCols<BL> c;
+        bagw_cols_init(c, cg, wave, lane, cbs);
+        bagw_walk<BL>(B32, nh, rows, ids, weights, s0, s1, lane, c, wave == 0 && cg == 0, bad);
+#pragma unroll
+        for (int k = 0; k < kBagK; k++) {
+          const int col = (cg * (kBagWaves * kBagK) + wave + kBagWaves * k) * 64 + lane;
+          if (k < c.nk && col < dim) S.part[(first + s) * dim + col] = c.P[k];
+        }
+        if (wave == 0 && cg == 0 && lane == 0) atomicAdd(S.cnt + j, c.m);
+      }
+    }
+  }
+}
+
+// S = +0, + P_0, + P_1 ... in segment order, one thread per column; then the multiply, the division and the conversion
+__global__ __launch_bounds__(kBagThreads) void k_embed_bagw_finish(int dim, int bitlevel, long long n_ids,
+                                                                   const long long *__restrict__ offsets, int mode, int dtype,
+                                                                   void *__restrict__ out, void *scratch, int cap,
+                                                                   long long segcap) {
+  const BagWScratch S = bagw_scratch(scratch, cap, segcap);
+  const int nl = S.head[0] < cap ? S.head[0] : cap;
+  const int chunks = (dim + kBagThreads - 1) / kBagThreads;
+  for (long long w = blockIdx.x; w < (long long)nl * chunks; w += gridDim.x) {
+    const int j = (int)(w / chunks), col = (int)(w % chunks) * kBagThreads + (int)threadIdx.x;
+    if (S.list[j] < 0 || col >= dim) continue;
+    const long long b = S.list[j];
+    long long start, end;
+    bag_bounds(offsets, b, n_ids, &start, &end);
+    const long long nseg = (end - start + W2B_EMBED_WSEG - 1) / W2B_EMBED_WSEG;
+    const float *p = S.part + (long long)S.base[j] * dim + col;
+    float sum = 0.f;
+    for (long long s = 0; s < nseg; s++) sum = __fadd_rn(sum, p[s * dim]);
+    bag_store(out, b * (long long)dim + col, sum, S.cnt[j], bitlevel, mode, dtype);
   }
 }
 
@@ -383,5 +610,53 @@ hipError_t w2b_launch_embed_bag(const uint64_t *T, long long rows, int dim, int 
   }
   if (n_ids > W2B_EMBED_SPLIT)
     hipLaunchKernelGGL(k_embed_bag_finish, dim3(gfin), dim3(kBagThreads), 0, s, dim, bitlevel, mode, dtype, out, scratch, cap);
+  return hipGetLastError();
+}
+
+// weighted bags: `cap` list slots as above and `segcap` rows of part -- every segment of every long bag when the bags do
+// not overlap (a bag of n ids has at most n / W2B_EMBED_WSEG + 1 segments)
+long long w2b_embed_bagw_scratch(long long n_ids, long long n_bags, int dim, int *cap_out, long long *segcap_out,
+                                 long long *head_bytes) {
+  long long cap = n_ids / W2B_EMBED_WSEG + 1;
+  if (cap > n_bags) cap = n_bags;
+  if (cap < 1) cap = 1;
+  const long long segcap = n_ids / W2B_EMBED_WSEG + cap;    // < 2^31: n_ids <= 2^40
+  *cap_out = (int)cap;
+  *segcap_out = segcap;
+  *head_bytes = (16 + 3 * cap) * 4;
+  return *head_bytes + segcap * (long long)dim * 4;
+}
+
+hipError_t w2b_launch_embed_bag_weighted(const uint64_t *T, long long rows, int dim, int bitlevel, const long long *ids,
+                                         const float *weights, long long n_ids, const long long *offsets, long long n_bags,
+                                         int mode, int dtype, void *out, unsigned long long *bad, void *scratch, hipStream_t s) {
+  if (n_bags <= 0) return hipSuccess;
+  int cap = 0;
+  long long segcap = 0, head = 0;
+  w2b_embed_bagw_scratch(n_ids, n_bags, dim, &cap, &segcap, &head);
+  hipError_t he = hipMemsetAsync(scratch, 0, (size_t)head, s);      // the rows of part are stored whole before they are read
+  if (he != hipSuccess) return he;
+  const uint32_t *B32 = (const uint32_t *)T;
+  const long long nh = (long long)((dim + 63) / 64) * bitlevel * 2;
+  const unsigned grid = (unsigned)(n_bags < (1ll << 22) ? n_bags : (1ll << 22));
+  const long long fin = (long long)cap * ((dim + kBagThreads - 1) / kBagThreads);
+  const unsigned glong = 2048, gfin = (unsigned)(fin < 4096 ? fin : 4096);
+  const bool longs = n_ids > W2B_EMBED_WSEG;
+  if (bitlevel == 1) {
+    hipLaunchKernelGGL(k_embed_bagw<1>, dim3(grid), dim3(kBagThreads), 0, s, B32, nh, rows, dim, ids, weights, n_ids, offsets,
+                       n_bags, mode, dtype, out, bad, scratch, cap, segcap);
+    if (longs)
+      hipLaunchKernelGGL(k_embed_bagw_long<1>, dim3(glong), dim3(kBagThreads), 0, s, B32, nh, rows, dim, ids, weights, n_ids,
+                         offsets, bad, scratch, cap, segcap);
+  } else {
+    hipLaunchKernelGGL(k_embed_bagw<2>, dim3(grid), dim3(kBagThreads), 0, s, B32, nh, rows, dim, ids, weights, n_ids, offsets,
+                       n_bags, mode, dtype, out, bad, scratch, cap, segcap);
+    if (longs)
+      hipLaunchKernelGGL(k_embed_bagw_long<2>, dim3(glong), dim3(kBagThreads), 0, s, B32, nh, rows, dim, ids, weights, n_ids,
+                         offsets, bad, scratch, cap, segcap);
+  }
+  if (longs)
+    hipLaunchKernelGGL(k_embed_bagw_finish, dim3(gfin), dim3(kBagThreads), 0, s, dim, bitlevel, n_ids, offsets, mode, dtype, out,
+                       scratch, cap, segcap);
   return hipGetLastError();
 }

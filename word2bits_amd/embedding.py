@@ -5,6 +5,7 @@
     sent = emb.bag(ids, offsets, mode="mean")                   # numpy [n_bags, dim]; bag b = ids[offsets[b]:offsets[b+1]]
     x = emb.torch_lookup(token_ids, dtype=torch.bfloat16)       # torch tensor on the device, ids from any device
     s = emb.torch_bag(token_ids, offsets, mode="sum")
+    v = emb.torch_bag(token_ids, offsets, mode="mean", per_sample_weights=sif)   # weighted pooling (SIF, TF-IDF, a mask)
 
 Lookup and pooling run on the MI355X (w2b_kernels_embed.hip); there is no CPU path in this module.
 """
@@ -88,14 +89,25 @@ class PackedEmbedding:
                                             C.c_void_p(out.ctypes.data)))
         return out
 
-    def bag(self, ids, offsets, mode="sum", dtype="float32"):
-        """Sum or mean of the rows of every bag: numpy [len(offsets) - 1, dim]."""
+    def bag(self, ids, offsets, mode="sum", dtype="float32", per_sample_weights=None):
+        """Sum or mean of the rows of every bag: numpy [len(offsets) - 1, dim].  per_sample_weights (float array of ids'
+        shape, cast to float32) weighs every id's row: the weighted bag of the header, whose mean still divides by the
+        number of ids."""
         code, m = _dtype_code(dtype), _mode_code(mode)
-        ids = np.ascontiguousarray(ids, np.int32).ravel()
+        ids = np.ascontiguousarray(ids, np.int32)
+        if per_sample_weights is not None and np.shape(per_sample_weights) != ids.shape:
+            raise ValueError("per_sample_weights must have the shape of ids")
+        ids = ids.ravel()
         offsets = np.ascontiguousarray(offsets, np.int64).ravel()
         if offsets.size < 1:
             raise ValueError("offsets has n_bags + 1 entries")
         out = self._out((offsets.size - 1, self.dim), code)
+        if per_sample_weights is not None:
+            w = np.ascontiguousarray(per_sample_weights, np.float32).ravel()
+            _lib.check(self._L.w2b_embed_bag_weighted(self._h, ids.size, ids.ctypes.data_as(_lib.i32p),
+                                                      w.ctypes.data_as(_lib.f32p), offsets.size - 1,
+                                                      offsets.ctypes.data_as(_lib.i64p), m, code, C.c_void_p(out.ctypes.data)))
+            return out
         _lib.check(self._L.w2b_embed_bag(self._h, ids.size, ids.ctypes.data_as(_lib.i32p), offsets.size - 1,
                                          offsets.ctypes.data_as(_lib.i64p), m, code, C.c_void_p(out.ctypes.data)))
         return out
@@ -113,11 +125,23 @@ class PackedEmbedding:
     def bag_device(self, n_ids, n_bags, mode="sum", dtype="float32"):
         _lib.check(self._L.w2b_embed_bag_device(self._h, int(n_ids), int(n_bags), _mode_code(mode), _dtype_code(dtype)))
 
+    def reserve_weights(self, max_ids):
+        """Address of the library's float32 [max_ids] weights buffer (w2b_embed_reserve_weights); it moves only when it
+        grows itself."""
+        p = C.c_void_p()
+        _lib.check(self._L.w2b_embed_reserve_weights(self._h, int(max_ids), C.byref(p)))
+        return p.value
+
+    def bag_weighted_device(self, n_ids, n_bags, mode="sum", dtype="float32"):
+        _lib.check(self._L.w2b_embed_bag_weighted_device(self._h, int(n_ids), int(n_bags), _mode_code(mode),
+                                                         _dtype_code(dtype)))
+
     def synchronize(self):
         _lib.check(self._L.w2b_embed_synchronize(self._h))
 
     def bad_ids(self):
-        """Ids >= rows and clamped bags that the device form has ignored since the last call (synchronises, resets)."""
+        """Ids >= rows, clamped bags and refused weights that the device form has ignored since the last call
+        (synchronises, resets)."""
         n = C.c_int64()
         _lib.check(self._L.w2b_embed_bad_ids(self._h, C.byref(n)))
         return n.value
@@ -143,11 +167,15 @@ class PackedEmbedding:
         return (self._view(ids_p, max(int(max_ids), 1), "<i8")[:int(max_ids)],
                 self._view(off_p, int(max_bags) + 1, "<i8"), out[:nout * self.dim].view(nout, self.dim))
 
+    def staging_weights(self, max_ids):
+        """torch view of the weights buffer: float32 [max_ids]; valid until a later call reserves more weights."""
+        return self._view(self.reserve_weights(max_ids), max(int(max_ids), 1), "<f4")[:int(max_ids)]
+
     def _finish(self, out, copy, what):
         self.synchronize()
         bad = self.bad_ids()
         if bad:
-            raise _lib.W2bError(_lib.W2B_EINVAL, "%s: %d ids >= rows or bag bounds outside the ids" % (what, bad))
+            raise _lib.W2bError(_lib.W2B_EINVAL, "%s: %d ids >= rows, bag bounds outside the ids or weights out of range" % (what, bad))
         return out.clone() if copy else out
 
     def torch_lookup(self, ids, dtype=None, copy=True):
@@ -163,24 +191,33 @@ class PackedEmbedding:
             self.lookup_device(n, dtype)
         return self._finish(out[:n].view(tuple(ids.shape) + (self.dim,)), copy, "torch_lookup")
 
-    def torch_bag(self, ids, offsets, mode="sum", dtype=None, copy=True):
-        """Sum or mean per bag (torch integer tensors on any device; offsets has n_bags + 1 entries): [n_bags, dim]."""
+    def torch_bag(self, ids, offsets, mode="sum", dtype=None, copy=True, per_sample_weights=None):
+        """Sum or mean per bag (torch integer tensors on any device; offsets has n_bags + 1 entries): [n_bags, dim].
+        per_sample_weights (float tensor of ids' shape on any device, cast to float32) as in PackedEmbedding.bag."""
         import torch
         dtype = torch.float32 if dtype is None else dtype
         n, nb = ids.numel(), offsets.numel() - 1
         if nb < 0:
             raise ValueError("offsets has n_bags + 1 entries")
+        if per_sample_weights is not None and tuple(per_sample_weights.shape) != tuple(ids.shape):
+            raise ValueError("per_sample_weights must have the shape of ids")
         ids_t, off_t, out = self.staging(n, nb, dtype)
+        w_t = self.staging_weights(n) if per_sample_weights is not None else None
         if nb:
             if n:
                 ids_t.copy_(ids.reshape(-1))
+                if w_t is not None:
+                    w_t.copy_(per_sample_weights.reshape(-1))             # copy_ casts to float32
             off_t.copy_(offsets.reshape(-1))
             torch.cuda.synchronize()
-            self.bag_device(n, nb, mode, dtype)
+            if w_t is not None:
+                self.bag_weighted_device(n, nb, mode, dtype)
+            else:
+                self.bag_device(n, nb, mode, dtype)
         return self._finish(out[:nb], copy, "torch_bag")
 
     def timing(self):
-        """(kernel ms, launches, bytes moved: packed words read + output written) since the last call."""
+        """(kernel ms, launches, bytes moved: packed words (and weights) read + output written) since the last call."""
         ms, n, b = C.c_double(), C.c_int64(), C.c_double()
         _lib.check(self._L.w2b_embed_timing_read(self._h, C.byref(ms), C.byref(n), C.byref(b)))
         return ms.value, n.value, b.value
