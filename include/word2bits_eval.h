@@ -309,6 +309,55 @@ int w2b_eval_vectors_text(w2b_eval *e, const char *queries, int64_t len, int32_t
 int w2b_vector_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel,
                            const float *x /* [dim] */, int32_t normalize, float *S_out, float *score_out);
 
+/* ---- 3CosMul: the multiplicative analogy rule, on both packed modes ----------------------------------------------------
+ * Every other analogy answer of this header is 3CosAdd, the additive (M[b2] - M[b1]) + M[b3].  This one is 3CosMul (Levy &
+ * Goldberg 2014; gensim's most_similar_cosmul): for the question (b1, b2, b3) -- "b1 is to b2 as b3 is to ?", positives b2
+ * and b3, negative b1 -- every row c has three similarities u_i, float32, shifted to [0, 1], and the score
+ *     score = (u2 * u3) / (u1 + eps),      eps = 1e-6f (the float 0x358637BD).
+ * The multiply, the add and the division are each ONE float32 operation rounded to nearest, nothing is contracted, the
+ * division is the correctly rounded one.  The additive rule lets one large term dominate; this one balances the three.
+ *   bits handle: A_i(c) = size - H(b_i, c), the number of columns on which rows b_i and c agree, an exact integer;
+ *     u_i = (float)A_i / (float)size, one correctly rounded division -- (1 + cos) / 2 without the detour.  Both conversions
+ *     are exact for size <= 2^24; a handle with a larger size is W2B_EINVAL.  (u depends on A alone: a host-built table of
+ *     size + 1 floats, as w(r) is in codes mode.)
+ *   codes handle: cos_i = ((float)J(b_i,c) * w(b_i)) * w(c), the expression that w2b_eval_neighbors scores by, J and w as in
+ *     codes mode; u_i = (1.0f + cos_i) * 0.5f, one add and one multiply.
+ *   no subnormals: on a bits handle u is 0 or >= 2^-24; on a codes handle cos may overshoot +-1 by an ulp, so that 1 + cos is
+ *     0, +-2^-24 or +-2^-23 at its smallest and u is 0 or |u| >= 2^-25.  So u2 * u3 is 0 or at least 2^-50 in magnitude, u1 +
+ *     eps stays positive (at least eps - 2^-24) and at most 1 + 2^-19, and the quotient is 0 or between 2^-51 and 2^21 in
+ *     magnitude: no operand and no result is subnormal, none overflows, and the result does not depend on how an instruction
+ *     treats subnormals.
+ *   fp32 handle: W2B_EINVAL ("not available on an fp32 handle: load the file with bits or codes"); w2b_eval_load_bits and
+ *     w2b_eval_load_codes read the reference's float format and reduce it.  Handles made by *_from_trainer in bits / codes
+ *     mode work like loaded ones.
+ *   answers: the rows c other than b1, b2, b3 with score > 0, by score descending, equal float scores in ascending row order
+ *     -- the codes key, score bits << 32 | ~row, on both handle kinds.  best / bestd are [nq][k] in the shape of
+ *     w2b_eval_topk: a short list ends in row -1 / score 0, bestd may be NULL.  1 <= k <= W2B_EVAL_MAX_K; nq == 0 is W2B_OK.
+ * Everything is validated before anything is launched -- k and nq first (so a NULL handle with a bad k is W2B_EINVAL for the
+ * k, as in w2b_eval_bag), then the handle, then the rows: a row outside [0, words) is W2B_EINVAL, naming the question -- with
+ * the cause in w2b_last_error(); on error best / bestd are untouched.
+ * w2b_eval_set_topk_scratch bounds the scratch of a launch as it does for w2b_eval_topk on the same handle, and results never
+ * depend on it.  w2b_eval_timing_read counts these launches, macs = 3 x questions x rows x size on both handle kinds.
+ * The scans: word2bits_amd/csrc/w2b_kernels_evalcosmul.hip (bits: three popcounts per word, a float epilogue behind an exact
+ * prefilter) and the COSMUL instance of the codes scan (w2b_kernels_evalcodes.hip: the same matrix-core products, another
+ * epilogue). */
+int w2b_eval_cosmul(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
+                    int32_t k, int32_t *best, float *bestd);
+/* The text form of `./nearest ... bits|codes cosmul`: the format of w2b_eval_nearest_text, but every non-empty line is
+ * three words A B C.  Any other count gives "<words>: expected 3 words\n"; a word that w2b_eval_lookup does not find gives
+ * "<words>: not in vocabulary: <WORD>\n" (the first such word).  All valid lines are scored in one w2b_eval_cosmul batch. */
+int w2b_eval_cosmul_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out, int64_t *out_len);
+/* w2b_eval_transcript byte for byte, except that each question's answer comes from w2b_eval_cosmul with k = 1 (bits and
+ * codes handles; `./compute_accuracy FILE <bitlevel> <threshold> bits|codes cosmul`). */
+int w2b_eval_transcript_cosmul(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len);
+/* Host twin of the 3CosMul kernels (pure C, no device): ONE question (b1, b2, b3) against EVERY row c of
+ * packed[words][bitlevel * ceil(dim / 64)], the question's own rows included: u_out[3][words] = u1, u2, u3 and
+ * score_out[words] = the float score, with the semantics above for bitlevel 1 (bits) or 2 (codes).  Either output may be
+ * NULL.  W2B_EINVAL: a bitlevel other than 1 or 2, a row outside [0, words), dim > 2^24 at bitlevel 1. */
+int w2b_cosmul_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel,
+                           int64_t b1, int64_t b2, int64_t b3, float *u_out /* [3][words] or NULL */,
+                           float *score_out /* [words] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

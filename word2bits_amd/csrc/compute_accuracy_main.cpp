@@ -1,5 +1,5 @@
 // compute_accuracy_main.cpp -- drop-in for the reference's evaluator program (ref src/compute-accuracy.c:63-189):
-//   ./compute_accuracy <FILE> <bitlevel> <threshold> [fma|nofma|bits|codes] < questions-words.txt
+//   ./compute_accuracy <FILE> <bitlevel> <threshold> [fma|nofma|bits|codes] [cosmul] < questions-words.txt
 // Same positional arguments, same stdout.  The scan runs on the MI355X through include/word2bits_eval.h.
 // The optional 4th argument (or W2B_EVAL_FUSED=0|1) selects which build of the reference the scores are
 // bit-identical to: "fma" (default; the reference's own Makefile flags on an FMA-capable host) or "nofma"
@@ -8,6 +8,8 @@
 // with ties to the lowest row (include/word2bits_eval.h, "bits mode"); the transcript keeps the reference's format.
 // "codes" (2-bit models only; <bitlevel> is ignored) does the same for 2-bit rows: exact integer dot products on the packed
 // rows, scaled by the rows' lengths in a fixed float sequence ("codes mode").
+// "cosmul" as a 5th argument (after bits or codes) answers every question by the multiplicative rule 3CosMul instead of the
+// additive one (w2b_eval_transcript_cosmul); the transcript keeps the reference's format.
 #include "w2b_eval_cli.h"
 
 int main(int argc, char **argv) {
@@ -19,11 +21,13 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Optional 4th argument: fma (default) | nofma = the build of the reference whose arithmetic is "
                     "reproduced; bits = 1-bit models only: exact integer scores on the bit-packed rows, ties to the lowest "
                     "row (<bitlevel> is ignored); codes = 2-bit models only: exact integer dot products on the bit-packed "
-                    "rows, scaled by the rows' lengths (<bitlevel> is ignored)\n");
+                    "rows, scaled by the rows' lengths (<bitlevel> is ignored).  Optional 5th argument (after bits or codes): cosmul "
+                    "= every question is answered by the multiplicative rule 3CosMul instead of the additive one\n");
     return 0;
   }
   const int bitlevel = argc > 2 ? atoi(argv[2]) : 0;          // ref :78
   const long long threshold = argc > 3 ? atoi(argv[3]) : 0;   // ref :79
+  const bool is_cosmul = argc > 5 && !strcmp(argv[5], "cosmul");
   return w2b_eval_cli("compute_accuracy", argv[1], bitlevel, threshold, argc > 4 ? argv[4] : nullptr,
-                      w2b_eval_transcript);
+                      is_cosmul ? w2b_eval_transcript_cosmul : w2b_eval_transcript);
 }

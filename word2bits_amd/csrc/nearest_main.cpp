@@ -1,5 +1,5 @@
 // nearest_main.cpp -- what is near a word, and the best few answers to an analogy:
-//   ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits|codes] [signed|bag|vector] < queries
+//   ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits|codes] [signed|bag|vector|cosmul] < queries
 // FILE is a vectors file in the reference's binary format or a bit-packed .w2bp file, loaded exactly like
 // ./compute_accuracy loads it (ref src/compute-accuracy.c:80-112).  One query per input line: one word = its k
 // nearest words, three words A B C = the k best answers to "A is to B as C is to ?" (ref :155-177 with N = k).
@@ -12,11 +12,13 @@
 // nearest to their unnormalised sum, the line's own words excluded (w2b_eval_bag_text): a sentence, a ten-word phrase.
 // "vector" (after the mode; every mode): every line is `size` numbers, a float vector of the model's width, and is answered
 // with the k rows nearest to it by cosine, nothing excluded (w2b_eval_vectors_text with normalize = 1).
+// "cosmul" (after the mode; bits and codes only): every line is three words A B C and is answered with the k best answers
+// to "A is to B as C is to ?" by the multiplicative rule 3CosMul (w2b_eval_cosmul_text).
 #include "w2b_eval_cli.h"
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    printf("Usage: ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits|codes] [signed|bag|vector] < queries\nwhere FILE contains word "
+    printf("Usage: ./nearest <FILE> <k> [bitlevel] [threshold] [fma|nofma|bits|codes] [signed|bag|vector|cosmul] < queries\nwhere FILE contains word "
            "projections and every input line is one word (its k nearest words) or three words A B C (the k best "
            "answers to A : B = C : ?); 1 <= k <= %d; bits = 1-bit models only: exact integer scores on the bit-packed "
            "rows, ties to the lowest row (bitlevel is ignored); codes = 2-bit models only: exact integer dot products on "
@@ -24,7 +26,9 @@ int main(int argc, char **argv) {
            "input line is 1 to %d words, each with an optional + or - in front: the k rows nearest to that signed sum; bag (after "
            "the mode, bits and codes only) = every input line is one bag of 1 to %d words: the k rows nearest to their sum, the "
            "line's own words excluded; vector (after the mode, every mode) = every input line is a float vector of the model's "
-           "width, as many numbers as a row has: the k rows nearest to it by cosine, nothing excluded\n",
+           "width, as many numbers as a row has: the k rows nearest to it by cosine, nothing excluded; cosmul (after the mode, "
+           "bits and codes only) = every input line is three words A B C: the k best answers to A : B = C : ? by the "
+           "multiplicative rule 3CosMul\n",
            W2B_EVAL_MAX_K, W2B_EVAL_MAX_TERMS, W2B_EVAL_MAX_BAG);
     return 0;
   }
@@ -36,9 +40,10 @@ int main(int argc, char **argv) {
   const int bitlevel = argc > 3 ? atoi(argv[3]) : 0;
   const long long threshold = argc > 4 ? atoi(argv[4]) : 0;
   const bool is_signed = argc > 6 && !strcmp(argv[6], "signed"), is_bag = argc > 6 && !strcmp(argv[6], "bag");
-  const bool is_vector = argc > 6 && !strcmp(argv[6], "vector");
+  const bool is_vector = argc > 6 && !strcmp(argv[6], "vector"), is_cosmul = argc > 6 && !strcmp(argv[6], "cosmul");
   return w2b_eval_cli("nearest", argv[1], bitlevel, threshold, argc > 5 ? argv[5] : nullptr,
-                      [k, is_signed, is_bag, is_vector](w2b_eval *e, const char *in, int64_t len, char **txt, int64_t *txt_len) {
+                      [k, is_signed, is_bag, is_vector, is_cosmul](w2b_eval *e, const char *in, int64_t len, char **txt, int64_t *txt_len) {
+                        if (is_cosmul) return w2b_eval_cosmul_text(e, in, len, k, txt, txt_len);
                         if (is_vector) return w2b_eval_vectors_text(e, in, len, 1, k, txt, txt_len);
                         if (is_bag) return w2b_eval_bag_text(e, in, len, 1, k, txt, txt_len);
                         return is_signed ? w2b_eval_combine_text(e, in, len, k, txt, txt_len)

@@ -3,10 +3,10 @@
 // GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
 // w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
 // adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms, w2b_kernels_evalvec.hip
-// the float-vector question on them.  No arithmetic on scores happens here (the exceptions are question weights: the bag
+// the float-vector question on them, w2b_kernels_evalcosmul.hip the 3CosMul scan on 1-bit rows.  No arithmetic on scores happens here (the exceptions are question weights: the bag
 // question's 1 / sqrt(N_T), built from the integer the device sums, and the vector question's wx with the fp32 handle's
-// vec = x * wx) and there is no CPU fallback (w2b_codes_scores_host, w2b_bag_scores_host and w2b_vector_scores_host are
-// the tests' twins of the kernels).
+// vec = x * wx; and the 3CosMul table u = A / size of a bits handle) and there is no CPU fallback (w2b_codes_scores_host,
+// w2b_bag_scores_host, w2b_vector_scores_host and w2b_cosmul_scores_host are the tests' twins of the kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
@@ -59,6 +59,7 @@ struct w2b_eval {
   // weights [3][cap_q]
   int codes = 0;
   float *wrow = nullptr;                                // [rows_padded] w(c), 0 past the vocabulary
+  float *utab = nullptr;                                // bits, w2b_eval_cosmul: u by agreement count [size + 1] (made on first use)
   // per-call scratch (grown on demand)
   float *Q = nullptr;
   int32_t *b123 = nullptr;
@@ -87,6 +88,7 @@ static void eval_release(w2b_eval *e) {
   if (e->M) (void)hipFree(e->M);
   if (e->B) (void)hipFree(e->B);
   if (e->wrow) (void)hipFree(e->wrow);
+  if (e->utab) (void)hipFree(e->utab);
   if (e->P) (void)hipFree(e->P);
   if (e->Q) (void)hipFree(e->Q);
   if (e->b123) (void)hipFree(e->b123);
@@ -586,6 +588,78 @@ extern "C" int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int6
 }
 
 namespace {
+constexpr int64_t kCosmulMaxBits = 1ll << 24;   // the largest 1-bit size whose agreement counts are exact in float32
+constexpr float kCosmulEps = 1e-6f;             // 0x358637BD
+
+// u by agreement count on 1-bit rows: (float)A / (float)dim, one correctly rounded division, A = 0..dim
+std::vector<float> cosmul_utab(int64_t dim) {
+  std::vector<float> u((size_t)dim + 1);
+  for (int64_t a = 0; a <= dim; a++) u[(size_t)a] = (float)a / (float)dim;
+  return u;
+}
+
+// score = (u2 * u3) / (u1 + eps), one rounding per operation
+inline float cosmul_score(float u1, float u2, float u3) {
+#pragma clang fp contract(off)
+  const float num = u2 * u3;
+  const float den = u1 + kCosmulEps;
+  return num / den;
+}
+}  // namespace
+
+// Host twin of the 3CosMul kernels.  The float sequence of the header, one rounding per operation (this file is built with
+// -ffp-contract=off, and the function says so again).
+extern "C" int w2b_cosmul_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t b1,
+                                      int64_t b2, int64_t b3, float *u_out, float *score_out) {
+#pragma clang fp contract(off)
+  const std::string who = "w2b_cosmul_scores_host";
+  if (!packed || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (bitlevel == 1 && dim > kCosmulMaxBits) return efail(W2B_EINVAL, who + ": size must be at most 2^24 on 1-bit rows");
+  if (b1 < 0 || b2 < 0 || b3 < 0 || b1 >= words || b2 >= words || b3 >= words)
+    return efail(W2B_EINVAL, who + ": question row out of range");
+  const int64_t b[3] = {b1, b2, b3};
+  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
+  auto valid = [&](int64_t blk) { return (blk + 1) * 64 <= dim ? ~0ull : (1ull << (dim - blk * 64)) - 1; };   // padding bits do not count
+  std::vector<float> u((size_t)(3 * words));
+  if (bitlevel == 1) {
+    const std::vector<float> ut = cosmul_utab(dim);
+    for (int t = 0; t < 3; t++) {
+      const uint64_t *rt = packed + b[t] * wpr;
+      for (int64_t c = 0; c < words; c++) {
+        const uint64_t *rc = packed + c * wpr;
+        int64_t h = 0;
+        for (int64_t w = 0; w < nb; w++) h += __builtin_popcountll((rt[w] ^ rc[w]) & valid(w));
+        u[(size_t)(t * words + c)] = ut[(size_t)(dim - h)];
+      }
+    }
+  } else {
+    std::vector<int32_t> J((size_t)(3 * words));
+    if (int rc = w2b_codes_scores_host(packed, words, dim, b1, b2, b3, J.data(), nullptr)) return rc;
+    const std::vector<float> wt = codes_weights(dim);
+    auto weight = [&](const uint64_t *r) {
+      int64_t n3 = 0;
+      for (int64_t blk = 0; blk < nb; blk++) n3 += __builtin_popcountll(r[2 * blk + 1] & valid(blk));
+      return wt[(size_t)n3];
+    };
+    for (int t = 0; t < 3; t++) {
+      const float wb = weight(packed + b[t] * wpr);
+      for (int64_t c = 0; c < words; c++) {
+        const float pj = (float)J[(size_t)(t * words + c)] * wb;
+        const float cs = pj * weight(packed + c * wpr);
+        const float one = 1.0f + cs;
+        u[(size_t)(t * words + c)] = one * 0.5f;
+      }
+    }
+  }
+  if (u_out) memcpy(u_out, u.data(), u.size() * 4);
+  if (score_out)
+    for (int64_t c = 0; c < words; c++)
+      score_out[c] = cosmul_score(u[(size_t)c], u[(size_t)(words + c)], u[(size_t)(2 * words + c)]);
+  return W2B_OK;
+}
+
+namespace {
 constexpr int64_t kBagMaxSize = 58254;   // the largest size with 9 * 4096 * size < 2^31
 
 // what w2b_eval_bag and its host twin refuse in one bag (null: nothing)
@@ -1006,6 +1080,27 @@ struct ScanBits {
   float score(unsigned long long key) const { return (float)(int32_t)(key >> 32) / (float)e->size; }   // one correctly rounded division
 };
 
+// The 3CosMul question (include/word2bits_eval.h, "3CosMul"): the chunks, scratch and selection state of the three-row scans
+// above, another scan kernel, float keys on both handle kinds.
+struct ScanCosmulBits : ScanBits {
+  using ScanBits::ScanBits;
+  hipError_t timed(int64_t n, int64_t, const Rows3 &d) {
+    return w2b_launch_cosmul_bits((const uint32_t *)e->B, (int)e->words, (int)e->size, e->utab, (int)n, d.d1, d.d2, d.d3, k,
+                                  splits, rpb, slots, merged, e->stream);
+  }
+  float score(unsigned long long key) const { return f32_score(key); }
+};
+struct ScanCosmulCodes : ScanCodes {
+  using ScanCodes::ScanCodes;
+  hipError_t timed(int64_t n, int64_t, const Rows3 &d) {
+    const uint32_t *B32 = (const uint32_t *)e->B;
+    hipError_t le = w2b_launch_codes_operands(B32, (int)e->size, (int)n, e->wrow, d.d1, d.d2, d.d3, e->P, e->Q, e->stream);
+    if (le != hipSuccess) return le;
+    return w2b_launch_codes_scan_cosmul(B32, (int)e->words, (int)e->size, e->wrow, e->P, e->Q, (int)n, d.d1, d.d2, d.d3, k,
+                                        t.bound, t.bkt, t.slots, t.cnt, t.merged, e->stream);
+  }
+};
+
 struct EventPair;
 
 // The bags of w2b_eval_bag.  A chunk's ids go up as they are, its bounds rebased to the chunk's first id; with `exclude`
@@ -1341,6 +1436,31 @@ extern "C" int w2b_eval_vectors(w2b_eval *e, int64_t nq, const float *x, int32_t
   return eval_scan_chunks(e, ScanVectorsF(e, k), std::move(in), nq, best, bestd, who, 1.0);
 }
 
+// The 3CosMul question: what does not depend on the handle first, then the handle, then the rows; the chunks.
+extern "C" int w2b_eval_cosmul(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t k,
+                               int32_t *best, float *bestd) {
+  const std::string who = "w2b_eval_cosmul";
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  if (nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !best))) return efail(W2B_EINVAL, who + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes)
+    return efail(W2B_EINVAL, who + ": not available on an fp32 handle: load the file with bits or codes");
+  if (e->bits && e->size > kCosmulMaxBits) return efail(W2B_EINVAL, who + ": size must be at most 2^24 on a bits handle");
+  for (int64_t q = 0; q < nq; q++)
+    if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words)
+      return efail(W2B_EINVAL, who + ": question " + std::to_string(q) + ": row out of range");
+  if (nq == 0) return W2B_OK;
+  EHIP(hipSetDevice(e->device));
+  if (e->bits && !e->utab) {
+    const std::vector<float> u = cosmul_utab(e->size);
+    if (hipMalloc(&e->utab, u.size() * 4) != hipSuccess) return efail(W2B_ENOMEM, who + ": device allocation failed");
+    EHIP(hipMemcpy(e->utab, u.data(), u.size() * 4, hipMemcpyHostToDevice));
+  }
+  const Rows3 in{b1, b2, b3};
+  if (e->bits) return eval_scan_chunks(e, ScanCosmulBits(e, nq, k), in, nq, best, bestd, who, 3.0);
+  return eval_scan_chunks(e, ScanCosmulCodes(e, k), in, nq, best, bestd, who, 3.0);
+}
+
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                              int32_t *best, float *bestd) {
   return eval_scan(e, nq, b1, b2, b3, false, 0, best, bestd, "w2b_eval_top1");
@@ -1432,8 +1552,11 @@ int text_out(const std::string &txt, const char *who, char **out, int64_t *out_l
 }
 }  // namespace
 
-extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len) {
-  if (!e || !out || len < 0 || (len > 0 && !questions)) return efail(W2B_EINVAL, "w2b_eval_transcript: bad argument");
+// `answer(e, nq, b1, b2, b3, best)` scores all answerable questions at once: best[q] = the answer's row or -1
+template <class Answer>
+static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len, const char *who,
+                           Answer answer) {
+  if (!e || !out || len < 0 || (len > 0 && !questions)) return efail(W2B_EINVAL, std::string(who) + ": bad argument");
   *out = nullptr;
   TokenIn in{questions, len};
   std::string st1, st2, st3, st4;
@@ -1469,7 +1592,7 @@ extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t l
   // the scan of ref :155-177 for all of them at once, on the GPU
   std::vector<int32_t> best(b1s.size());
   if (!b1s.empty()) {
-    const int rc = w2b_eval_top1(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), best.data(), nullptr);
+    const int rc = answer(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), best.data());
     if (rc != W2B_OK) return rc;
   }
   // pass 2: replay the counters and print (ref :120-131,178-187)
@@ -1502,7 +1625,21 @@ extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t l
     }
   }
   appendf(txt, "Questions seen / total: %d %d   %.2f %% \n", TQS, TQ, TQS / (float)TQ * 100);
-  return text_out(txt, "w2b_eval_transcript", out, out_len);
+  return text_out(txt, who, out, out_len);
+}
+
+extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len) {
+  return eval_transcript(e, questions, len, out, out_len, "w2b_eval_transcript",
+                         [](w2b_eval *ev, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t *best) {
+                           return w2b_eval_top1(ev, nq, b1, b2, b3, best, nullptr);
+                         });
+}
+
+extern "C" int w2b_eval_transcript_cosmul(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len) {
+  return eval_transcript(e, questions, len, out, out_len, "w2b_eval_transcript_cosmul",
+                         [](w2b_eval *ev, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t *best) {
+                           return w2b_eval_cosmul(ev, nq, b1, b2, b3, 1, best, nullptr);
+                         });
 }
 
 
@@ -1594,6 +1731,46 @@ extern "C" int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t l
   }
   const std::string txt = query_answers(e, lines, k, best, bestd);
   return text_out(txt, "w2b_eval_nearest_text", out, out_len);
+}
+
+// the 3CosMul form: every non-empty line is three words A B C
+extern "C" int w2b_eval_cosmul_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out, int64_t *out_len) {
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_cosmul_text: k must be 1..64");
+  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_cosmul_text: bad argument");
+  if (!e) return efail(W2B_EINVAL, "w2b_eval_cosmul_text: null handle");
+  if (!e->bits && !e->codes)
+    return efail(W2B_EINVAL, "w2b_eval_cosmul_text: not available on an fp32 handle: load the file with bits or codes");
+  *out = nullptr;
+  std::vector<QueryLine> lines;
+  std::vector<int32_t> b1s, b2s, b3s;
+  std::vector<std::string> tok;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
+    if (tok.empty()) continue;
+    QueryLine ln{joined(tok), std::string(), -1};
+    if (tok.size() != 3) {
+      ln.error = "expected 3 words";
+    } else {
+      int64_t r[3] = {0, 0, 0};
+      for (size_t i = 0; i < 3 && ln.error.empty(); i++) {
+        r[i] = w2b_eval_lookup(e, tok[i].c_str());
+        if (r[i] == e->words) ln.error = "not in vocabulary: " + tok[i];
+      }
+      if (ln.error.empty()) {
+        ln.q = (int64_t)b1s.size();
+        b1s.push_back((int32_t)r[0]);
+        b2s.push_back((int32_t)r[1]);
+        b3s.push_back((int32_t)r[2]);
+      }
+    }
+    lines.push_back(ln);
+  }
+  std::vector<int32_t> best(b1s.size() * (size_t)k);
+  std::vector<float> bestd(b1s.size() * (size_t)k);
+  if (!b1s.empty()) {
+    const int rc = w2b_eval_cosmul(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), k, best.data(), bestd.data());
+    if (rc != W2B_OK) return rc;
+  }
+  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_cosmul_text", out, out_len);
 }
 
 // the signed form: +WORD, -WORD or WORD, 1 to W2B_EVAL_MAX_TERMS of them per line

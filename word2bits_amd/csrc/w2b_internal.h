@@ -196,6 +196,17 @@ hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const fl
                                  int nq, const int *b1, const int *b2, const int *b3, int k, unsigned long long *best,
                                  unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
                                  unsigned long long *out, hipStream_t s);
+// The 3CosMul question on bit-packed rows (include/word2bits_eval.h, "3CosMul").  2-bit rows: the COSMUL instance of the
+// codes scan, with the arguments of w2b_launch_codes_scan's top-k form (k >= 1).  1-bit rows (w2b_kernels_evalcosmul.hip):
+// utab = u by agreement count, dim + 1 floats ((float)A / (float)dim); the scan into `slots` ([nq][splits][k]) and the merge
+// into `out`, splits and rows_per_split from w2b_bits_layout(topk = 1).  Keys are score bits << 32 | ~row, 0 = no row.
+hipError_t w2b_launch_codes_scan_cosmul(const uint32_t *B, int words, int dim, const float *wrow, const void *T,
+                                        const float *Wq, int nq, const int *b1, const int *b2, const int *b3, int k,
+                                        unsigned long long *bound, unsigned long long *bkt, unsigned long long *keys,
+                                        unsigned char *cnt, unsigned long long *out, hipStream_t s);
+hipError_t w2b_launch_cosmul_bits(const uint32_t *B, int words, int dim, const float *utab, int nq, const int *b1,
+                                  const int *b2, const int *b3, int k, int splits, int rows_per_split,
+                                  unsigned long long *slots, unsigned long long *out, hipStream_t s);
 // The bag question on bit-packed rows (w2b_kernels_evalbag.hip; include/word2bits_eval.h, "bag questions").  bitlevel 1: B =
 // the 1-bit rows (nw = 2 * ceil(dim / 64) halves), 2: the 2-bit rows and wrow as above.  ids / off = the chunk's bags, off
 // [nq + 1] rebased to ids[0]; T = the two digit planes of the pooled vectors in fragment order (w2b_bag_operand_bytes, ZEROED

@@ -80,7 +80,14 @@ __global__ void k_codes_operands(const uint32_t *__restrict__ B, int nw, int dim
   }
 }
 
-template <int KS, int R, bool CHUNKED, bool TOPK>
+// COSMUL: the 3CosMul question (include/word2bits_eval.h): the same three accumulator tiles, combined as
+//   cos_i = (J_i * w(b_i)) * w(c),  u_i = (1 + cos_i) * 0.5,  score = (u2 * u3) / (u1 + eps)
+// one rounding per operation.  The scores are positive floats, so the key, the `seen` pruning and the selection stay as
+// they are.  (A lane without a question and a row past the vocabulary have w = 0: cos = 0, a finite score that is dropped
+// like every other one of theirs.)
+constexpr float kCosmulEps = 1e-6f;    // 0x358637BD
+
+template <int KS, int R, bool CHUNKED, bool TOPK, bool COSMUL = false>
 __global__ void __launch_bounds__(CT, 1)
 k_codes_scan(const uint32_t *__restrict__ B, int nw, int words, const float *__restrict__ wrow, const i32x4 *__restrict__ T,
              const float *__restrict__ Wq, int ks, int nq, int qtiles, int qt_per_y, const int *__restrict__ b1,
@@ -155,7 +162,14 @@ k_codes_scan(const uint32_t *__restrict__ B, int nw, int words, const float *__r
           const int e = 4 * g + i;
           const float p1 = __fmul_rn((float)acc[0][r][e], w1), p2 = __fmul_rn((float)acc[1][r][e], w2),
                       p3 = __fmul_rn((float)acc[2][r][e], w3);
-          d[r][e] = __fmul_rn(__fadd_rn(__fsub_rn(p2, p1), p3), wc[i]);
+          if constexpr (COSMUL) {
+            const float u1 = __fmul_rn(__fadd_rn(1.0f, __fmul_rn(p1, wc[i])), 0.5f),
+                        u2 = __fmul_rn(__fadd_rn(1.0f, __fmul_rn(p2, wc[i])), 0.5f),
+                        u3 = __fmul_rn(__fadd_rn(1.0f, __fmul_rn(p3, wc[i])), 0.5f);
+            d[r][e] = __fdiv_rn(__fmul_rn(u2, u3), __fadd_rn(u1, kCosmulEps));
+          } else {
+            d[r][e] = __fmul_rn(__fadd_rn(__fsub_rn(p2, p1), p3), wc[i]);
+          }
           mr[r] = __builtin_fmaxf(mr[r], d[r][e]);
         }
       }
@@ -290,10 +304,11 @@ hipError_t w2b_launch_codes_operands(const uint32_t *B, int dim, int nq, const f
   return hipGetLastError();
 }
 
-hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const float *wrow, const void *T, const float *Wq,
-                                 int nq, const int *b1, const int *b2, const int *b3, int k, unsigned long long *best,
-                                 unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
-                                 unsigned long long *out, hipStream_t s) {
+namespace {
+template <bool COSMUL>
+hipError_t codes_scan(const uint32_t *B, int words, int dim, const float *wrow, const void *T, const float *Wq, int nq,
+                      const int *b1, const int *b2, const int *b3, int k, unsigned long long *best, unsigned long long *bkt,
+                      unsigned long long *keys, unsigned char *cnt, unsigned long long *out, hipStream_t s) {
   if (nq <= 0 || words <= 0) return hipSuccess;
   const int ks = (dim + 31) / 32, nw = (dim + 63) / 64 * 4, qtiles = (nq + 31) / 32;
   TopkArgs tk{};
@@ -315,7 +330,10 @@ hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const fl
     const int per_y = (qtiles + gy - 1) / gy;
     gy = (qtiles + per_y - 1) / per_y;
     const dim3 grid((unsigned)gx, (unsigned)gy);
-    if (k > 0)
+    if constexpr (COSMUL)
+      hipLaunchKernelGGL((k_codes_scan<KS, R, CH, true, true>), grid, dim3(CT), 0, s, B, nw, words, wrow, (const i32x4 *)T, Wq, ks,
+                         nq, qtiles, per_y, b1, b2, b3, best, tk);
+    else if (k > 0)
       hipLaunchKernelGGL((k_codes_scan<KS, R, CH, true>), grid, dim3(CT), 0, s, B, nw, words, wrow, (const i32x4 *)T, Wq, ks, nq,
                          qtiles, per_y, b1, b2, b3, best, tk);
     else
@@ -325,4 +343,21 @@ hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const fl
   });
   if (e != hipSuccess || k <= 0) return e;
   return w2b_launch_eval_topk_merge(keys, cnt, tk.nunits, tk.cap, k, nq, out, s);
+}
+}  // namespace
+
+hipError_t w2b_launch_codes_scan(const uint32_t *B, int words, int dim, const float *wrow, const void *T, const float *Wq,
+                                 int nq, const int *b1, const int *b2, const int *b3, int k, unsigned long long *best,
+                                 unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt,
+                                 unsigned long long *out, hipStream_t s) {
+  return codes_scan<false>(B, words, dim, wrow, T, Wq, nq, b1, b2, b3, k, best, bkt, keys, cnt, out, s);
+}
+
+// the 3CosMul form (k >= 1 only): the arguments of the top-k form above
+hipError_t w2b_launch_codes_scan_cosmul(const uint32_t *B, int words, int dim, const float *wrow, const void *T,
+                                        const float *Wq, int nq, const int *b1, const int *b2, const int *b3, int k,
+                                        unsigned long long *bound, unsigned long long *bkt, unsigned long long *keys,
+                                        unsigned char *cnt, unsigned long long *out, hipStream_t s) {
+  if (k < 1) return hipErrorInvalidValue;
+  return codes_scan<true>(B, words, dim, wrow, T, Wq, nq, b1, b2, b3, k, bound, bkt, keys, cnt, out, s);
 }

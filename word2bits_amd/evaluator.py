@@ -8,9 +8,10 @@
     ev = Evaluator("vectors2.w2bp", codes=True)                      # 2-bit model kept packed: the i8 matrix-core scan
     rows, scores = ev.bag([3, 17, 4, 9, 9], [0, 2, 5], 10)           # two bags of rows pooled: nearest to each sum
     rows, scores = ev.vectors(hidden, 10)                            # float vectors [nq, size] of one's own: nearest to each
+    rows, scores = ev.cosmul(b1, b2, b3, 10)                         # analogies by the multiplicative rule 3CosMul
 
 The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip,
-w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip);
+w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip, w2b_kernels_evalcosmul.hip);
 there is no CPU path in this module.
 """
 import ctypes as C
@@ -130,6 +131,16 @@ class Evaluator:
         equal scores by ascending row); a list of fewer than k rows ends in row -1 / score 0.  1 <= k <= 64."""
         return self._scan(self._L.w2b_eval_topk, (b1, b2, b3), int(k))
 
+    def cosmul(self, b1, b2, b3, k):
+        """The analogy "b1 is to b2 as b3 is to ?" by the multiplicative rule 3CosMul (w2b_eval_cosmul; bits and codes
+        handles): score = (u2 * u3) / (u1 + 1e-6) with the similarities shifted to [0, 1].  Returns (rows int32 [nq, k],
+        scores float32 [nq, k]) in the order of topk; b1, b2, b3 are excluded from their question's answers."""
+        return self._scan(self._L.w2b_eval_cosmul, (b1, b2, b3), int(k))
+
+    def cosmul_text(self, queries, k):
+        """stdout of `nearest FILE k ... bits|codes cosmul < queries` as bytes: every line is three words A B C."""
+        return self._text(self._L.w2b_eval_cosmul_text, queries, int(k))
+
     def neighbors(self, rows, k):
         """The k nearest rows of each row in `rows` (the row itself excluded): topk(rows, rows, rows, k)."""
         return self._scan(self._L.w2b_eval_neighbors, (rows,), int(k))
@@ -209,9 +220,12 @@ class Evaluator:
         """Upper bound for the device scratch of one top-k launch (0 = default); results never depend on it."""
         _lib.check(self._L.w2b_eval_set_topk_scratch(self._h, int(nbytes)))
 
-    def transcript(self, questions):
-        """stdout of `compute_accuracy FILE bitlevel threshold < questions` as bytes."""
-        return self._text(self._L.w2b_eval_transcript, questions)
+    def transcript(self, questions, method="add"):
+        """stdout of `compute_accuracy FILE bitlevel threshold < questions` as bytes.  method="cosmul" (bits and codes
+        handles) answers every question by 3CosMul instead: `compute_accuracy FILE ... bits|codes cosmul`."""
+        if method not in ("add", "cosmul"):
+            raise ValueError('method must be "add" or "cosmul"')
+        return self._text(self._L.w2b_eval_transcript_cosmul if method == "cosmul" else self._L.w2b_eval_transcript, questions)
 
     def set_kernel(self, variant):
         """1 = f32 MFMA kernel (default), 0 = the same fused chain on the vector ALU (cross-check)"""
