@@ -358,6 +358,64 @@ int w2b_cosmul_scores_host(const uint64_t *packed, int64_t words, int64_t dim, i
                            int64_t b1, int64_t b2, int64_t b3, float *u_out /* [3][words] or NULL */,
                            float *score_out /* [words] or NULL */);
 
+/* ---- word classes: k-means on the packed rows, word2vec's -classes output -------------------------------------------------
+ * "Which words belong together?"  Every other question of this header asks which ROWS are nearest to a question; this one
+ * asks the transposed question -- which of K centroids is nearest to every row -- and needs one more pass, the rows of every
+ * class summed.  It is spherical k-means as word2vec's k-means block has it: a centroid is the normalised sum of its members'
+ * raw vectors, a row goes to the centroid with the largest dot product.  It runs on the integer codes of a bits handle
+ * (t = +-1) or a codes handle (t in {+-1, +-3}); an fp32 handle is W2B_EINVAL ("not available on an fp32 handle: load the file
+ * with bits or codes").  The row's own length is a positive factor common to all classes and is left out of the comparison.
+ * Everything is deterministic, bit for bit:
+ *     cl[c] = init[c], or c % K when init is NULL                                          (word2vec: cl[a] = a % clcn)
+ *     iters_run = 0; moved = 0; score[c] = +0 for every row
+ *     while iters_run < max_iters:
+ *       sums    T_k[a] = sum of t_c[a] over the rows c with cl[c] == k, exact integers;
+ *               N_k = sum_a T_k[a]^2 (an int64); class k is LIVE iff N_k > 0;
+ *               wq_k = (float)(1.0 / sqrt((double)N_k)) -- the expression of wq in w2b_eval_bag: (double)N_k rounded to nearest
+ *               even, the double square root and the double division each correctly rounded, the result rounded to float
+ *       assign  for every row c and class k:  S_k(c): acc = +0; for a = 0 .. size - 1: acc = fmaf((float)T_k[a], (float)t_c[a], acc)
+ *               -- strictly sequential in a, one accumulator per (row, class): the chain of w2b_eval_vectors --
+ *               d_k(c) = S_k(c) * wq_k, ONE float32 multiply, rounded on its own, nothing contracted;
+ *               the LIVE classes are walked in ascending k: the first one is taken, a later one replaces it iff d_k > d_best;
+ *               new[c] = that class, score[c] = its d; no live class at all: new[c] = 0, score[c] = +0
+ *       moved = the number of rows with new[c] != cl[c];  cl = new;  iters_run += 1;  stop if moved == 0
+ *     finally T_out, counts = the sums and the member counts of the FINAL cl (one more sums pass)
+ * Stopping at moved == 0 is exact: the next iteration would reproduce the same sums and the same assignment.  A class that is
+ * empty, or whose members cancel in every column, is not live and attracts no row: it stays empty.  Two deliberate departures
+ * from word2vec: its `closev = -10` start would drop legitimate scores here (with integer codes |d| reaches 3 * sqrt(size)), and
+ * its dead centroids are NaN by accident of 0 / 0 where this rule is spelled out.
+ *   no subnormals: S is 0 or an integer-valued float with |S| >= 1, wq >= 2^-31.5, so d is 0 or at least 2^-32 in magnitude; S
+ *     is never -0 because the chain starts at +0; nothing overflows.  The result does not depend on how an instruction treats
+ *     subnormals.
+ *   limits, all W2B_EINVAL with the cause in w2b_last_error(): 1 <= n_classes <= min(words, W2B_EVAL_MAX_CLASSES); 0 <=
+ *     max_iters <= 1000; words <= 5592405 (3 * words < 2^24, so (float)T is exact); 9 * words^2 * size < 2^63 (N_k fits an
+ *     int64); every init[c] in [0, n_classes) -- the error names the first offending row.
+ *   validation order, as in w2b_eval_bag: what does not depend on the handle first, n_classes >= 1 and max_iters (so a NULL
+ *     handle with a bad n_classes is W2B_EINVAL for the n_classes), then the handle and the limits that depend on it, then
+ *     init.  On error no output is touched.
+ *   outputs: cls [words]; score [words], T_out [n_classes][size], counts [n_classes], iters_run and moved (the moved count of
+ *     the last iteration run, 0 when none ran) may each be NULL.
+ * w2b_eval_classes keeps the class array, the sums and the centroid operands on the device for all iterations
+ * (word2bits_amd/csrc/w2b_kernels_evalclasses.hip: the assign is the f32 matrix-core scan of w2b_eval_vectors with the operand
+ * roles swapped, the sums a counting sort by class and an integer pooling); per iteration the host sees the moved count and
+ * N_k, from which it builds wq_k as w2b_eval_bag builds wq.  Handles made by *_from_trainer in bits / codes mode work like
+ * loaded ones.  w2b_eval_timing_read counts one launch per iteration run, macs = iterations run x n_classes x rows x size, and
+ * the device time of both passes; w2b_eval_classes_timing splits the last call's time into the assign scans and the sums
+ * passes (the one before the first iteration included). */
+#define W2B_EVAL_MAX_CLASSES 16384
+int w2b_eval_classes(w2b_eval *e, int32_t n_classes, int32_t max_iters, const int32_t *init /* [words] or NULL */,
+                     int32_t *cls /* [words] */, float *score /* [words] or NULL */, int32_t *T_out /* [n_classes][size] or NULL */,
+                     int64_t *counts /* [n_classes] or NULL */, int32_t *iters_run /* or NULL */, int64_t *moved /* or NULL */);
+int w2b_eval_classes_timing(w2b_eval *e, double *assign_ms, double *sums_ms);
+/* word2vec's -classes file: one line "<w2b_eval_word(row)> <class>\n" per row in row order, from w2b_eval_classes with init =
+ * NULL (`./classes FILE K [iters] [threshold] bits|codes`).  *out is malloc'ed; release it with w2b_eval_free_text. */
+int w2b_eval_classes_text(w2b_eval *e, int32_t n_classes, int32_t max_iters, char **out, int64_t *out_len);
+/* Host twin of the class kernels (pure C, explicit fmaf, no device): the loop above on packed[words][bitlevel * ceil(dim / 64)],
+ * bitlevel 1 (bits) or 2 (codes), with the same validation, outputs and NULL rules. */
+int w2b_classes_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int32_t n_classes, int32_t max_iters,
+                     const int32_t *init, int32_t *cls, float *score, int32_t *T_out, int64_t *counts, int32_t *iters_run,
+                     int64_t *moved);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,13 +3,15 @@
 // GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
 // w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
 // adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms, w2b_kernels_evalvec.hip
-// the float-vector question on them, w2b_kernels_evalcosmul.hip the 3CosMul scan on 1-bit rows.  No arithmetic on scores happens here (the exceptions are question weights: the bag
+// the float-vector question on them, w2b_kernels_evalcosmul.hip the 3CosMul scan on 1-bit rows, w2b_kernels_evalclasses.hip the
+// k-means word classes on both packed forms (whose wq = 1 / sqrt(N_k) the host builds like the bag question's).  No arithmetic on scores happens here (the exceptions are question weights: the bag
 // question's 1 / sqrt(N_T), built from the integer the device sums, and the vector question's wx with the fp32 handle's
 // vec = x * wx; and the 3CosMul table u = A / size of a bits handle) and there is no CPU fallback (w2b_codes_scores_host,
-// w2b_bag_scores_host, w2b_vector_scores_host and w2b_cosmul_scores_host are the tests' twins of the kernels).
+// w2b_bag_scores_host, w2b_vector_scores_host, w2b_cosmul_scores_host and w2b_classes_host are the tests' twins of the kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
+#include "w2b_evalclasses.h"
 
 #include <algorithm>
 #include <cmath>
@@ -76,6 +78,7 @@ struct w2b_eval {
   double kernel_ms = 0;                                 // score-kernel time since the last timing_read
   int64_t launches = 0;
   double macs = 0;
+  double cls_assign_ms = 0, cls_sums_ms = 0;             // w2b_eval_classes: the two shares of its last call's device time
   // top-k scratch of one launch: bound / buckets / slot counts / slots / merged keys
   void *tk_buf = nullptr;
   size_t tk_bytes = 0;
@@ -1899,3 +1902,305 @@ extern "C" int w2b_eval_vectors_text(w2b_eval *e, const char *queries, int64_t l
 }
 
 extern "C" void w2b_eval_free_text(char *text) { free(text); }
+
+// ------------------------------------------------------------------------------------ word classes
+namespace {
+constexpr int64_t kClassesMaxWords = 5592405;                       // 3 * words < 2^24: (float)T is exact
+
+// what w2b_eval_classes and its host twin refuse: first what needs no table, then the table's shape, then `init`
+const char *bad_classes_args(int32_t n_classes, int32_t max_iters) {
+  if (n_classes < 1) return "n_classes must be at least 1";
+  if (max_iters < 0 || max_iters > 1000) return "max_iters must be 0..1000";
+  return nullptr;
+}
+const char *bad_classes_shape(int64_t words, int64_t size, int32_t n_classes) {
+  if (n_classes > W2B_EVAL_MAX_CLASSES || n_classes > words) return "n_classes must be at most min(words, 16384)";
+  if (words > kClassesMaxWords) return "words must be at most 5592405 (3 * words < 2^24)";
+  if ((unsigned __int128)9 * (unsigned __int128)words * (unsigned __int128)words * (unsigned __int128)size >=
+      ((unsigned __int128)1 << 63))
+    return "9 * words^2 * size must stay below 2^63";
+  return nullptr;
+}
+int64_t bad_classes_init(const int32_t *init, int64_t words, int32_t n_classes) {
+  if (init)
+    for (int64_t c = 0; c < words; c++)
+      if (init[c] < 0 || init[c] >= n_classes) return c;
+  return -1;
+}
+std::string classes_init_error(int64_t row) { return "init: row " + std::to_string(row) + ": class out of range"; }
+
+// wq_k of the header from N_k > 0: the expression of bag_weight
+inline float classes_weight(long long n) { return (float)(1.0 / sqrt((double)n)); }
+
+// The chains of one row against every class: Tf = (float)T transposed, [size][K]; t = the row's codes; acc [K].  Explicit
+// fmaf, strictly in column order per class.  The body is compiled twice, for a processor with FMA instructions (the
+// classes vectorise) and for any other one (a library call per step): the same correctly rounded operation either way.
+__attribute__((always_inline)) inline void classes_chains_body(const float *Tf, const int8_t *t, int64_t size, int32_t K,
+                                                               float *acc) {
+  for (int32_t k = 0; k < K; k++) acc[k] = 0.f;
+  for (int64_t a = 0; a < size; a++) {
+    const float ta = (float)t[a];
+    const float *row = Tf + a * K;
+    for (int32_t k = 0; k < K; k++) acc[k] = __builtin_fmaf(row[k], ta, acc[k]);
+  }
+}
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+__attribute__((target("avx2,fma"))) void classes_chains_fma(const float *Tf, const int8_t *t, int64_t size, int32_t K,
+                                                            float *acc) {
+  classes_chains_body(Tf, t, size, K, acc);
+}
+#endif
+void classes_chains_plain(const float *Tf, const int8_t *t, int64_t size, int32_t K, float *acc) {
+  classes_chains_body(Tf, t, size, K, acc);
+}
+
+// T [K][size] and counts [K] of the class array cl
+void classes_sums_host(const int8_t *t, int64_t words, int64_t size, int32_t K, const int32_t *cl, int32_t *T, int64_t *counts) {
+  std::fill(T, T + (size_t)K * (size_t)size, 0);
+  std::fill(counts, counts + K, (int64_t)0);
+  for (int64_t c = 0; c < words; c++) {
+    int32_t *Tk = T + (int64_t)cl[c] * size;
+    const int8_t *tc = t + c * size;
+    for (int64_t a = 0; a < size; a++) Tk[a] += tc[a];
+    counts[cl[c]]++;
+  }
+}
+}  // namespace
+
+// Host twin of the class kernels: the loop of the header, one step at a time (this file is built with -ffp-contract=off, and
+// the function says so again).
+extern "C" int w2b_classes_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int32_t n_classes,
+                                int32_t max_iters, const int32_t *init, int32_t *cls, float *score, int32_t *T_out,
+                                int64_t *counts, int32_t *iters_run, int64_t *moved) {
+#pragma clang fp contract(off)
+  const std::string who = "w2b_classes_host";
+  if (const char *why = bad_classes_args(n_classes, max_iters)) return efail(W2B_EINVAL, who + ": " + why);
+  if (!packed || !cls || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (const char *why = bad_classes_shape(words, dim, n_classes)) return efail(W2B_EINVAL, who + ": " + why);
+  const int64_t bad = bad_classes_init(init, words, n_classes);
+  if (bad >= 0) return efail(W2B_EINVAL, who + ": " + classes_init_error(bad));
+  const int32_t K = n_classes;
+  const int64_t wpr = (dim + 63) / 64 * bitlevel;
+  std::vector<int8_t> t((size_t)(words * dim));
+  for (int64_t c = 0; c < words; c++) {
+    const uint64_t *rc = packed + c * wpr;
+    for (int64_t a = 0; a < dim; a++) {
+      const uint64_t bit = 1ull << (a & 63);
+      int8_t v = 1;
+      if (bitlevel == 2 && (rc[2 * (a >> 6) + 1] & bit)) v = 3;
+      if (rc[bitlevel * (a >> 6)] & bit) v = (int8_t)-v;
+      t[(size_t)(c * dim + a)] = v;
+    }
+  }
+  std::vector<int32_t> cl((size_t)words), nw((size_t)words), T((size_t)K * (size_t)dim);
+  std::vector<float> sc((size_t)words, 0.f), Tf((size_t)K * (size_t)dim), wq((size_t)K), acc((size_t)K);
+  std::vector<int64_t> cnt((size_t)K);
+  std::vector<char> live((size_t)K);
+  for (int64_t c = 0; c < words; c++) cl[(size_t)c] = init ? init[c] : (int32_t)(c % K);
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+  const bool fma = __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
+#endif
+  int32_t it = 0;
+  int64_t mv = 0;
+  while (it < max_iters) {
+    classes_sums_host(t.data(), words, dim, K, cl.data(), T.data(), cnt.data());
+    for (int32_t k = 0; k < K; k++) {
+      long long n = 0;
+      for (int64_t a = 0; a < dim; a++) {
+        const long long v = T[(size_t)(k * dim + a)];
+        n += v * v;
+        Tf[(size_t)(a * K + k)] = (float)v;
+      }
+      live[(size_t)k] = n > 0;
+      wq[(size_t)k] = n > 0 ? classes_weight(n) : 0.f;
+    }
+    mv = 0;
+    for (int64_t c = 0; c < words; c++) {
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+      if (fma) classes_chains_fma(Tf.data(), t.data() + c * dim, dim, K, acc.data());
+      else
+#endif
+        classes_chains_plain(Tf.data(), t.data() + c * dim, dim, K, acc.data());
+      int32_t bk = -1;
+      float bd = 0.f;
+      for (int32_t k = 0; k < K; k++) {
+        if (!live[(size_t)k]) continue;
+        const float d = acc[(size_t)k] * wq[(size_t)k];
+        if (bk < 0 || d > bd) bk = k, bd = d;
+      }
+      if (bk < 0) bk = 0, bd = 0.f;
+      nw[(size_t)c] = bk;
+      sc[(size_t)c] = bd;
+      mv += bk != cl[(size_t)c];
+    }
+    cl.swap(nw);
+    it++;
+    if (mv == 0) break;
+  }
+  classes_sums_host(t.data(), words, dim, K, cl.data(), T.data(), cnt.data());
+  std::copy(cl.begin(), cl.end(), cls);
+  if (score) std::copy(sc.begin(), sc.end(), score);
+  if (T_out) std::copy(T.begin(), T.end(), T_out);
+  if (counts) std::copy(cnt.begin(), cnt.end(), counts);
+  if (iters_run) *iters_run = it;
+  if (moved) *moved = mv;
+  return W2B_OK;
+}
+
+namespace {
+// every device buffer of one w2b_eval_classes call, carved out of one allocation
+struct ClassesBuffers {
+  char *base = nullptr;
+  int32_t *cl[2] = {nullptr, nullptr}, *hist = nullptr, *start = nullptr, *cursor = nullptr, *order = nullptr, *T = nullptr;
+  float *score = nullptr, *wq = nullptr;
+  uint32_t *live = nullptr;
+  long long *counts = nullptr, *N = nullptr;
+  unsigned long long *moved = nullptr;
+  void *X = nullptr;
+  ~ClassesBuffers() { if (base) (void)hipFree(base); }
+  bool make(int64_t words, int64_t size, int32_t K) {
+    const int64_t slots = w2b_cls_class_slots(K);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_cl0 = take((size_t)words * 4), o_cl1 = take((size_t)words * 4), o_score = take((size_t)words * 4);
+    const size_t o_order = take((size_t)words * 4), o_hist = take((size_t)K * 4), o_start = take((size_t)(K + 1) * 4);
+    const size_t o_cursor = take((size_t)K * 4), o_T = take((size_t)K * (size_t)size * 4), o_counts = take((size_t)K * 8);
+    const size_t o_N = take((size_t)K * 8), o_wq = take((size_t)slots * 4), o_live = take((size_t)slots / 8);
+    const size_t o_moved = take(8), o_X = take(w2b_cls_operand_bytes((int)size, K));
+    if (hipMalloc(&base, at) != hipSuccess) { base = nullptr; return false; }
+    cl[0] = (int32_t *)(base + o_cl0); cl[1] = (int32_t *)(base + o_cl1); score = (float *)(base + o_score);
+    order = (int32_t *)(base + o_order); hist = (int32_t *)(base + o_hist); start = (int32_t *)(base + o_start);
+    cursor = (int32_t *)(base + o_cursor); T = (int32_t *)(base + o_T); counts = (long long *)(base + o_counts);
+    N = (long long *)(base + o_N); wq = (float *)(base + o_wq); live = (uint32_t *)(base + o_live);
+    moved = (unsigned long long *)(base + o_moved); X = base + o_X;
+    return true;
+  }
+};
+}  // namespace
+
+// Word classes: every check first, then the loop of the header with the class array, the sums and the centroid operands on
+// the device throughout; per iteration the host sees the moved count and N_k (from which it builds wq_k and the live bits,
+// as w2b_eval_bag builds wq).  Each iteration ends with the sums of its new class array: what the next one scores against,
+// and after the last one the T_out and counts of the result.
+extern "C" int w2b_eval_classes(w2b_eval *e, int32_t n_classes, int32_t max_iters, const int32_t *init, int32_t *cls,
+                                float *score, int32_t *T_out, int64_t *counts, int32_t *iters_run, int64_t *moved) {
+  const std::string who = "w2b_eval_classes";
+  if (const char *why = bad_classes_args(n_classes, max_iters)) return efail(W2B_EINVAL, who + ": " + why);
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes)
+    return efail(W2B_EINVAL, who + ": not available on an fp32 handle: load the file with bits or codes");
+  if (!cls) return efail(W2B_EINVAL, who + ": bad argument");
+  if (const char *why = bad_classes_shape(e->words, e->size, n_classes)) return efail(W2B_EINVAL, who + ": " + why);
+  const int64_t bad = bad_classes_init(init, e->words, n_classes);
+  if (bad >= 0) return efail(W2B_EINVAL, who + ": " + classes_init_error(bad));
+  EHIP(hipSetDevice(e->device));
+  const int32_t K = n_classes;
+  const int words = (int)e->words, size = (int)e->size, bl = e->codes ? 2 : 1;
+  const int64_t slots = w2b_cls_class_slots(K);
+  ClassesBuffers d;
+  if (!d.make(words, size, K)) return efail(W2B_ENOMEM, who + ": device allocation failed");
+  std::vector<int32_t> h_cl((size_t)words);
+  for (int64_t c = 0; c < words; c++) h_cl[(size_t)c] = init ? init[c] : (int32_t)(c % K);
+  EHIP(hipMemcpy(d.cl[0], h_cl.data(), (size_t)words * 4, hipMemcpyHostToDevice));
+  EHIP(hipMemsetAsync(d.score, 0, (size_t)words * 4, e->stream));
+  EventPair ev, ev2;
+  EHIP(ev.create());
+  EHIP(ev2.create());
+  std::vector<long long> h_N((size_t)K);
+  std::vector<float> h_wq((size_t)slots);
+  std::vector<uint32_t> h_live((size_t)slots / 32);
+  // the host's share of an iteration: wq and the live bits from N, for the next assign
+  auto weights_up = [&]() -> int {
+    std::fill(h_wq.begin(), h_wq.end(), 0.f);
+    std::fill(h_live.begin(), h_live.end(), 0u);
+    for (int32_t k = 0; k < K; k++)
+      if (h_N[(size_t)k] > 0) {
+        h_wq[(size_t)k] = classes_weight(h_N[(size_t)k]);
+        h_live[(size_t)k >> 5] |= 1u << (k & 31);
+      }
+    EHIP(hipMemcpy(d.wq, h_wq.data(), (size_t)slots * 4, hipMemcpyHostToDevice));
+    EHIP(hipMemcpy(d.live, h_live.data(), (size_t)slots / 8, hipMemcpyHostToDevice));
+    return W2B_OK;
+  };
+  auto sums = [&](const int32_t *cl) {
+    return w2b_launch_cls_sums(e->B, words, size, bl, K, cl, d.hist, d.start, d.cursor, d.order, d.T, d.counts, d.N, d.X,
+                               e->stream);
+  };
+  float ms = 0;
+  e->cls_assign_ms = e->cls_sums_ms = 0;
+  EHIP(hipEventRecord(ev.t[0], e->stream));
+  EHIP(sums(d.cl[0]));
+  EHIP(hipEventRecord(ev.t[1], e->stream));
+  EHIP(hipMemcpyAsync(h_N.data(), d.N, (size_t)K * 8, hipMemcpyDeviceToHost, e->stream));
+  EHIP(hipStreamSynchronize(e->stream));
+  EHIP(hipEventElapsedTime(&ms, ev.t[0], ev.t[1]));
+  e->cls_sums_ms += ms;
+  int cur = 0;
+  int32_t it = 0;
+  unsigned long long mv = 0;
+  while (it < max_iters) {
+    if (int rc = weights_up()) return rc;
+    EHIP(hipMemsetAsync(d.moved, 0, 8, e->stream));
+    EHIP(hipEventRecord(ev.t[0], e->stream));
+    EHIP(w2b_launch_cls_assign(e->B, words, size, bl, K, d.X, d.wq, d.live, d.cl[cur], d.cl[cur ^ 1], d.score, d.moved,
+                               e->stream));
+    EHIP(hipEventRecord(ev.t[1], e->stream));
+    EHIP(hipEventRecord(ev2.t[0], e->stream));
+    EHIP(sums(d.cl[cur ^ 1]));
+    EHIP(hipEventRecord(ev2.t[1], e->stream));
+    EHIP(hipMemcpyAsync(&mv, d.moved, 8, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipMemcpyAsync(h_N.data(), d.N, (size_t)K * 8, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+    EHIP(hipEventElapsedTime(&ms, ev.t[0], ev.t[1]));
+    e->cls_assign_ms += ms;
+    EHIP(hipEventElapsedTime(&ms, ev2.t[0], ev2.t[1]));
+    e->cls_sums_ms += ms;
+    e->launches++;
+    e->macs += (double)K * (double)words * (double)size;
+    cur ^= 1;
+    it++;
+    if (mv == 0) break;
+  }
+  e->kernel_ms += e->cls_assign_ms + e->cls_sums_ms;
+  std::vector<float> h_score(score ? (size_t)words : 0);
+  std::vector<int32_t> h_T(T_out ? (size_t)K * (size_t)size : 0);
+  std::vector<long long> h_counts(counts ? (size_t)K : 0);
+  EHIP(hipMemcpy(h_cl.data(), d.cl[cur], (size_t)words * 4, hipMemcpyDeviceToHost));
+  if (score) EHIP(hipMemcpy(h_score.data(), d.score, (size_t)words * 4, hipMemcpyDeviceToHost));
+  if (T_out) EHIP(hipMemcpy(h_T.data(), d.T, h_T.size() * 4, hipMemcpyDeviceToHost));
+  if (counts) EHIP(hipMemcpy(h_counts.data(), d.counts, (size_t)K * 8, hipMemcpyDeviceToHost));
+  std::copy(h_cl.begin(), h_cl.end(), cls);
+  if (score) std::copy(h_score.begin(), h_score.end(), score);
+  if (T_out) std::copy(h_T.begin(), h_T.end(), T_out);
+  if (counts) std::copy(h_counts.begin(), h_counts.end(), counts);
+  if (iters_run) *iters_run = it;
+  if (moved) *moved = (int64_t)mv;
+  return W2B_OK;
+}
+
+extern "C" int w2b_eval_classes_timing(w2b_eval *e, double *assign_ms, double *sums_ms) {
+  if (!e) return efail(W2B_EINVAL, "w2b_eval_classes_timing: null handle");
+  if (assign_ms) *assign_ms = e->cls_assign_ms;
+  if (sums_ms) *sums_ms = e->cls_sums_ms;
+  return W2B_OK;
+}
+
+// word2vec's -classes file: one line "<word> <class>" per row, in row order
+extern "C" int w2b_eval_classes_text(w2b_eval *e, int32_t n_classes, int32_t max_iters, char **out, int64_t *out_len) {
+  const std::string who = "w2b_eval_classes_text";
+  if (const char *why = bad_classes_args(n_classes, max_iters)) return efail(W2B_EINVAL, who + ": " + why);
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!out) return efail(W2B_EINVAL, who + ": bad argument");
+  std::vector<int32_t> cls((size_t)(e->words > 0 ? e->words : 1));
+  if (int rc = w2b_eval_classes(e, n_classes, max_iters, nullptr, cls.data(), nullptr, nullptr, nullptr, nullptr, nullptr))
+    return rc;
+  std::string txt;
+  for (int64_t c = 0; c < e->words; c++) {
+    txt += e->vocab.data() + c * kMaxW;
+    txt += ' ';
+    txt += std::to_string(cls[(size_t)c]);
+    txt += '\n';
+  }
+  return text_out(txt, who.c_str(), out, out_len);
+}

@@ -9,9 +9,10 @@
     rows, scores = ev.bag([3, 17, 4, 9, 9], [0, 2, 5], 10)           # two bags of rows pooled: nearest to each sum
     rows, scores = ev.vectors(hidden, 10)                            # float vectors [nq, size] of one's own: nearest to each
     rows, scores = ev.cosmul(b1, b2, b3, 10)                         # analogies by the multiplicative rule 3CosMul
+    cls = ev.classes(500)                                            # word classes by k-means (word2vec's -classes)
 
 The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip,
-w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip, w2b_kernels_evalcosmul.hip);
+w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip, w2b_kernels_evalcosmul.hip, w2b_kernels_evalclasses.hip);
 there is no CPU path in this module.
 """
 import ctypes as C
@@ -211,6 +212,41 @@ class Evaluator:
     def vectors_text(self, queries, k, normalize=True):
         """stdout of `nearest FILE k ... vector < queries` as bytes: every line is `size` numbers."""
         return self._text(self._L.w2b_eval_vectors_text, queries, int(normalize), int(k))
+
+    def classes(self, n_classes, iters=10, init=None, details=False):
+        """Word classes by k-means (w2b_eval_classes; bits and codes handles): at most `iters` iterations of spherical k-means
+        on the packed rows, from `init` (int32 [words], classes in [0, n_classes)) or from class = row % n_classes.  Returns
+        cls int32 [words]; with details=True (cls, score float32 [words], T int32 [n_classes, size] the classes' summed rows,
+        counts int64 [n_classes], iters_run, moved)."""
+        K = int(n_classes)
+        cls, score = np.empty(self.words, np.int32), np.empty(self.words, np.float32)
+        T, counts = np.empty((max(K, 0), self.size), np.int32), np.empty(max(K, 0), np.int64)
+        it, moved = C.c_int32(), C.c_int64()
+        if init is not None:
+            init = np.ascontiguousarray(init, np.int32).ravel()
+            if len(init) != self.words:
+                raise ValueError("init must hold one class per row")
+        _lib.check(self._L.w2b_eval_classes(self._h, K, int(iters), None if init is None else init.ctypes.data_as(_lib.i32p),
+                                            cls.ctypes.data_as(_lib.i32p), score.ctypes.data_as(_lib.f32p),
+                                            T.ctypes.data_as(_lib.i32p), counts.ctypes.data_as(_lib.i64p), C.byref(it),
+                                            C.byref(moved)))
+        return (cls, score, T, counts, it.value, moved.value) if details else cls
+
+    def classes_text(self, n_classes, iters=10):
+        """stdout of `classes FILE n_classes iters ... bits|codes` as bytes: one line "<word> <class>" per row (word2vec's
+        -classes file)."""
+        out, n = C.c_void_p(), C.c_int64()
+        _lib.check(self._L.w2b_eval_classes_text(self._h, int(n_classes), int(iters), C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            self._L.w2b_eval_free_text(out)
+
+    def classes_timing(self):
+        """(assign ms, sums ms): the device time of the last classes() call, split into its assign scans and its sums passes."""
+        a, s = C.c_double(), C.c_double()
+        _lib.check(self._L.w2b_eval_classes_timing(self._h, C.byref(a), C.byref(s)))
+        return a.value, s.value
 
     def nearest_text(self, queries, k):
         """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
