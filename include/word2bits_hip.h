@@ -262,6 +262,10 @@ int w2b_suggested_threads(w2b_trainer *t, int32_t *out);
  * chosen from the word counts of w2b_set_vocab_counts and num_threads: 0 on flat distributions).  Any pointer may be NULL. */
 int w2b_worker_kernel_info(w2b_trainer *t, int32_t *resident, int32_t *radius, int32_t *column_bytes,
                            int32_t *workgroups_per_cu, int32_t *hot_rows);
+/* The plain kernel has two forms with the same results: a lean one for 16-byte columns, coherent rows, tables below 2 GiB, no
+ * atomic rows, reg == 0 and bitlevel 0..2, and the generic one for everything else.  *lean = 1 when w2b_train_step() runs the
+ * plain kernel in its lean form.  A trainer created with W2B_GENERIC_WORKER=1 in the environment always runs the generic form. */
+int w2b_worker_kernel_lean(w2b_trainer *t, int32_t *lean);
 
 /* ---- form (ii): explicit tuples (benchmark / single-step parity form) ------------------------
  * n centre words; ctx_off[n+1] CSR into ctx[] (context rows of u, ref :431-447);

@@ -528,14 +528,35 @@ __device__ __forceinline__ float log_sigmoid_term(const float f, const bool cent
 // TB: how rows are addressed (load_col): -1 = decided at run time from P.tab_bytes, 0 = one buffer resource per table (tables
 // below 2 GiB: the worker kernel's 16-byte-column instantiations are compiled for it since round 5 -- the run-time form costs
 // ~20 scalar instructions per row access and SGPRs that the kernel, at exactly its register budget, spills)
-template <int QM, int VEC, bool LOSS, int MM, int ATOM = 0, int TB = -1>
+// LEAN: the instruction-lean form for what a full-device launch with the default -reg 0 runs: 16-byte columns, coherent rows,
+// one buffer resource per table, no atomic rows, and P.reg == 0 GUARANTEED BY THE CALLER (w2b_workers_lean).  Same rows, same
+// order, same cache policy, same bits; what it leaves out:
+//   * the regularisation terms.  With reg == 0 the generic form computes ar2 = +0 and
+//       v row:  x' = x + (a - ar2 * x), a = g * avg        u row:  r' = r + (err - ar2 * r)
+//     For a finite x, ar2 * x is +0 (x >= +0) or -0 (x <= -0), and a - (+-0) is a itself, sign of zero included, except
+//     (-0) - (-0) = +0: the one case where the generic delta differs from a.  It reaches the stored value only for x = -0
+//     (x + (+0) = +0 where x + (-0) = -0), so the lean v update is x' = x + (a + 0.f): a + 0.f turns a = -0 into +0 and
+//     changes nothing else, and then x = +0 / -0 / anything finite gives the generic form's bits in all four sign cases
+//     (+0 + +0 = +0, -0 + +0 = +0, +0 and -0 with a != 0 give a).  err starts at +0 and only ever has terms added to it, so
+//     it is never -0 and the u update is r' = r + err as it stands.  Outside: a row that already holds inf or NaN
+//     (ar2 * x is NaN there, and the generic form turns the whole element into NaN; the lean form adds to it).
+//     The loss sum loses nothing: its reg * sum q^2 terms are only booked with reg != 0.
+//   * QM == 1: q = +-fl(1/3) and rounding is symmetric in the sign, so avg * q = +-fl(avg * fl(1/3)) and g * q =
+//     +-fl(g * fl(1/3)): one product per element and word / per target, then a select on the same `x < 0` that quant<1>
+//     uses (-0, +0, NaN -> +), instead of a product per element and target in the dot product and in the error sum.
+template <int QM, int VEC, bool LOSS, int MM, int ATOM = 0, int TB = -1, bool LEAN = false>
 __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &L, const QParam &qp,
                                              const int cw, const int nt, const float alpha,
                                              double &loss_acc, const XHot &X) {
+  static_assert(!LEAN || (VEC == 4 && MM == 0 && ATOM == 0 && TB == 0 && QM <= 2), "lean form: see w2b_workers_lean");
+  constexpr bool REG = !LEAN;                                   // may P.reg be non-zero?
+  constexpr bool ATOM_U = !(VEC == 4 && ATOM < 1), ATOM_V = !(VEC == 4 && ATOM < 2);   // can rows of u / v be updated with atomic adds?
+  constexpr bool THIRDS = LEAN && QM == 1;
+  constexpr float third = 1.f / 3.f;                            // fl(1/3), the magnitude quant<1> returns
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
   const int dim = P.dim, col0 = tid * VEC;
   const bool active = col0 < dim;
-  const float ar2 = (2.f * alpha) * P.reg;                      // 2*alpha*reg (ref :490,:501)
+  const float ar2 = REG ? (2.f * alpha) * P.reg : 0.f;          // 2*alpha*reg (ref :490,:501)
   constexpr int TC = TFor<LOSS>::value;                         // rows per chunk
 
   Col<VEC> x[TC];
@@ -555,11 +576,13 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
   };
   // row <- val (= old + d): a store (hot rows: to this XCD's copy), or an atomic add of d for rows 1..atomic_rank
   // (VEC == 4: only the ATOM instantiations look at the ranks; the 4-byte-column kernels decide at run time)
-  const int atomic_rank = (VEC == 4 && ATOM < 2) ? 0 : P.atomic_rank, atomic_rank_u = (VEC == 4 && ATOM < 1) ? 0 : P.atomic_rank_u;
+  // (an instantiation that never adds atomically has no atomic code: `row <= 0` is nothing the compiler can fold, and no row
+  // is row 0 -- 0 is the sentence end, and the draws of ref :456-458 skip it)
+  [[maybe_unused]] const int atomic_rank = ATOM_V ? P.atomic_rank : 0, atomic_rank_u = ATOM_U ? P.atomic_rank_u : 0;
   auto up_u = [&](int row, const Col<VEC> &val, const Col<VEC> &d) {
     if constexpr (VEC == 4) { if ((unsigned)(row - 1) < (unsigned)nhu) { xhot_st(X.cu, row - 1, nhu, dim, col0, val); return; } }
-    if (row <= atomic_rank_u) add_col<VEC, TB>(P.u, row, dim, col0, d, P.tab_bytes);
-    else store_col<VEC, MM, TB>(P.u, row, dim, col0, val, P.tab_bytes);
+    if constexpr (ATOM_U) { if (row <= atomic_rank_u) { add_col<VEC, TB>(P.u, row, dim, col0, d, P.tab_bytes); return; } }
+    store_col<VEC, MM, TB>(P.u, row, dim, col0, val, P.tab_bytes);
   };
   auto ld_v = [&](int row) -> Col<VEC> {
     if constexpr (VEC == 4) { if ((unsigned)(row - 1) < (unsigned)nhv) return xhot_ld(X.cv, row - 1, nhv, dim, col0); }
@@ -567,8 +590,8 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
   };
   auto up_v = [&](int row, const Col<VEC> &val, const Col<VEC> &d) {
     if constexpr (VEC == 4) { if ((unsigned)(row - 1) < (unsigned)nhv) { xhot_st(X.cv, row - 1, nhv, dim, col0, val); return; } }
-    if (row <= atomic_rank) add_col<VEC, TB>(P.v, row, dim, col0, d, P.tab_bytes);
-    else store_col<VEC, MM, TB>(P.v, row, dim, col0, val, P.tab_bytes);
+    if constexpr (ATOM_V) { if (row <= atomic_rank) { add_col<VEC, TB>(P.v, row, dim, col0, d, P.tab_bytes); return; } }
+    store_col<VEC, MM, TB>(P.v, row, dim, col0, val, P.tab_bytes);
   };
   // one chunk of target rows
   auto load_targets = [&](bool zero) {
@@ -587,7 +610,7 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
   // ---- phase A: context_avg = (1/cw) * sum_j quantize(u[ctx_j])   (ref :431-449)
   Col<VEC> avg;
   float regsq = 0.f;                       // LOSS with reg != 0: this thread's sum of q^2 over the window rows AND the target rows
-  const bool reg_on = P.reg != 0.f;
+  const bool reg_on = REG && P.reg != 0.f;
   float *fsave = reinterpret_cast<float *>(L.prev);
 #pragma unroll
   for (int e = 0; e < VEC; e++) avg.e[e] = 0.f;
@@ -616,6 +639,11 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
 #pragma unroll
     for (int e = 0; e < VEC; e++) avg.e[e] = active ? avg.e[e] / cwf : 0.f;   // ref :449
   }
+  [[maybe_unused]] Col<VEC> avg3;                               // THIRDS: |avg * q| of every element
+  if constexpr (THIRDS) {
+#pragma unroll
+    for (int e = 0; e < VEC; e++) avg3.e[e] = avg.e[e] * third;
+  }
 
   // ---- phase B: targets (ref :450-492)
   Col<VEC> err;
@@ -630,8 +658,11 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
       float t[VEC];
 #pragma unroll
       for (int e = 0; e < VEC; e++) {
-        const float q = quant<QM>(x[i].e[e], qp);
-        t[e] = avg.e[e] * q;                                    // ref :466 (re-associated as a binary tree)
+        if constexpr (THIRDS) t[e] = (x[i].e[e] < 0.f) ? -avg3.e[e] : avg3.e[e];
+        else {
+          const float q = quant<QM>(x[i].e[e], qp);
+          t[e] = avg.e[e] * q;                                  // ref :466 (re-associated as a binary tree)
+        }
       }
       // pairwise tree over the elements of a column
       const float s = (VEC == 4) ? (t[0] + t[1 % VEC]) + (t[2 % VEC] + t[3 % VEC]) : ((VEC == 2) ? t[0] + t[1 % VEC] : t[0]);
@@ -688,6 +719,7 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
     for (int i = 0; i < TC; i++) {
       if (i < n) {
         const float g = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gl), i));
+        [[maybe_unused]] const float g3 = g * third;            // THIRDS: |g * q|
         // (wave-uniform choice: rows[i] lives in SGPRs) a frequent row below the hot ones gets its delta as an atomic add;
         // every lane of the wavefront takes part in the transpose of that form, idle lanes with zeros
         const bool by_add = (VEC == 4 && ATOM >= 2) && rows[i] <= atomic_rank && !((unsigned)(rows[i] - 1) < (unsigned)nhv);
@@ -703,10 +735,14 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
             // opaque copy: re-derive the quantized value here instead of keeping VEC extra registers per
             // row alive since the dot product (halves the register footprint of a chunk)
             if (QM != 0) asm volatile("" : "+v"(xv));
-            const float q = quant<QM>(xv, qp);
-            if (LOSS && reg_on) regsq += q * q;                 // reg * sum q^2 of every target row (ref :463,:468-471)
-            err.e[e] += g * q;
-            dl.e[e] = g * avg.e[e] - ar2 * xv;
+            if constexpr (THIRDS) err.e[e] += (xv < 0.f) ? -g3 : g3;
+            else {
+              const float q = quant<QM>(xv, qp);
+              if (LOSS && reg_on) regsq += q * q;               // reg * sum q^2 of every target row (ref :463,:468-471)
+              err.e[e] += g * q;
+            }
+            if constexpr (REG) dl.e[e] = g * avg.e[e] - ar2 * xv;
+            else dl.e[e] = g * avg.e[e] + 0.f;                  // (-0 -> +0: what the generic form's `- ar2 * xv` does where it matters)
             x[i].e[e] = xv + dl.e[e];
           }
           if (!by_add) up_v(rows[i], x[i], dl);
@@ -770,15 +806,16 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
           const int m = L.umult[j0 + jj];
           if (m > 0) {
             const int crow = __builtin_amdgcn_readfirstlane(L.ctx[j0 + jj]);
-            const bool by_add = crow <= atomic_rank_u && !(VEC == 4 && (unsigned)(crow - 1) < (unsigned)nhu);   // (4-byte columns)
+            [[maybe_unused]] const bool by_add = ATOM_U && crow <= atomic_rank_u && !(VEC == 4 && (unsigned)(crow - 1) < (unsigned)nhu);   // (4-byte columns)
             Col<VEC> dl;
             for (int k = 0; k < m; k++) {      // a row that occurs m times in the window is updated m times
 #pragma unroll
               for (int e = 0; e < VEC; e++) {
-                dl.e[e] = err.e[e] - ar2 * r[jj].e[e];
+                if constexpr (REG) dl.e[e] = err.e[e] - ar2 * r[jj].e[e];
+                else dl.e[e] = err.e[e];
                 r[jj].e[e] = r[jj].e[e] + dl.e[e];
               }
-              if (by_add && k + 1 < m) up_u(crow, r[jj], dl);    // (every one of the m updates is an add of its own)
+              if constexpr (ATOM_U) { if (by_add && k + 1 < m) up_u(crow, r[jj], dl); }   // (every one of the m updates is an add of its own)
             }
             up_u(crow, r[jj], dl);
           }

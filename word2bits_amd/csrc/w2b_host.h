@@ -52,6 +52,7 @@ struct w2b_trainer {
   int xhot_nu = -1, xhot_nv = -1;       // layout the buffer currently has (-1: none)
   bool xhot_master_changed = true;      // the master rows may differ from what the copies were folded into
   bool debug = false;           // W2B_DEBUG was set when the trainer was created (diagnostics on stderr)
+  bool generic_worker = false;  // W2B_GENERIC_WORKER=1 was set when the trainer was created: the plain worker kernel runs its generic form
   const int32_t *corpus = nullptr;
   W2bDevBuf<int32_t> corpus_owned;
   long long n_tokens = 0;

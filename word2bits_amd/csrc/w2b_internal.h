@@ -105,7 +105,9 @@ hipError_t w2b_launch_tuples(const W2bParams &p, long long n, const int32_t *cen
                              const int32_t *ctx_off, const int32_t *ctx, const int32_t *neg,
                              float alpha, int grid, int num_cus, int per_cu_override, bool loss,
                              hipStream_t s);
-hipError_t w2b_launch_workers(const W2bParams &p, long long max_positions, bool loss, hipStream_t s, int grid = 0);   // grid workgroups = workers worker_base .. worker_base + grid
+hipError_t w2b_launch_workers(const W2bParams &p, long long max_positions, bool loss, hipStream_t s, int grid = 0,   // grid workgroups = workers worker_base .. worker_base + grid
+                              bool force_generic = false);
+bool w2b_workers_lean(const W2bParams &p, bool force_generic);          // does w2b_launch_workers run the lean form of the kernel?
 // sentence-resident variant (w2b_kernels_resident.hip): radius >= 0 when it can run for this shape
 int w2b_resident_plan(int dim, int window, int negative);
 bool w2b_resident_atomic_ok(const W2bParams &p, int radius);           // atomic_rank > 0: can the sentence-resident kernel do it?

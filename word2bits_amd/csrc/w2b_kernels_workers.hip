@@ -5,7 +5,7 @@
 namespace {
 // ------------------------------------------------------------------------------------ form (i): workers
 
-template <int QM, int VEC, bool LOSS, int MAXTHREADS, int MM, int ATOM = 0, int TB = -1>
+template <int QM, int VEC, bool LOSS, int MAXTHREADS, int MM, int ATOM = 0, int TB = -1, bool LEAN = false>
 __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES : 1)) k_train_workers(const W2bParams P, const long long max_positions) {
   extern __shared__ int smem[];
   WordLds L = carve_word_lds(smem, P.window, P.negative, VEC);
@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(MAXTHREADS, (MAXTHREADS <= 256 ? W2B_MINWAVES 
     if constexpr (VEC == 1 && MAXTHREADS == 1024) wide = P.wide != 0;
     if (cw > 0) {
       if (wide) { if constexpr (VEC == 1 && MAXTHREADS == 1024) process_word_wide<QM, LOSS, MM>(P, L, qp, cw, nt, alpha, loss_acc); }
-      else process_word<QM, VEC, LOSS, MM, ATOM, TB>(P, L, qp, cw, nt, alpha, loss_acc, XH);
+      else process_word<QM, VEC, LOSS, MM, ATOM, TB, LEAN>(P, L, qp, cw, nt, alpha, loss_acc, XH);
     } else __syncthreads();
     if (VEC == 4 && hot && ++since_merge >= P.hot_period) {
       since_merge = 0;
@@ -119,7 +119,18 @@ int w2b_workers_per_cu(const W2bParams &p, bool loss) {
   return nb > 0 ? nb : 1;
 }
 
-hipError_t w2b_launch_workers(const W2bParams &p, long long max_positions, bool loss, hipStream_t s, int grid) {
+// Does the lean form of the kernel (process_word<..., LEAN>, w2b_device.hpp) run this launch?  16-byte columns, at most 256
+// threads, coherent rows, one buffer resource per table, no atomic rows, reg == 0, bitlevel 0..2 -- what a full-device launch
+// with the default -reg 0 is.  Everything else, and every launch of a trainer created under W2B_GENERIC_WORKER=1, runs the
+// generic form.
+bool w2b_workers_lean(const W2bParams &p, bool force_generic) {
+  int vec;
+  const int threads = w2b_block_threads(p.dim, &vec);
+  return !force_generic && vec == 4 && threads <= 256 && p.mem_mode == 0 && !p.exact && p.tab_bytes != 0 && p.atomic_rank <= 0 &&
+         p.atomic_rank_u <= 0 && p.reg == 0.f && p.bitlevel >= 0 && p.bitlevel <= 2;
+}
+
+hipError_t w2b_launch_workers(const W2bParams &p, long long max_positions, bool loss, hipStream_t s, int grid, bool force_generic) {
   if (grid <= 0) grid = p.num_threads - p.worker_base;
   int vec;
   const int threads = w2b_block_threads(p.dim, &vec);
@@ -134,6 +145,13 @@ hipError_t w2b_launch_workers(const W2bParams &p, long long max_positions, bool 
     if constexpr (MM == 0) {          // coherent rows, 16-byte columns, at most 256 threads: the instantiations with the row addressing
       // fixed at compile time (TB) and, where rows are updated with atomic adds (w2b_tuning.atomic_rank*), the ATOM ones
       const int atom = p.atomic_rank > 0 ? 2 : (p.atomic_rank_u > 0 ? 1 : 0);
+      if constexpr (QM <= 2) {
+        if (w2b_workers_lean(p, force_generic)) {
+          if (loss) hipLaunchKernelGGL((k_train_workers<QM, 4, true, 256, 0, 0, 0, true>), dim3(grid), dim3(threads), lds, s, p, max_positions);
+          else hipLaunchKernelGGL((k_train_workers<QM, 4, false, 256, 0, 0, 0, true>), dim3(grid), dim3(threads), lds, s, p, max_positions);
+          return hipGetLastError();
+        }
+      }
       if (vec == 4 && threads <= 256 && (atom || p.tab_bytes != 0)) {
 #define W2B_LAUNCH_A(LOSS, ATOM, TB) hipLaunchKernelGGL((k_train_workers<QM, 4, LOSS, 256, 0, ATOM, TB>), dim3(grid), dim3(threads), lds, s, p, max_positions)
 #define W2B_LAUNCH_AT(LOSS, ATOM) do { if (p.tab_bytes != 0) W2B_LAUNCH_A(LOSS, ATOM, 0); else W2B_LAUNCH_A(LOSS, ATOM, -1); } while (0)

@@ -158,6 +158,10 @@ extern "C" int w2b_trainer_create(const w2b_config *cfg, w2b_trainer **out) {
   HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
   t->in.num_cus = prop.multiProcessorCount;
   t->debug = getenv("W2B_DEBUG") != nullptr;
+  {
+    const char *g = getenv("W2B_GENERIC_WORKER");
+    t->generic_worker = g && g[0] == '1' && g[1] == 0;
+  }
   t->in.tune = w2b_default_tuning();
   HIPCHK(t->stream.create());
   t->table_elems = (long long)cfg->vocab_size * cfg->layer1_size;
@@ -620,6 +624,15 @@ extern "C" int w2b_worker_kernel_info(w2b_trainer *t, int32_t *resident, int32_t
   return W2B_OK;
 }
 
+extern "C" int w2b_worker_kernel_lean(w2b_trainer *t, int32_t *lean) {
+  NEED(t);
+  if (!lean) return fail(W2B_EINVAL, "w2b_worker_kernel_lean: null");
+  const W2bLaunchPlan lp = w2b_plan_launch(t->in, t->in.cfg.num_threads);
+  const W2bParams p = make_params(t, lp);
+  *lean = (lp.kernel == W2B_KERNEL_PLAIN && w2b_workers_lean(p, t->generic_worker)) ? 1 : 0;
+  return W2B_OK;
+}
+
 extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
   NEED(t);
   if (!t->corpus || !t->shards_set) return fail(W2B_ESTATE, "w2b_train_step: corpus/shards not set");
@@ -659,7 +672,8 @@ extern "C" int w2b_train_step(w2b_trainer *t, int64_t max_positions) {
     for (int base = 0; base < t->in.cfg.num_threads; base += conc) {
       q.worker_base = base;
       q.num_threads = t->in.cfg.num_threads;
-      HIPCHK(w2b_launch_workers(q, max_positions, t->in.cfg.compute_loss != 0, t->stream, base + conc < t->in.cfg.num_threads ? conc : t->in.cfg.num_threads - base));
+      HIPCHK(w2b_launch_workers(q, max_positions, t->in.cfg.compute_loss != 0, t->stream, base + conc < t->in.cfg.num_threads ? conc : t->in.cfg.num_threads - base,
+                                t->generic_worker));
     }
   }
   HIPCHK(timing_end(t));

@@ -280,6 +280,12 @@ class Trainer:
         check(lib().w2b_worker_kernel_info(self._h, C.byref(a), None, None, None, None))
         return ("plain", "resident", "groups")[a.value]
 
+    def worker_kernel_lean(self):
+        """does train_step() run the plain kernel in its lean form (False: its generic form, or another kernel)?"""
+        a = C.c_int32(0)
+        check(lib().w2b_worker_kernel_lean(self._h, C.byref(a)))
+        return a.value == 1
+
     def suggested_threads(self):
         n = C.c_int32(0)
         check(lib().w2b_suggested_threads(self._h, C.byref(n)))
