@@ -416,6 +416,95 @@ int w2b_classes_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t
                      const int32_t *init, int32_t *cls, float *score, int32_t *T_out, int64_t *counts, int32_t *iters_run,
                      int64_t *moved);
 
+/* ---- documents: the corpus texts nearest to a query text, by relaxed word mover's similarity ------------------------------
+ * "Which of my documents is closest to this sentence?"  Every other question of this header is answered with ROWS; this one is
+ * answered with DOCUMENTS of a corpus that the handle keeps.  The measure is the relaxed word mover's distance (Kusner et al.
+ * 2015; gensim's wmdistance is the unrelaxed form) in its similarity form: every word of one text is matched to its best word
+ * of the other, and the matches are averaged -- stronger than the cosine of two pooled means, which w2b_eval_bag and
+ * w2b_embed_bag offer.  A bits or a codes handle is required; an fp32 handle is W2B_EINVAL ("not available on an fp32 handle:
+ * load the file with bits or codes"), as for w2b_eval_cosmul.  Handles made by *_from_trainer in bits / codes mode work like
+ * loaded ones.
+ *   documents: a corpus is ids[n_ids] plus offsets[n_docs + 1], non-decreasing, offsets[0] == 0, offsets[n_docs] == n_ids, as
+ *     in w2b_eval_bag; document d is ids[offsets[d] .. offsets[d + 1]).  An id < 0 is padding and contributes nothing; an id >=
+ *     w2b_eval_words(e) is W2B_EINVAL; a document of more than W2B_EVAL_MAX_DOC = 1024 positions, padding included, is
+ *     W2B_EINVAL; n_docs <= 0x7FFFFF00.  Queries have the same form and the same limits.  m(X) = the number of ids >= 0 in text
+ *     X; a repeated id counts every time.
+ *   word pairs: for rows x and c
+ *       bits   I(x,c) = size - 2 * H(x,c), an exact integer in [-size, size] (bits mode above);
+ *       codes  cos(x,c) = ((float)J(x,c) * w(x)) * w(c), J and w as in codes mode: exactly the expression that
+ *              w2b_eval_neighbors scores by, the conversion rounded to nearest even, both multiplies rounded on their own,
+ *              nothing contracted; its fixed-point image is F(x,c) = (int64) ldexp(cos(x,c), 50).
+ *     A handle with size >= 2^21 is W2B_EINVAL.  Below that limit: 1024 * size < 2^31, so a sum of 1024 values I fits an int32.
+ *     cos is never -0 and never NaN: w is finite and positive, (float)J is +0 exactly when J == 0 (so cos = +0) and otherwise a
+ *     non-zero integer-valued float, and no product underflows: |(float)J| >= 1 and w >= 1 / sqrt(9 * size) up to an ulp, so a
+ *     non-zero cos is at least about 1 / (9 * size) > 2^-25 in magnitude.  A float of that size is a multiple of 2^-48, and
+ *     |cos| stays below 2 (it overshoots 1 by a few ulp at most): F is an exact integer below 2^51 in magnitude, the
+ *     conversion drops nothing, and 1024 of them sum below 2^61.
+ *   directed coverage of X by Y, both texts with m > 0:
+ *       bits   R(X->Y) = sum over the positions x of X with id >= 0 of  max over the positions c of Y with id >= 0 of  I(x,c),
+ *              an int32;
+ *       codes  A(X->Y) = the same sum with F in place of I, an int64.
+ *     Sums of integers and maxima of integers: the result depends neither on the order of the positions in either text nor on
+ *     how a kernel splits the work, and no float is ever accumulated.  (The maximum may be taken over the floats cos and
+ *     converted afterwards: the conversion is monotone and exact.)
+ *   scores, float32, each conversion rounded to nearest even and ONE correctly rounded division:
+ *       bits   s(X->Y) = (float)R / (float)(m(X) * size);
+ *       codes  s(X->Y) = (float)A / ((float)m(X) * 0x1p50f), the divisor being exact.
+ *     symmetric = 0: score(Q, D) = s(Q->D), how well every query word is matched in D -- for short queries against long
+ *     documents.  symmetric = 1: score = min(s(Q->D), s(D->Q)), the similarity form of RWMD's maximum of its two lower bounds.
+ *     Anything else is W2B_EINVAL.  If m(Q) == 0 or m(D) == 0 the score is +0.  No score is subnormal: a non-zero one is at
+ *     least 2^-31 (bits) or 2^-60 (codes) in magnitude.
+ *   two consequences: a one-id query [r] against the corpus of the one-id documents [c], c = 0 .. words - 1, returns bit for bit
+ *     what w2b_eval_bag([r], exclude_own = 0) returns, rows and scores, on both handle kinds and with either `symmetric`; and
+ *     permuting the positions inside any document or query changes no output bit.
+ *   answers: per query the documents with score > 0, by score descending, equal float scores in ascending document index -- the
+ *     codes key, score bits << 32 | ~index.  best / bestd are [nq][k] in the shape of w2b_eval_topk: a short list ends in index
+ *     -1 / score 0, bestd may be NULL, 1 <= k <= W2B_EVAL_MAX_K.  Nothing is excluded: a document identical to the query is an
+ *     answer.  all_scores is NULL or [nq][n_docs] and receives every score, answers or not (W2B_EINVAL when nq * n_docs > 2^28).
+ * Everything is validated before anything is launched -- what does not depend on the handle first (k, symmetric, nq, the
+ * offsets, the lengths; so a NULL handle with a bad k is W2B_EINVAL for the k, as in w2b_eval_bag), then the handle (its kind,
+ * its size, a corpus being set: a query call without one is W2B_EINVAL), then the ids -- with the cause in w2b_last_error(); on
+ * error no output is touched.  nq == 0 is W2B_OK as soon as the checks that need no handle have passed: nothing is asked, so
+ * neither the handle nor a corpus is needed.
+ * How it runs (word2bits_amd/csrc/w2b_kernels_evaldocs.hip): a vocabulary row occurs in a corpus many times, so per chunk of
+ * queries a pair table Tab[c][x] = I or cos of every vocabulary row c against every query position x is built first (each
+ * query's columns padded to a whole 64-byte line), with the largest value of each row over a query's own columns beside it;
+ * then the corpus ids are streamed once per query of the chunk: Q->D is a per-lane running maximum over the slices Tab[id][the query's columns],
+ * D->Q a gather of the row maxima.  w2b_eval_set_topk_scratch bounds the scratch of a chunk of queries; a chunk is never
+ * smaller than one query, whose own need is 4 * words * (its ids >= 0 rounded up to 16, plus 1) bytes of table, 8 * k *
+ * (ceil(n_docs / 1024) + 1) bytes of selection slots and, with all_scores, 4 * n_docs bytes; results never depend on the
+ * bound.  w2b_eval_timing_read counts these launches (one per chunk: table + walk + merge), macs = (query positions x document
+ * positions, padding included, summed over all pairs) x size; w2b_eval_docs_timing splits the last call's device time into the
+ * table phase and the walk phase (walk + merge). */
+#define W2B_EVAL_MAX_DOC 1024
+/* copies the corpus to the device and keeps it on the handle; replaces an earlier one; n_docs == 0 drops it.  On error the
+ * earlier corpus stays. */
+int w2b_eval_docs_set(w2b_eval *e, int64_t n_ids, const int32_t *ids, int64_t n_docs, const int64_t *offsets);
+/* The corpus from text: one document per LINE of text[0..len) (every line counts, empty ones too: index = line number - 1),
+ * split on white space and upper-cased as w2b_eval_nearest_text does; words that w2b_eval_lookup does not find are dropped
+ * and counted in *dropped; a line with more than 1024 known words is W2B_EINVAL naming the line, and the earlier corpus stays.
+ * n_docs and dropped may be NULL. */
+int w2b_eval_docs_set_text(w2b_eval *e, const char *text, int64_t len, int64_t *n_docs, int64_t *dropped);
+int64_t w2b_eval_docs_count(const w2b_eval *e);
+int w2b_eval_docs(w2b_eval *e, int64_t n_qids, const int32_t *qids, int64_t nq, const int64_t *qoffsets,
+                  int32_t symmetric, int32_t k, int32_t *best, float *bestd, float *all_scores /* [nq][n_docs] or NULL */);
+/* The text form of `./nearest ... bits|codes docs CORPUS.txt`: every non-empty line is one query text, upper-cased and looked
+ * up as in w2b_eval_nearest_text, unknown words dropped.  The head of an answer is the line's words joined by one space,
+ * "<WORDS>:\n", followed by one line "<rank>\t<line number of the document, from 1>\t<score %.6f>\n" per answer.  Error lines:
+ * "<head>: no word in vocabulary\n" and "<head>: expected at most 1024 words\n".  All valid lines are scored in one
+ * w2b_eval_docs batch. */
+int w2b_eval_docs_text(w2b_eval *e, const char *queries, int64_t len, int32_t symmetric, int32_t k,
+                       char **out, int64_t *out_len);
+int w2b_eval_docs_timing(w2b_eval *e, double *table_ms, double *walk_ms);
+/* Host twin of the document kernels (pure C, no device): ONE query qids[0..n_q) against every document, every word pair
+ * computed directly from packed[words][bitlevel * ceil(dim / 64)] (no table), bitlevel 1 (bits) or 2 (codes): dir_out[2][n_docs]
+ * = R or A of Q->D, then of D->Q, as int64 (0 where either text has m == 0), score_out[n_docs] = the float score.  Either
+ * output may be NULL.  W2B_EINVAL as w2b_eval_docs_set and w2b_eval_docs have it, and for a bitlevel other than 1 or 2. */
+int w2b_docs_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel,
+                         int64_t n_ids, const int32_t *ids, int64_t n_docs, const int64_t *offsets,
+                         int64_t n_q, const int32_t *qids, int32_t symmetric,
+                         int64_t *dir_out, float *score_out);
+
 #ifdef __cplusplus
 }
 #endif

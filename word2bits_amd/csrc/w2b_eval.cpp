@@ -4,10 +4,10 @@
 // w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
 // adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms, w2b_kernels_evalvec.hip
 // the float-vector question on them, w2b_kernels_evalcosmul.hip the 3CosMul scan on 1-bit rows, w2b_kernels_evalclasses.hip the
-// k-means word classes on both packed forms (whose wq = 1 / sqrt(N_k) the host builds like the bag question's).  No arithmetic on scores happens here (the exceptions are question weights: the bag
+// k-means word classes on both packed forms (whose wq = 1 / sqrt(N_k) the host builds like the bag question's), w2b_kernels_evaldocs.hip the document question on them.  No arithmetic on scores happens here (the exceptions are question weights: the bag
 // question's 1 / sqrt(N_T), built from the integer the device sums, and the vector question's wx with the fp32 handle's
 // vec = x * wx; and the 3CosMul table u = A / size of a bits handle) and there is no CPU fallback (w2b_codes_scores_host,
-// w2b_bag_scores_host, w2b_vector_scores_host, w2b_cosmul_scores_host and w2b_classes_host are the tests' twins of the kernels).
+// w2b_bag_scores_host, w2b_vector_scores_host, w2b_cosmul_scores_host, w2b_classes_host and w2b_docs_scores_host are the tests' twins of the kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
@@ -79,6 +79,12 @@ struct w2b_eval {
   int64_t launches = 0;
   double macs = 0;
   double cls_assign_ms = 0, cls_sums_ms = 0;             // w2b_eval_classes: the two shares of its last call's device time
+  // w2b_eval_docs: the corpus of w2b_eval_docs_set WITHOUT its padding ids, its bounds [docs_n + 1], the positions it was given
+  // with (padding included: the multiply-add count), per-call buffers, and the two shares of the last call's device time
+  int32_t *docs_ids = nullptr;
+  long long *docs_off = nullptr;
+  int64_t docs_n = 0, docs_positions = 0;
+  double docs_table_ms = 0, docs_walk_ms = 0;
   // top-k scratch of one launch: bound / buckets / slot counts / slots / merged keys
   void *tk_buf = nullptr;
   size_t tk_bytes = 0;
@@ -92,6 +98,8 @@ static void eval_release(w2b_eval *e) {
   if (e->B) (void)hipFree(e->B);
   if (e->wrow) (void)hipFree(e->wrow);
   if (e->utab) (void)hipFree(e->utab);
+  if (e->docs_ids) (void)hipFree(e->docs_ids);
+  if (e->docs_off) (void)hipFree(e->docs_off);
   if (e->P) (void)hipFree(e->P);
   if (e->Q) (void)hipFree(e->Q);
   if (e->b123) (void)hipFree(e->b123);
@@ -780,6 +788,132 @@ extern "C" int w2b_vector_scores_host(const uint64_t *packed, int64_t words, int
   return W2B_OK;
 }
 
+namespace {
+constexpr int64_t kDocsMaxSize = 1ll << 21;      // size below it: 1024 * size < 2^31 and ldexp(cos, 50) is an integer
+constexpr int64_t kDocsMaxDocs = 0x7FFFFF00ll;
+constexpr int64_t kDocsMaxAll = 1ll << 28;       // nq * n_docs of an all_scores request
+
+// what w2b_eval_docs_set, w2b_eval_docs and the host twin refuse in texts given as ids + offsets before they look at a handle
+// or a table (empty: nothing); `what` = "document" or "query"
+std::string bad_texts(int64_t n_ids, const int32_t *ids, int64_t n, const int64_t *offsets, const char *what) {
+  if (n < 0 || n_ids < 0 || (n > 0 && !offsets) || (n_ids > 0 && !ids)) return "bad argument";
+  if (n == 0 ? n_ids != 0 : (offsets[0] != 0 || offsets[n] != n_ids))
+    return std::string(what) + " offsets must start at 0 and end at the number of ids";
+  for (int64_t d = 0; d < n; d++) {
+    if (offsets[d + 1] < offsets[d] || offsets[d + 1] > n_ids) return std::string(what) + " offsets must not decrease";
+    if (offsets[d + 1] - offsets[d] > W2B_EVAL_MAX_DOC) return std::string("a ") + what + " holds at most 1024 positions";
+  }
+  return std::string();
+}
+bool bad_text_ids(int64_t n_ids, const int32_t *ids, int64_t words) {
+  for (int64_t i = 0; i < n_ids; i++)
+    if (ids[i] >= words) return true;
+  return false;
+}
+const char *const kDocsSize = "size must be below 2^21 (1024 * size < 2^31)";
+const char *const kDocsFp32 = "not available on an fp32 handle: load the file with bits or codes";
+
+// the float steps of the header: one directed score from its integer sum
+inline float docs_score(int32_t bitlevel, int64_t sum, int64_t m, int64_t dim) {
+#pragma clang fp contract(off)
+  if (bitlevel == 1) return (float)(int32_t)sum / (float)(int32_t)(m * dim);
+  const float div = (float)m * 0x1p50f;          // exact
+  return (float)sum / div;
+}
+}  // namespace
+
+// Host twin of the document kernels: every (query position, document position) pair from the packed rows themselves, the
+// maxima and the sums in 64-bit integers, the float steps of the header one at a time (this file is built with
+// -ffp-contract=off, and the function says so again).
+extern "C" int w2b_docs_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                                    const int32_t *ids, int64_t n_docs, const int64_t *offsets, int64_t n_q,
+                                    const int32_t *qids, int32_t symmetric, int64_t *dir_out, float *score_out) {
+#pragma clang fp contract(off)
+  const std::string who = "w2b_docs_scores_host";
+  if (symmetric != 0 && symmetric != 1) return efail(W2B_EINVAL, who + ": symmetric must be 0 or 1");
+  if (n_q < 0 || (n_q > 0 && !qids)) return efail(W2B_EINVAL, who + ": bad argument");
+  if (n_q > W2B_EVAL_MAX_DOC) return efail(W2B_EINVAL, who + ": a query holds at most 1024 positions");
+  if (n_docs > kDocsMaxDocs) return efail(W2B_EINVAL, who + ": at most 0x7FFFFF00 documents");
+  const std::string why = bad_texts(n_ids, ids, n_docs, offsets, "document");
+  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
+  if (!packed || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (dim >= kDocsMaxSize) return efail(W2B_EINVAL, who + ": " + kDocsSize);
+  if (bad_text_ids(n_ids, ids, words)) return efail(W2B_EINVAL, who + ": document id out of range");
+  if (bad_text_ids(n_q, qids, words)) return efail(W2B_EINVAL, who + ": query id out of range");
+  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
+  auto valid = [&](int64_t b) { return (b + 1) * 64 <= dim ? ~0ull : (1ull << (dim - b * 64)) - 1; };   // padding bits do not count
+  const std::vector<float> wt = bitlevel == 2 ? codes_weights(dim) : std::vector<float>();
+  auto weight = [&](const uint64_t *r) {
+    int64_t n3 = 0;
+    for (int64_t b = 0; b < nb; b++) n3 += __builtin_popcountll(r[2 * b + 1] & valid(b));
+    return wt[(size_t)n3];
+  };
+  // I(x, c), or F(x, c) = (int64) ldexp(cos(x, c), 50)
+  auto pair = [&](const uint64_t *x, float wx, const uint64_t *c, float wc) -> int64_t {
+    if (bitlevel == 1) {
+      int64_t h = 0;
+      for (int64_t b = 0; b < nb; b++) h += __builtin_popcountll((x[b] ^ c[b]) & valid(b));
+      return dim - 2 * h;
+    }
+    int64_t j = 0;
+    for (int64_t b = 0; b < nb; b++) {
+      const uint64_t v = valid(b), neg = (x[2 * b] ^ c[2 * b]) & v, pos = ~neg & v;
+      const uint64_t mx = x[2 * b + 1], mc = c[2 * b + 1];
+      auto mag = [&](uint64_t m) {
+        return (int64_t)__builtin_popcountll(m) + 2 * __builtin_popcountll(m & mx) + 2 * __builtin_popcountll(m & mc) +
+               4 * __builtin_popcountll(m & mx & mc);
+      };
+      j += mag(pos) - mag(neg);
+    }
+    const float pj = (float)(int32_t)j * wx;
+    const float cs = pj * wc;
+    return (int64_t)ldexpf(cs, 50);
+  };
+  std::vector<const uint64_t *> qr;
+  std::vector<float> qw;
+  for (int64_t i = 0; i < n_q; i++)
+    if (qids[i] >= 0) {
+      qr.push_back(packed + (int64_t)qids[i] * wpr);
+      qw.push_back(bitlevel == 2 ? weight(qr.back()) : 0.f);
+    }
+  const int64_t mq = (int64_t)qr.size();
+  std::vector<int64_t> best_x((size_t)mq);
+  for (int64_t d = 0; d < n_docs; d++) {
+    int64_t md = 0, r_qd = 0, r_dq = 0;
+    for (int64_t i = offsets[d]; i < offsets[d + 1]; i++) {
+      if (ids[i] < 0 || mq == 0) continue;
+      const uint64_t *c = packed + (int64_t)ids[i] * wpr;
+      const float wc = bitlevel == 2 ? weight(c) : 0.f;
+      int64_t best_c = 0;
+      for (int64_t x = 0; x < mq; x++) {
+        const int64_t v = pair(qr[(size_t)x], qw[(size_t)x], c, wc);
+        if (md == 0 || v > best_x[(size_t)x]) best_x[(size_t)x] = v;
+        if (x == 0 || v > best_c) best_c = v;
+      }
+      r_dq += best_c;
+      md++;
+    }
+    if (md > 0)
+      for (int64_t x = 0; x < mq; x++) r_qd += best_x[(size_t)x];
+    if (dir_out) {
+      dir_out[d] = r_qd;
+      dir_out[n_docs + d] = r_dq;
+    }
+    if (!score_out) continue;
+    float sc = 0.f;
+    if (mq > 0 && md > 0) {
+      sc = docs_score(bitlevel, r_qd, mq, dim);
+      if (symmetric) {
+        const float s2 = docs_score(bitlevel, r_dq, md, dim);
+        sc = s2 < sc ? s2 : sc;
+      }
+    }
+    score_out[d] = sc;
+  }
+  return W2B_OK;
+}
+
 extern "C" void w2b_eval_free(w2b_eval *e) { eval_release(e); }
 extern "C" int64_t w2b_eval_words(const w2b_eval *e) { return e ? e->words : 0; }
 extern "C" int64_t w2b_eval_size(const w2b_eval *e) { return e ? e->size : 0; }
@@ -1464,6 +1598,173 @@ extern "C" int w2b_eval_cosmul(w2b_eval *e, int64_t nq, const int32_t *b1, const
   return eval_scan_chunks(e, ScanCosmulCodes(e, k), in, nq, best, bestd, who, 3.0);
 }
 
+// ------------------------------------------------------------------------------------ documents
+// The corpus of the document question: every check first -- what needs no handle, then the handle, then the ids -- then the
+// ids >= 0 alone go to the device with their own bounds (padding contributes nothing, so the walk never sees it).
+extern "C" int w2b_eval_docs_set(w2b_eval *e, int64_t n_ids, const int32_t *ids, int64_t n_docs, const int64_t *offsets) {
+  const std::string who = "w2b_eval_docs_set";
+  if (n_docs > kDocsMaxDocs) return efail(W2B_EINVAL, who + ": at most 0x7FFFFF00 documents");
+  const std::string why = bad_texts(n_ids, ids, n_docs, offsets, "document");
+  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": " + kDocsFp32);
+  if (e->size >= kDocsMaxSize) return efail(W2B_EINVAL, who + ": " + kDocsSize);
+  if (bad_text_ids(n_ids, ids, e->words)) return efail(W2B_EINVAL, who + ": document id out of range");
+  EHIP(hipSetDevice(e->device));
+  EHIP(hipStreamSynchronize(e->stream));          // (every call ends synchronised: nothing reads the corpus that is replaced)
+  std::vector<int32_t> h_ids;
+  std::vector<long long> h_off((size_t)n_docs + 1, 0);
+  h_ids.reserve((size_t)n_ids);
+  for (int64_t d = 0; d < n_docs; d++) {
+    for (int64_t i = offsets[d]; i < offsets[d + 1]; i++)
+      if (ids[i] >= 0) h_ids.push_back(ids[i]);
+    h_off[(size_t)d + 1] = (long long)h_ids.size();
+  }
+  int32_t *d_ids = nullptr;
+  long long *d_off = nullptr;
+  if (n_docs > 0) {
+    if (hipMalloc(&d_ids, h_ids.size() * 4 + 4) != hipSuccess || hipMalloc(&d_off, h_off.size() * 8) != hipSuccess) {
+      if (d_ids) (void)hipFree(d_ids);
+      return efail(W2B_ENOMEM, who + ": device allocation failed");
+    }
+    hipError_t he = hipMemcpy(d_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice);
+    if (he == hipSuccess && !h_ids.empty()) he = hipMemcpy(d_ids, h_ids.data(), h_ids.size() * 4, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+      (void)hipFree(d_ids);
+      (void)hipFree(d_off);
+      return efail(W2B_EHIP, who + ": " + hipGetErrorString(he));
+    }
+  }
+  if (e->docs_ids) (void)hipFree(e->docs_ids);
+  if (e->docs_off) (void)hipFree(e->docs_off);
+  e->docs_ids = d_ids;
+  e->docs_off = d_off;
+  e->docs_n = n_docs;
+  e->docs_positions = n_ids;
+  return W2B_OK;
+}
+
+extern "C" int64_t w2b_eval_docs_count(const w2b_eval *e) { return e ? e->docs_n : 0; }
+
+namespace {
+inline int64_t docs_pad16(int64_t m) { return (m + 15) / 16 * 16; }
+inline size_t docs_align(size_t b) { return (b + 255) / 256 * 256; }
+}  // namespace
+
+// The document question: every check first, then the chunks of queries.  A chunk is the longest run of queries whose
+// scratch stays within the bound of w2b_eval_set_topk_scratch, never less than one query; per chunk the pair table (timed
+// as the table phase), then the walk and the merge (the walk phase).
+extern "C" int w2b_eval_docs(w2b_eval *e, int64_t n_qids, const int32_t *qids, int64_t nq, const int64_t *qoffsets,
+                             int32_t symmetric, int32_t k, int32_t *best, float *bestd, float *all_scores) {
+  const std::string who = "w2b_eval_docs";
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  if (symmetric != 0 && symmetric != 1) return efail(W2B_EINVAL, who + ": symmetric must be 0 or 1");
+  if (nq > 0 && !best) return efail(W2B_EINVAL, who + ": bad argument");
+  const std::string why = bad_texts(n_qids, qids, nq, qoffsets, "query");
+  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
+  if (nq == 0) return W2B_OK;                      // nothing is asked: no handle and no corpus is needed
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": " + kDocsFp32);
+  if (e->size >= kDocsMaxSize) return efail(W2B_EINVAL, who + ": " + kDocsSize);
+  if (e->docs_n == 0) return efail(W2B_EINVAL, who + ": no corpus is set (w2b_eval_docs_set)");
+  if (all_scores && (__int128)nq * e->docs_n > kDocsMaxAll)
+    return efail(W2B_EINVAL, who + ": all_scores holds at most 2^28 scores (nq * n_docs)");
+  if (bad_text_ids(n_qids, qids, e->words)) return efail(W2B_EINVAL, who + ": query id out of range");
+  e->docs_table_ms = e->docs_walk_ms = 0;
+  EHIP(hipSetDevice(e->device));
+  const int64_t words = e->words, n_docs = e->docs_n;
+  const int bl = e->codes ? 2 : 1;
+  const int64_t splits = (n_docs + W2B_DOCS_PER_BLOCK - 1) / W2B_DOCS_PER_BLOCK;
+  const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+  // one query's own need: its columns of the table and its column of row maxima, its slots and merged keys, its scores
+  auto need = [&](int64_t m) {
+    return (docs_pad16(m) + 1) * words * 4 + (splits + 1) * k * 8 + (all_scores ? n_docs * 4 : 0);
+  };
+  std::vector<int32_t> h_col, h_qcol, h_qm;
+  std::vector<unsigned long long> keys;
+  std::vector<float> h_all;
+  EventPair ev, ev2;
+  EHIP(ev.create());
+  EHIP(ev2.create());
+  for (int64_t q0 = 0; q0 < nq;) {
+    // the chunk: its queries side by side as columns, each one's ids >= 0 first, padded to a whole 64-byte line
+    h_col.clear();
+    h_qcol.assign(1, 0);
+    h_qm.clear();
+    int64_t n = 0, used = 0, positions = 0;
+    while (q0 + n < nq && n < 32768) {
+      int64_t m = 0;
+      for (int64_t i = qoffsets[q0 + n]; i < qoffsets[q0 + n + 1]; i++) m += qids[i] >= 0;
+      if (n > 0 && used + need(m) > budget) break;
+      used += need(m);
+      for (int64_t i = qoffsets[q0 + n]; i < qoffsets[q0 + n + 1]; i++)
+        if (qids[i] >= 0) h_col.push_back(qids[i]);
+      h_col.resize((size_t)(h_qcol.back() + docs_pad16(m)), -1);
+      h_qcol.push_back((int32_t)h_col.size());
+      h_qm.push_back((int32_t)m);
+      positions += qoffsets[q0 + n + 1] - qoffsets[q0 + n];
+      n++;
+    }
+    const int64_t tcols = (int64_t)h_col.size();
+    // one buffer for the chunk's descriptors, one for its scratch
+    const size_t o_qcol = docs_align((size_t)tcols * 4), o_qm = o_qcol + docs_align((size_t)(n + 1) * 4);
+    if (eval_reserve_bag(&e->bag_buf, &e->bag_bytes, o_qm + docs_align((size_t)n * 4)) != W2B_OK)
+      return efail(W2B_ENOMEM, who + ": device allocation failed");
+    int32_t *d_col = (int32_t *)e->bag_buf, *d_qcol = (int32_t *)((char *)e->bag_buf + o_qcol),
+            *d_qm = (int32_t *)((char *)e->bag_buf + o_qm);
+    const size_t o_rmax = docs_align((size_t)words * (size_t)tcols * 4), o_slots = o_rmax + docs_align((size_t)words * (size_t)n * 4);
+    const size_t o_merged = o_slots + docs_align((size_t)n * (size_t)splits * k * 8), o_all = o_merged + docs_align((size_t)n * k * 8);
+    if (eval_reserve_topk(e, o_all + (all_scores ? docs_align((size_t)n * (size_t)n_docs * 4) : 0) + 256) != W2B_OK)
+      return efail(W2B_ENOMEM, who + ": device allocation failed");
+    char *tk = (char *)e->tk_buf;
+    unsigned long long *d_slots = (unsigned long long *)(tk + o_slots), *d_merged = (unsigned long long *)(tk + o_merged);
+    float *d_all = all_scores ? (float *)(tk + o_all) : nullptr;
+    if (tcols > 0) EHIP(hipMemcpyAsync(d_col, h_col.data(), (size_t)tcols * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d_qcol, h_qcol.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(d_qm, h_qm.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipEventRecord(ev.t[0], e->stream));
+    hipError_t le = w2b_launch_docs_table((const uint32_t *)e->B, (int)words, (int)e->size, bl, e->wrow, d_col, (int)tcols, d_qcol,
+                                          d_qm, (int)n, tk, tk + o_rmax, e->stream);
+    if (le == hipSuccess) le = hipEventRecord(ev.t[1], e->stream);
+    if (le == hipSuccess) le = hipEventRecord(ev2.t[0], e->stream);
+    if (le == hipSuccess)
+      le = w2b_launch_docs_walk(tk, tk + o_rmax, (int)tcols, (int)n, (int)e->size, bl, d_qcol, d_qm, e->docs_ids, e->docs_off, n_docs,
+                                symmetric, k, d_slots, d_merged, d_all, e->stream);
+    if (le == hipSuccess) le = hipEventRecord(ev2.t[1], e->stream);
+    keys.assign((size_t)(n * k), 0ull);
+    if (le == hipSuccess) le = hipMemcpyAsync(keys.data(), d_merged, (size_t)(n * k) * 8, hipMemcpyDeviceToHost, e->stream);
+    if (all_scores) {
+      h_all.resize((size_t)(n * n_docs));
+      if (le == hipSuccess) le = hipMemcpyAsync(h_all.data(), d_all, h_all.size() * 4, hipMemcpyDeviceToHost, e->stream);
+    }
+    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+    float ms = 0, ms2 = 0;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, ev.t[0], ev.t[1]);
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms2, ev2.t[0], ev2.t[1]);
+    if (le != hipSuccess) return efail(W2B_EHIP, who + ": " + hipGetErrorString(le));
+    e->docs_table_ms += ms;
+    e->docs_walk_ms += ms2;
+    e->kernel_ms += (double)ms + (double)ms2;
+    e->launches++;
+    e->macs += (double)positions * (double)e->docs_positions * (double)e->size;
+    for (int64_t i = 0; i < n * k; i++) {
+      const unsigned long long key = keys[(size_t)i];
+      best[q0 * k + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : -1;
+      if (bestd) bestd[q0 * k + i] = f32_score(key);
+    }
+    if (all_scores) std::copy(h_all.begin(), h_all.end(), all_scores + q0 * n_docs);
+    q0 += n;
+  }
+  return W2B_OK;
+}
+
+extern "C" int w2b_eval_docs_timing(w2b_eval *e, double *table_ms, double *walk_ms) {
+  if (!e) return efail(W2B_EINVAL, "w2b_eval_docs_timing: null handle");
+  if (table_ms) *table_ms = e->docs_table_ms;
+  if (walk_ms) *walk_ms = e->docs_walk_ms;
+  return W2B_OK;
+}
+
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                              int32_t *best, float *bestd) {
   return eval_scan(e, nq, b1, b2, b3, false, 0, best, bestd, "w2b_eval_top1");
@@ -1899,6 +2200,90 @@ extern "C" int w2b_eval_vectors_text(w2b_eval *e, const char *queries, int64_t l
     if (rc != W2B_OK) return rc;
   }
   return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_vectors_text", out, out_len);
+}
+
+// the corpus from text: one document per line, empty lines included; words that are not in the vocabulary are dropped
+extern "C" int w2b_eval_docs_set_text(w2b_eval *e, const char *text, int64_t len, int64_t *n_docs, int64_t *dropped) {
+  const std::string who = "w2b_eval_docs_set_text";
+  if (len < 0 || (len > 0 && !text)) return efail(W2B_EINVAL, who + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": " + kDocsFp32);
+  std::vector<int32_t> ids;
+  std::vector<int64_t> offsets(1, 0);
+  std::vector<std::string> tok;
+  int64_t lost = 0;
+  for (int64_t pos = 0; next_query_line(text, len, pos, tok);) {
+    for (const std::string &w : tok) {
+      const int64_t row = w2b_eval_lookup(e, w.c_str());
+      if (row == e->words) lost++;
+      else ids.push_back((int32_t)row);
+    }
+    if ((int64_t)ids.size() - offsets.back() > W2B_EVAL_MAX_DOC)
+      return efail(W2B_EINVAL, who + ": line " + std::to_string(offsets.size()) + ": a document holds at most 1024 words");
+    offsets.push_back((int64_t)ids.size());
+  }
+  if (int rc = w2b_eval_docs_set(e, (int64_t)ids.size(), ids.data(), (int64_t)offsets.size() - 1, offsets.data())) return rc;
+  if (n_docs) *n_docs = (int64_t)offsets.size() - 1;
+  if (dropped) *dropped = lost;
+  return W2B_OK;
+}
+
+// the document form: every non-empty line is one query text; an answer line names a document by its line number
+extern "C" int w2b_eval_docs_text(w2b_eval *e, const char *queries, int64_t len, int32_t symmetric, int32_t k, char **out,
+                                  int64_t *out_len) {
+  const std::string who = "w2b_eval_docs_text";
+  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
+  if (symmetric != 0 && symmetric != 1) return efail(W2B_EINVAL, who + ": symmetric must be 0 or 1");
+  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, who + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": " + kDocsFp32);
+  if (e->docs_n == 0) return efail(W2B_EINVAL, who + ": no corpus is set (w2b_eval_docs_set)");
+  *out = nullptr;
+  std::vector<QueryLine> lines;
+  std::vector<int32_t> ids;
+  std::vector<int64_t> offsets(1, 0);
+  std::vector<std::string> tok;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
+    if (tok.empty()) continue;
+    QueryLine ln{joined(tok), std::string(), -1};
+    const size_t at = ids.size();
+    for (const std::string &w : tok) {
+      const int64_t row = w2b_eval_lookup(e, w.c_str());
+      if (row != e->words) ids.push_back((int32_t)row);
+    }
+    if (ids.size() == at) ln.error = "no word in vocabulary";
+    else if (ids.size() - at > W2B_EVAL_MAX_DOC) ln.error = "expected at most 1024 words";
+    if (ln.error.empty()) {
+      ln.q = (int64_t)offsets.size() - 1;
+      offsets.push_back((int64_t)ids.size());
+    } else {
+      ids.resize(at);
+    }
+    lines.push_back(ln);
+  }
+  const size_t nq = offsets.size() - 1;
+  std::vector<int32_t> best(nq * (size_t)k);
+  std::vector<float> bestd(nq * (size_t)k);
+  if (nq > 0) {
+    const int rc = w2b_eval_docs(e, (int64_t)ids.size(), ids.data(), (int64_t)nq, offsets.data(), symmetric, k, best.data(),
+                                 bestd.data(), nullptr);
+    if (rc != W2B_OK) return rc;
+  }
+  std::string txt;
+  for (const QueryLine &ln : lines) {
+    txt += ln.head;
+    if (!ln.error.empty()) {
+      txt += ": " + ln.error + "\n";
+      continue;
+    }
+    txt += ":\n";
+    for (int j = 0; j < k; j++) {
+      const int32_t d = best[(size_t)(ln.q * k + j)];
+      if (d < 0) break;
+      appendf(txt, "%d\t%lld\t%.6f\n", j + 1, (long long)d + 1, (double)bestd[(size_t)(ln.q * k + j)]);
+    }
+  }
+  return text_out(txt, who.c_str(), out, out_len);
 }
 
 extern "C" void w2b_eval_free_text(char *text) { free(text); }

@@ -237,6 +237,18 @@ hipError_t w2b_launch_vec_scan(const uint64_t *B, int words, int dim, int bitlev
                                const void *X, const float *Wx, int nq, int k, unsigned long long *bound,
                                unsigned long long *bkt, unsigned long long *keys, unsigned char *cnt, unsigned long long *out,
                                hipStream_t s);
+// The document question on bit-packed rows (w2b_kernels_evaldocs.hip; include/word2bits_eval.h, "documents").  A chunk of nq
+// queries is tcols columns: query q owns columns qcol[q] .. qcol[q + 1) (a multiple of 16), the first qm[q] of them carry its
+// ids >= 0, colrow[x] = the row of column x or -1 for a pad column.  Table: Tab [words][tcols] (int32 I / float32 cos) and
+// Rmax [words][nq] (the largest value of a row over a query's own columns); every element is written.  Walk: ids / off = the
+// corpus WITHOUT its padding ids (off [n_docs + 1]); slots [nq][ceil(n_docs / W2B_DOCS_PER_BLOCK)][k] receives every
+// workgroup's k best keys, out[q * k + j] the j-th best key (score bits << 32 | ~document), all_scores (or null) [nq][n_docs].
+#define W2B_DOCS_PER_BLOCK 1024     // documents of one walk workgroup
+hipError_t w2b_launch_docs_table(const uint32_t *B, int words, int dim, int bitlevel, const float *wrow, const int *colrow,
+                                 int tcols, const int *qcol, const int *qm, int nq, void *Tab, void *Rmax, hipStream_t s);
+hipError_t w2b_launch_docs_walk(const void *Tab, const void *Rmax, int tcols, int nq, int dim, int bitlevel, const int *qcol,
+                                const int *qm, const int *ids, const long long *off, long long n_docs, int symmetric, int k,
+                                unsigned long long *slots, unsigned long long *out, float *all_scores, hipStream_t s);
 // the packed embedding layer (w2b_kernels_embed.hip; include/word2bits_embed.h).  T = the packed table [rows][wpr], ids /
 // offsets = int64 device buffers, `bad` = the device counter of ignored ids and clamped bags.  A bag launch needs
 // w2b_embed_bag_scratch(...) bytes of device scratch (it zeroes them itself).

@@ -10,9 +10,11 @@
     rows, scores = ev.vectors(hidden, 10)                            # float vectors [nq, size] of one's own: nearest to each
     rows, scores = ev.cosmul(b1, b2, b3, 10)                         # analogies by the multiplicative rule 3CosMul
     cls = ev.classes(500)                                            # word classes by k-means (word2vec's -classes)
+    ev.set_docs(ids, offsets); docs, scores = ev.docs(qids, qoffsets, 10)   # corpus texts nearest to query texts (RWMD)
 
 The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip,
-w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip, w2b_kernels_evalcosmul.hip, w2b_kernels_evalclasses.hip);
+w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip, w2b_kernels_evalcosmul.hip, w2b_kernels_evalclasses.hip,
+w2b_kernels_evaldocs.hip);
 there is no CPU path in this module.
 """
 import ctypes as C
@@ -246,6 +248,51 @@ class Evaluator:
         """(assign ms, sums ms): the device time of the last classes() call, split into its assign scans and its sums passes."""
         a, s = C.c_double(), C.c_double()
         _lib.check(self._L.w2b_eval_classes_timing(self._h, C.byref(a), C.byref(s)))
+        return a.value, s.value
+
+    def set_docs(self, ids, offsets):
+        """The corpus of the document question (w2b_eval_docs_set; bits and codes handles): document d is the rows
+        ids[offsets[d]:offsets[d + 1]], at most 1024 positions, an id < 0 is padding.  Replaces an earlier corpus; an empty
+        one (offsets == [0]) drops it."""
+        ids, offsets = np.ascontiguousarray(ids, np.int32).ravel(), np.ascontiguousarray(offsets, np.int64).ravel()
+        _lib.check(self._L.w2b_eval_docs_set(self._h, len(ids), ids.ctypes.data_as(_lib.i32p), max(len(offsets) - 1, 0),
+                                             offsets.ctypes.data_as(_lib.i64p)))
+
+    def set_docs_text(self, text):
+        """The corpus from text (bytes): one document per line, empty lines included; words not in the vocabulary are
+        dropped.  Returns (n_docs, dropped)."""
+        text = bytes(text)
+        n, dropped = C.c_int64(), C.c_int64()
+        _lib.check(self._L.w2b_eval_docs_set_text(self._h, text, len(text), C.byref(n), C.byref(dropped)))
+        return n.value, dropped.value
+
+    def docs_count(self):
+        return int(self._L.w2b_eval_docs_count(self._h))
+
+    def docs(self, ids, offsets, k, symmetric=True, all_scores=False):
+        """The document question (w2b_eval_docs): query q is the rows ids[offsets[q]:offsets[q + 1]]; the answer is the k
+        documents of the corpus nearest to it by relaxed word mover's similarity -- every word matched to its best word of
+        the other text, the matches averaged; symmetric=True takes the smaller of the two directions, False scores how well
+        the query's words are matched in the document alone.  Returns (documents int32 [nq, k], scores float32 [nq, k]) in
+        the order of topk, a short list ending in -1 / 0; with all_scores=True also every score, float32 [nq, n_docs]."""
+        ids, offsets = np.ascontiguousarray(ids, np.int32).ravel(), np.ascontiguousarray(offsets, np.int64).ravel()
+        nq, k = max(len(offsets) - 1, 0), int(k)
+        best, bestd = np.empty((nq, max(k, 0)), np.int32), np.empty((nq, max(k, 0)), np.float32)
+        every = np.empty((nq, self.docs_count()), np.float32) if all_scores else None
+        _lib.check(self._L.w2b_eval_docs(self._h, len(ids), ids.ctypes.data_as(_lib.i32p), nq, offsets.ctypes.data_as(_lib.i64p),
+                                         int(symmetric), k, best.ctypes.data_as(_lib.i32p), bestd.ctypes.data_as(_lib.f32p),
+                                         every.ctypes.data_as(_lib.f32p) if all_scores else None))
+        return (best, bestd, every) if all_scores else (best, bestd)
+
+    def docs_text(self, queries, k, symmetric=True):
+        """stdout of `nearest FILE k ... bits|codes docs CORPUS.txt < queries` as bytes: every line is one query text, an
+        answer line is "<rank>\t<line number of the document>\t<score>"."""
+        return self._text(self._L.w2b_eval_docs_text, queries, int(symmetric), int(k))
+
+    def docs_timing(self):
+        """(table ms, walk ms): the device time of the last docs() call, split into its pair-table phase and its walk."""
+        a, s = C.c_double(), C.c_double()
+        _lib.check(self._L.w2b_eval_docs_timing(self._h, C.byref(a), C.byref(s)))
         return a.value, s.value
 
     def nearest_text(self, queries, k):
