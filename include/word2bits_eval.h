@@ -505,6 +505,72 @@ int w2b_docs_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int
                          int64_t n_q, const int32_t *qids, int32_t symmetric,
                          int64_t *dir_out, float *score_out);
 
+/* ---- pair similarity: the cosine of two words or two bags, and its rank correlation with human scores --------------------
+ * "How similar are these two words, these two sentences?" -- the second intrinsic evaluation beside the analogies: a list of
+ * human-rated pairs (WordSim-353, SimLex, MEN, Rare Words; STS for sentences) is scored and the correlation between the model's
+ * cosines and the human scores is reported (gensim's evaluate_word_pairs; for bags n_similarity, the cosine of the two pooled
+ * vectors).  Every other question of this header is "one question against all rows, top-k"; this one scores GIVEN pairs.  A bits
+ * or a codes handle is required; an fp32 handle is W2B_EINVAL ("not available on an fp32 handle: load the file with bits or
+ * codes"), as for w2b_eval_cosmul.  A handle with size > 2^24 is W2B_EINVAL.  Handles made by *_from_trainer in bits / codes mode
+ * work like loaded ones.
+ *   pairs: one ids[n_ids] array and offsets[2 * np + 1], non-decreasing, offsets[0] == 0, offsets[2 * np] == n_ids: bag 2 p is
+ *     side A of pair p, bag 2 p + 1 side B.  An id < 0 is padding and contributes nothing; an id >= w2b_eval_words(e) is
+ *     W2B_EINVAL, naming the pair; a bag of more than W2B_EVAL_MAX_BAG ids, padding included, is W2B_EINVAL.  np == 0 is W2B_OK.
+ *   integers, exact: per side T[a] = sum over the bag's ids r >= 0 of t_r[a], t = +-1 on a bits handle, t in {+-1, +-3} on a codes
+ *     handle -- the pooling of w2b_eval_bag: the same row twice adds twice, |T[a]| <= 3 * 4096 -- and over the `size` columns
+ *         J = sum_a T_A[a] * T_B[a],     N_A = sum_a T_A[a]^2,     N_B = sum_a T_B[a]^2,
+ *     each an int64 below 12288^2 * 2^24 < 2^53: exact as integers and as doubles.  Integer adds commute, so no split of the work
+ *     changes them.  parts (or NULL) receives [np][3] = J, N_A, N_B.
+ *   score: built on the host from the three integers the device returns, as w2b_eval_bag builds wq:
+ *         score = (float)((double)J / sqrt((double)N_A * (double)N_B)),
+ *     the double multiply, the square root and the division each correctly rounded, the result rounded to float.  A pair with
+ *     N_A == 0 or N_B == 0 is EMPTY -- a bag with no id >= 0, or one whose T is zero in every column -- and scores +0.  Two
+ *     consequences: identical bags score exactly 1.0f (sqrt(fl(N * N)) == N), and on a bits handle a pair of one-word bags [r],
+ *     [c] has N_A = N_B = size and scores bit for bit the (float)J / (float)size that w2b_eval_neighbors and w2b_eval_bag give
+ *     row c for the question r (J and size are exact in float32, and a double quotient rounded to float is the correctly rounded
+ *     float quotient).
+ * Everything is validated before anything is launched -- what does not depend on the handle first (the arguments, the offsets,
+ * the bag lengths), then the handle, then the ids, as in w2b_eval_bag -- with the cause in w2b_last_error(); on error score and
+ * parts are untouched.
+ * How it runs (word2bits_amd/csrc/w2b_kernels_evalpairs.hip): lane = column, an id is wave-uniform, so a packed word is one
+ * broadcast load; one wavefront per pair, a workgroup per pair of more than 256 ids, one lane per one-word pair (popcounts on
+ * whole words).  Large calls run in chunks of whole pairs: w2b_eval_set_topk_scratch bounds the device staging of a launch
+ * (the ids, 4 bytes each, and 36 bytes per pair: two bounds, a path entry and the 24 bytes of parts); a chunk is never smaller
+ * than 64 pairs, however large they are; results never depend on the chunking.  w2b_eval_timing_read counts these launches (one
+ * per chunk), macs = n_ids x size, the pooling adds. */
+int w2b_eval_pairs(w2b_eval *e, int64_t n_ids, const int32_t *ids, int64_t np, const int64_t *offsets /* [2 * np + 1] */,
+                   float *score /* [np] */, int64_t *parts /* [np][3] = J, N_A, N_B, or NULL */);
+/* The text form of ./similarity: a list of rated pairs in, their scores and the two correlations out.  Lines are numbered from 1.
+ * A line that is empty (or white space only; a '\r' before the '\n' is dropped) or starts with '#' is no pair.  Every other line
+ * is one pair of exactly three fields A, B, gold: if the line contains a tab the fields are its tab-separated parts, each
+ * stripped of the blanks around it; otherwise they are its runs of non-blank characters.  A and B are 1 to W2B_EVAL_MAX_BAG words
+ * separated by blanks, upper-cased and looked up as w2b_eval_bag_text does; gold is parsed with strtod in the C locale, must be
+ * consumed completely and be finite.  Anything else makes the line MALFORMED.  A word that w2b_eval_lookup does not find is
+ * dropped from its bag and counted.  All well-formed lines go through one w2b_eval_pairs batch; a pair that comes back EMPTY
+ * (above: for example every word of a side unknown) is SKIPPED, the others are SCORED.
+ * With details != 0 one line per pair line, in input order:
+ *     "<score %.6f>\t<gold as written>\t<A as written>\t<B as written>\n"    or
+ *     "skipped\t<gold>\t<A>\t<B>\n"                                          or     "malformed line <n>\n"
+ * then always
+ *     "pairs: <scored> scored, <skipped> skipped, <malformed> malformed\n"
+ *     "words: <looked up> looked up, <oov> not in vocabulary\n"      (every word of a well-formed line is looked up)
+ *     "pearson: <%.6f or nan>\n"  "spearman: <%.6f or nan>\n"        (w2b_rank_correlation of gold and (double)score over the
+ *                                                                      scored pairs in input order)
+ * *out is malloc'ed; release it with w2b_eval_free_text. */
+int w2b_eval_pairs_text(w2b_eval *e, const char *pairs, int64_t len, int32_t details, char **out, int64_t *out_len);
+/* Host twin of the pair kernels (pure C, no device): the pairs above on packed[words][bitlevel * ceil(dim / 64)], bitlevel 1 (bits)
+ * or 2 (codes), T from the unpacked rows.  score and parts may each be NULL.  W2B_EINVAL as w2b_eval_pairs has it for the
+ * arguments, the offsets, the bag lengths and the ids, and for a bitlevel other than 1 or 2 and dim > 2^24; on error nothing is
+ * written. */
+int w2b_pairs_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n_ids, const int32_t *ids,
+                   int64_t np, const int64_t *offsets, float *score, int64_t *parts);
+/* Pearson's r and Spearman's rho of x[n], y[n], in double on the host (no device):
+ *     r = sum (x - mx)(y - my) / sqrt(sum (x - mx)^2 * sum (y - my)^2),   mx, my the means;
+ *     rho = the same r on the 1-based ranks, equal values sharing the mean of their ranks (scipy's spearmanr).
+ * A value is NaN with n < 2, with a zero variance, or when an input is NaN.  Either output may be NULL.  W2B_EINVAL: n < 0, a
+ * NULL input with n > 0. */
+int w2b_rank_correlation(int64_t n, const double *x, const double *y, double *pearson, double *spearman);
+
 #ifdef __cplusplus
 }
 #endif

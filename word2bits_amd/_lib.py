@@ -184,6 +184,10 @@ SIGNATURES = {
     "w2b_eval_docs_timing": (C.c_int, [vp, f64p, f64p]),
     "w2b_docs_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int64, i64p, C.c_int64, i32p,
                                        C.c_int32, i64p, f32p]),
+    "w2b_eval_pairs": (C.c_int, [vp, C.c_int64, i32p, C.c_int64, i64p, f32p, i64p]),
+    "w2b_eval_pairs_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp), i64p]),
+    "w2b_pairs_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int64, i64p, f32p, i64p]),
+    "w2b_rank_correlation": (C.c_int, [C.c_int64, f64p, f64p, f64p, f64p]),
     # include/word2bits_embed.h
     "w2b_embed_load": (C.c_int, [C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp)]),
     "w2b_embed_create": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(vp)]),

@@ -4,10 +4,10 @@
 // w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
 // adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms, w2b_kernels_evalvec.hip
 // the float-vector question on them, w2b_kernels_evalcosmul.hip the 3CosMul scan on 1-bit rows, w2b_kernels_evalclasses.hip the
-// k-means word classes on both packed forms (whose wq = 1 / sqrt(N_k) the host builds like the bag question's), w2b_kernels_evaldocs.hip the document question on them.  No arithmetic on scores happens here (the exceptions are question weights: the bag
+// k-means word classes on both packed forms (whose wq = 1 / sqrt(N_k) the host builds like the bag question's), w2b_kernels_evaldocs.hip the document question on them, w2b_kernels_evalpairs.hip the pair question (whose cosine the host builds from the three integers the device sums, and whose rank correlations are host arithmetic in double).  No arithmetic on scores happens here (the exceptions are question weights: the bag
 // question's 1 / sqrt(N_T), built from the integer the device sums, and the vector question's wx with the fp32 handle's
 // vec = x * wx; and the 3CosMul table u = A / size of a bits handle) and there is no CPU fallback (w2b_codes_scores_host,
-// w2b_bag_scores_host, w2b_vector_scores_host, w2b_cosmul_scores_host, w2b_classes_host and w2b_docs_scores_host are the tests' twins of the kernels).
+// w2b_bag_scores_host, w2b_vector_scores_host, w2b_cosmul_scores_host, w2b_classes_host, w2b_docs_scores_host and w2b_pairs_host are the tests' twins of the kernels).
 #include "../../include/word2bits_eval.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
@@ -914,6 +914,129 @@ extern "C" int w2b_docs_scores_host(const uint64_t *packed, int64_t words, int64
   return W2B_OK;
 }
 
+namespace {
+constexpr int64_t kPairsMaxSize = 1ll << 24;     // 12288^2 * size < 2^53: J, N_A, N_B are exact as doubles
+
+// what w2b_eval_pairs and its host twin refuse before they look at a handle or a table (empty: nothing)
+std::string bad_pairs(int64_t n_ids, const int32_t *ids, int64_t np, const int64_t *offsets, const float *score,
+                      const int64_t *parts) {
+  if (np < 0 || n_ids < 0 || (np > 0 && (!offsets || (!score && !parts))) || (n_ids > 0 && !ids)) return "bad argument";
+  if (np > (INT64_MAX >> 2)) return "bad argument";
+  if (np == 0 ? n_ids != 0 : (offsets[0] != 0 || offsets[2 * np] != n_ids)) return "offsets must start at 0 and end at n_ids";
+  for (int64_t b = 0; b < 2 * np; b++) {
+    if (offsets[b + 1] < offsets[b] || offsets[b + 1] > n_ids) return "offsets must not decrease";
+    if (offsets[b + 1] - offsets[b] > W2B_EVAL_MAX_BAG) return "a bag holds at most 4096 ids";
+  }
+  return std::string();
+}
+// the first pair with an id >= words (-1: none)
+int64_t bad_pair_id(const int32_t *ids, int64_t np, const int64_t *offsets, int64_t words) {
+  for (int64_t p = 0; p < np; p++)
+    for (int64_t i = offsets[2 * p]; i < offsets[2 * p + 2]; i++)
+      if (ids[i] >= words) return p;
+  return -1;
+}
+
+// the score of the header from the three integers; an empty pair scores +0
+inline float pair_score(int64_t j, int64_t na, int64_t nb) {
+#pragma clang fp contract(off)
+  if (na == 0 || nb == 0) return 0.f;
+  const double nn = (double)na * (double)nb;
+  const double root = sqrt(nn);
+  return (float)((double)j / root);
+}
+}  // namespace
+
+// Host twin of the pair kernels: both pooled vectors from the unpacked rows, the three sums in 64-bit integers, the double
+// steps of the header one at a time (this file is built with -ffp-contract=off, and pair_score says so again).
+extern "C" int w2b_pairs_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n_ids,
+                              const int32_t *ids, int64_t np, const int64_t *offsets, float *score, int64_t *parts) {
+  const std::string who = "w2b_pairs_host";
+  const std::string why = bad_pairs(n_ids, ids, np, offsets, score, parts);
+  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
+  if (!packed || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (dim > kPairsMaxSize) return efail(W2B_EINVAL, who + ": size must be at most 2^24");
+  const int64_t bad = bad_pair_id(ids, np, offsets, words);
+  if (bad >= 0) return efail(W2B_EINVAL, who + ": pair " + std::to_string(bad) + ": id out of range");
+  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
+  auto t_of = [&](const uint64_t *r, int64_t a) -> int32_t {
+    const uint64_t bit = 1ull << (a & 63);
+    if (bitlevel == 1) return (r[a >> 6] & bit) ? -1 : 1;
+    return ((r[2 * (a >> 6) + 1] & bit) ? 3 : 1) * ((r[2 * (a >> 6)] & bit) ? -1 : 1);
+  };
+  std::vector<int32_t> T[2] = {std::vector<int32_t>((size_t)dim), std::vector<int32_t>((size_t)dim)};
+  for (int64_t p = 0; p < np; p++) {
+    for (int side = 0; side < 2; side++) {
+      std::fill(T[side].begin(), T[side].end(), 0);
+      for (int64_t i = offsets[2 * p + side]; i < offsets[2 * p + side + 1]; i++)
+        if (ids[i] >= 0)
+          for (int64_t a = 0; a < dim; a++) T[side][(size_t)a] += t_of(packed + (int64_t)ids[i] * wpr, a);
+    }
+    int64_t j = 0, na = 0, nbb = 0;
+    for (int64_t a = 0; a < dim; a++) {
+      const int64_t x = T[0][(size_t)a], y = T[1][(size_t)a];
+      j += x * y;
+      na += x * x;
+      nbb += y * y;
+    }
+    if (score) score[p] = pair_score(j, na, nbb);
+    if (parts) parts[3 * p] = j, parts[3 * p + 1] = na, parts[3 * p + 2] = nbb;
+  }
+  return W2B_OK;
+}
+
+namespace {
+// Pearson's r of the header; NaN with n < 2 or a zero variance
+double pearson_r(const std::vector<double> &x, const std::vector<double> &y) {
+#pragma clang fp contract(off)
+  const size_t n = x.size();
+  if (n < 2) return NAN;
+  if (*std::min_element(x.begin(), x.end()) == *std::max_element(x.begin(), x.end()) ||
+      *std::min_element(y.begin(), y.end()) == *std::max_element(y.begin(), y.end()))
+    return NAN;                                    // (a constant: its deviations from a rounded mean need not be zero)
+  double mx = 0, my = 0;
+  for (size_t i = 0; i < n; i++) mx += x[i], my += y[i];
+  mx /= (double)n;
+  my /= (double)n;
+  double sxy = 0, sxx = 0, syy = 0;
+  for (size_t i = 0; i < n; i++) {
+    const double dx = x[i] - mx, dy = y[i] - my;
+    sxy += dx * dy;
+    sxx += dx * dx;
+    syy += dy * dy;
+  }
+  if (!(sxx > 0) || !(syy > 0)) return NAN;
+  return sxy / sqrt(sxx * syy);
+}
+// 1-based ranks, equal values sharing the mean of their ranks
+std::vector<double> mean_ranks(const std::vector<double> &v) {
+  const size_t n = v.size();
+  std::vector<size_t> idx(n);
+  for (size_t i = 0; i < n; i++) idx[i] = i;
+  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return v[a] < v[b]; });
+  std::vector<double> r(n);
+  for (size_t i = 0; i < n;) {
+    size_t k = i;
+    while (k < n && v[idx[k]] == v[idx[i]]) k++;
+    const double mean = 0.5 * (double)(i + 1 + k);           // ranks i + 1 .. k
+    for (size_t t = i; t < k; t++) r[idx[t]] = mean;
+    i = k;
+  }
+  return r;
+}
+}  // namespace
+
+extern "C" int w2b_rank_correlation(int64_t n, const double *x, const double *y, double *pearson, double *spearman) {
+  if (n < 0 || (n > 0 && (!x || !y))) return efail(W2B_EINVAL, "w2b_rank_correlation: bad argument");
+  const std::vector<double> xv(x, x + n), yv(y, y + n);
+  bool nan = false;
+  for (int64_t i = 0; i < n; i++) nan |= std::isnan(xv[(size_t)i]) || std::isnan(yv[(size_t)i]);
+  if (pearson) *pearson = nan ? NAN : pearson_r(xv, yv);
+  if (spearman) *spearman = nan ? NAN : pearson_r(mean_ranks(xv), mean_ranks(yv));
+  return W2B_OK;
+}
+
 extern "C" void w2b_eval_free(w2b_eval *e) { eval_release(e); }
 extern "C" int64_t w2b_eval_words(const w2b_eval *e) { return e ? e->words : 0; }
 extern "C" int64_t w2b_eval_size(const w2b_eval *e) { return e ? e->size : 0; }
@@ -1765,6 +1888,87 @@ extern "C" int w2b_eval_docs_timing(w2b_eval *e, double *table_ms, double *walk_
   return W2B_OK;
 }
 
+// ------------------------------------------------------------------------------------ pair similarity
+namespace {
+constexpr int64_t kPairsChunk = 1 << 20;         // pairs per launch at most
+constexpr int64_t kPairsChunkIds = 1ll << 30;    // ids per launch at most: the chunk's bounds are 32-bit
+constexpr int64_t kPairsMinChunk = 64;           // pairs that a launch takes whatever the budget is
+constexpr int64_t kPairsPerPair = 36;            // staging bytes of a pair beside its ids: two bounds, a path entry, the parts
+}  // namespace
+
+// The pair question: every check first -- what needs no handle, then the handle, then the ids -- then chunks of whole pairs.
+// A chunk's staging is one device buffer: parts [n][3] (64-bit), bounds [2 n + 1], the pairs sorted by path [n], the ids.  The
+// integers of all chunks are collected first and the outputs written at the end: an error in a later chunk leaves them untouched.
+extern "C" int w2b_eval_pairs(w2b_eval *e, int64_t n_ids, const int32_t *ids, int64_t np, const int64_t *offsets, float *score,
+                              int64_t *parts) {
+  const std::string who = "w2b_eval_pairs";
+  const std::string why = bad_pairs(n_ids, ids, np, offsets, score, parts);
+  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
+  if (np > 0 && !score) return efail(W2B_EINVAL, who + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": not available on an fp32 handle: load the file with bits or codes");
+  if (e->size > kPairsMaxSize) return efail(W2B_EINVAL, who + ": size must be at most 2^24");
+  const int64_t bad = bad_pair_id(ids, np, offsets, e->words);
+  if (bad >= 0) return efail(W2B_EINVAL, who + ": pair " + std::to_string(bad) + ": id out of range");
+  if (np == 0) return W2B_OK;
+  EHIP(hipSetDevice(e->device));
+  const int bl = e->codes ? 2 : 1;
+  const int64_t budget = e->tk_budget > 0 ? e->tk_budget : kTopkScratch;
+  std::vector<int64_t> all((size_t)np * 3, 0);
+  std::vector<int32_t> h_off, h_list[3], h_sorted;
+  EventPair ev;
+  EHIP(ev.create());
+  for (int64_t p0 = 0; p0 < np;) {
+    const int64_t i0 = offsets[2 * p0];
+    int64_t n = 0, used = 0;
+    while (p0 + n < np && n < kPairsChunk) {
+      const int64_t m1 = offsets[2 * (p0 + n) + 2] - offsets[2 * (p0 + n)], need = kPairsPerPair + 4 * m1;
+      if (n >= kPairsMinChunk && used + need > budget) break;
+      if (n > 0 && offsets[2 * (p0 + n) + 2] - i0 > kPairsChunkIds) break;
+      used += need;
+      n++;
+    }
+    const int64_t m = offsets[2 * (p0 + n)] - i0;
+    if (e->words > 0) {                            // (no rows: every id is padding and every pair is empty)
+      h_off.resize((size_t)(2 * n + 1));
+      for (int64_t b = 0; b <= 2 * n; b++) h_off[(size_t)b] = (int32_t)(offsets[2 * p0 + b] - i0);
+      for (auto &l : h_list) l.clear();
+      for (int64_t q = 0; q < n; q++)
+        h_list[w2b_pairs_path(bl, ids + i0, h_off[(size_t)(2 * q)], h_off[(size_t)(2 * q + 1)], h_off[(size_t)(2 * q + 2)])]
+            .push_back((int32_t)q);
+      h_sorted.clear();
+      for (const auto &l : h_list) h_sorted.insert(h_sorted.end(), l.begin(), l.end());
+      const size_t o_off = (size_t)n * 24, o_list = o_off + (size_t)(2 * n + 1) * 4, o_ids = o_list + (size_t)n * 4;
+      if (eval_reserve_bag(&e->bag_buf, &e->bag_bytes, o_ids + (size_t)m * 4 + 4) != W2B_OK)
+        return efail(W2B_ENOMEM, who + ": device allocation failed");
+      char *buf = (char *)e->bag_buf;
+      long long *d_parts = (long long *)buf;
+      int32_t *d_off = (int32_t *)(buf + o_off), *d_list = (int32_t *)(buf + o_list), *d_ids = (int32_t *)(buf + o_ids);
+      EHIP(hipMemcpyAsync(d_off, h_off.data(), h_off.size() * 4, hipMemcpyHostToDevice, e->stream));
+      EHIP(hipMemcpyAsync(d_list, h_sorted.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+      if (m > 0) EHIP(hipMemcpyAsync(d_ids, ids + i0, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+      EHIP(hipEventRecord(ev.t[0], e->stream));
+      hipError_t le = w2b_launch_pairs(e->B, (int)e->size, bl, d_ids, d_off, d_list, (int)h_list[W2B_PAIRS_PATH_ONE].size(),
+                                       (int)h_list[W2B_PAIRS_PATH_SHORT].size(), (int)h_list[W2B_PAIRS_PATH_LONG].size(), d_parts,
+                                       e->stream);
+      if (le == hipSuccess) le = hipEventRecord(ev.t[1], e->stream);
+      if (le == hipSuccess)
+        le = hipMemcpyAsync(all.data() + 3 * p0, d_parts, (size_t)n * 24, hipMemcpyDeviceToHost, e->stream);
+      if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+      float ms = 0;
+      if (le == hipSuccess) le = hipEventElapsedTime(&ms, ev.t[0], ev.t[1]);
+      if (le != hipSuccess) return efail(W2B_EHIP, who + ": " + hipGetErrorString(le));
+      e->kernel_ms += ms;
+    }
+    e->launches++;
+    e->macs += (double)m * (double)e->size;
+    p0 += n;
+  }
+  for (int64_t p = 0; p < np; p++) score[p] = pair_score(all[(size_t)(3 * p)], all[(size_t)(3 * p + 1)], all[(size_t)(3 * p + 2)]);
+  if (parts) memcpy(parts, all.data(), all.size() * 8);
+  return W2B_OK;
+}
+
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
                              int32_t *best, float *bestd) {
   return eval_scan(e, nq, b1, b2, b3, false, 0, best, bestd, "w2b_eval_top1");
@@ -2282,6 +2486,143 @@ extern "C" int w2b_eval_docs_text(w2b_eval *e, const char *queries, int64_t len,
       if (d < 0) break;
       appendf(txt, "%d\t%lld\t%.6f\n", j + 1, (long long)d + 1, (double)bestd[(size_t)(ln.q * k + j)]);
     }
+  }
+  return text_out(txt, who.c_str(), out, out_len);
+}
+
+namespace {
+// one pair line of w2b_eval_pairs_text: its fields as written, or its number when it is malformed
+struct PairLine {
+  bool malformed;
+  int64_t number, p;
+  std::string gold_text, a_text, b_text;
+  double gold;
+};
+
+// the blank-separated words of s, upper-cased
+std::vector<std::string> upper_words(const std::string &s) {
+  std::vector<std::string> tok;
+  for (size_t i = 0; i < s.size();) {
+    while (i < s.size() && is_space((unsigned char)s[i])) i++;
+    const size_t s0 = i;
+    while (i < s.size() && !is_space((unsigned char)s[i])) i++;
+    if (i > s0) {
+      tok.emplace_back(s, s0, i - s0);
+      upper_inplace(tok.back());
+    }
+  }
+  return tok;
+}
+
+std::string stripped(const std::string &s) {
+  size_t a = 0, b = s.size();
+  while (a < b && is_space((unsigned char)s[a])) a++;
+  while (b > a && is_space((unsigned char)s[b - 1])) b--;
+  return s.substr(a, b - a);
+}
+
+// the three fields of a pair line: the tab-separated parts when there is a tab, else the runs of non-blank characters
+std::vector<std::string> pair_fields(const std::string &line) {
+  std::vector<std::string> f;
+  if (line.find('\t') != std::string::npos) {
+    for (size_t i = 0;;) {
+      const size_t t = line.find('\t', i);
+      f.push_back(stripped(line.substr(i, t == std::string::npos ? t : t - i)));
+      if (t == std::string::npos) break;
+      i = t + 1;
+    }
+    return f;
+  }
+  for (size_t i = 0; i < line.size();) {
+    while (i < line.size() && is_space((unsigned char)line[i])) i++;
+    const size_t s0 = i;
+    while (i < line.size() && !is_space((unsigned char)line[i])) i++;
+    if (i > s0) f.emplace_back(line, s0, i - s0);
+  }
+  return f;
+}
+}  // namespace
+
+// the pair form: every pair line is A, B and a gold score; one batch, then the correlations of the scored pairs
+extern "C" int w2b_eval_pairs_text(w2b_eval *e, const char *pairs, int64_t len, int32_t details, char **out, int64_t *out_len) {
+  const std::string who = "w2b_eval_pairs_text";
+  if (!out || len < 0 || (len > 0 && !pairs)) return efail(W2B_EINVAL, who + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": not available on an fp32 handle: load the file with bits or codes");
+  *out = nullptr;
+  static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+  if (!c_locale) return efail(W2B_ENOMEM, who + ": no C locale");
+  std::vector<PairLine> lines;
+  std::vector<int32_t> ids;
+  std::vector<int64_t> offsets(1, 0);
+  int64_t looked = 0, oov = 0, malformed = 0, number = 0;
+  for (int64_t pos = 0; pos < len;) {
+    int64_t end = pos;
+    while (end < len && pairs[end] != '\n') end++;
+    std::string line(pairs + pos, (size_t)(end - pos));
+    pos = end + 1;
+    number++;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (stripped(line).empty() || line[0] == '#') continue;
+    PairLine ln{true, number, -1, std::string(), std::string(), std::string(), 0.0};
+    const std::vector<std::string> f = pair_fields(line);
+    std::vector<std::string> wa, wb;
+    if (f.size() == 3 && !f[2].empty()) {
+      char *stop = nullptr;
+      ln.gold = strtod_l(f[2].c_str(), &stop, c_locale);
+      wa = upper_words(f[0]);
+      wb = upper_words(f[1]);
+      ln.malformed = stop != f[2].c_str() + f[2].size() || !std::isfinite(ln.gold) || wa.empty() || wb.empty() ||
+                     wa.size() > W2B_EVAL_MAX_BAG || wb.size() > W2B_EVAL_MAX_BAG;
+    }
+    if (ln.malformed) {
+      malformed++;
+    } else {
+      ln.a_text = f[0], ln.b_text = f[1], ln.gold_text = f[2];
+      ln.p = (int64_t)(offsets.size() - 1) / 2;
+      for (const std::vector<std::string> *side : {&wa, &wb}) {
+        for (const std::string &w : *side) {
+          const int64_t row = w2b_eval_lookup(e, w.c_str());
+          looked++;
+          if (row == e->words) oov++;
+          else ids.push_back((int32_t)row);
+        }
+        offsets.push_back((int64_t)ids.size());
+      }
+    }
+    lines.push_back(ln);
+  }
+  const int64_t np = (int64_t)(offsets.size() - 1) / 2;
+  std::vector<float> score((size_t)np);
+  std::vector<int64_t> parts((size_t)np * 3);
+  if (np > 0)
+    if (int rc = w2b_eval_pairs(e, (int64_t)ids.size(), ids.data(), np, offsets.data(), score.data(), parts.data())) return rc;
+  std::string txt;
+  std::vector<double> x, y;
+  int64_t skipped = 0;
+  for (const PairLine &ln : lines) {
+    if (ln.malformed) {
+      if (details) txt += "malformed line " + std::to_string(ln.number) + "\n";
+      continue;
+    }
+    const bool empty = parts[(size_t)(3 * ln.p + 1)] == 0 || parts[(size_t)(3 * ln.p + 2)] == 0;
+    if (empty) {
+      skipped++;
+      if (details) txt += "skipped";
+    } else {
+      x.push_back(ln.gold);
+      y.push_back((double)score[(size_t)ln.p]);
+      if (details) appendf(txt, "%.6f", (double)score[(size_t)ln.p]);
+    }
+    if (details) txt += "\t" + ln.gold_text + "\t" + ln.a_text + "\t" + ln.b_text + "\n";
+  }
+  double pearson = NAN, spearman = NAN;
+  if (int rc = w2b_rank_correlation((int64_t)x.size(), x.data(), y.data(), &pearson, &spearman)) return rc;
+  appendf(txt, "pairs: %lld scored, %lld skipped, %lld malformed\n", (long long)x.size(), (long long)skipped, (long long)malformed);
+  appendf(txt, "words: %lld looked up, %lld not in vocabulary\n", (long long)looked, (long long)oov);
+  for (const auto &c : {std::make_pair("pearson", pearson), std::make_pair("spearman", spearman)}) {
+    if (std::isnan(c.second)) txt += std::string(c.first) + ": nan\n";
+    else appendf(txt, "%s: %.6f\n", c.first, c.second);
   }
   return text_out(txt, who.c_str(), out, out_len);
 }

@@ -249,6 +249,18 @@ hipError_t w2b_launch_docs_table(const uint32_t *B, int words, int dim, int bitl
 hipError_t w2b_launch_docs_walk(const void *Tab, const void *Rmax, int tcols, int nq, int dim, int bitlevel, const int *qcol,
                                 const int *qm, const int *ids, const long long *off, long long n_docs, int symmetric, int k,
                                 unsigned long long *slots, unsigned long long *out, float *all_scores, hipStream_t s);
+// The pair question on bit-packed rows (w2b_kernels_evalpairs.hip; include/word2bits_eval.h, "pair similarity").  B = the
+// packed rows as 64-bit words, [words][bitlevel * ceil(dim / 64)]; ids / off = a chunk of pairs, off [2 n + 1] rebased to ids[0]:
+// bag 2 q is side A of pair q, bag 2 q + 1 side B; every id is < words (ids < 0 are padding), and words > 0.  list = the chunk's
+// pairs sorted by path, n_one + n_short + n_long = n of them, the path of a pair being w2b_pairs_path of its bounds (ids = the
+// chunk's ids, host memory).  parts [n][3] receives J, N_A, N_B of every pair; every element is written.
+#define W2B_PAIRS_LONG_IDS 256      // a pair of more ids than this, padding included, gets a workgroup of its own
+#define W2B_PAIRS_PATH_ONE 0
+#define W2B_PAIRS_PATH_SHORT 1
+#define W2B_PAIRS_PATH_LONG 2
+int w2b_pairs_path(int bitlevel, const int *ids, long long a0, long long a1, long long b1);
+hipError_t w2b_launch_pairs(const uint64_t *B, int dim, int bitlevel, const int *ids, const int *off, const int *list,
+                            int n_one, int n_short, int n_long, long long *parts, hipStream_t s);
 // the packed embedding layer (w2b_kernels_embed.hip; include/word2bits_embed.h).  T = the packed table [rows][wpr], ids /
 // offsets = int64 device buffers, `bad` = the device counter of ignored ids and clamped bags.  A bag launch needs
 // w2b_embed_bag_scratch(...) bytes of device scratch (it zeroes them itself).

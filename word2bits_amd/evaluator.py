@@ -11,10 +11,12 @@
     rows, scores = ev.cosmul(b1, b2, b3, 10)                         # analogies by the multiplicative rule 3CosMul
     cls = ev.classes(500)                                            # word classes by k-means (word2vec's -classes)
     ev.set_docs(ids, offsets); docs, scores = ev.docs(qids, qoffsets, 10)   # corpus texts nearest to query texts (RWMD)
+    cos = ev.pairs([3, 17, 4, 9, 9], [0, 1, 2, 3, 5])                # given pairs of words / bags: (3, 17) and ([4], [9, 9])
+    r, rho = rank_correlation(gold, cos)                             # ... and their correlation with human scores
 
 The exhaustive scan runs on the MI355X (w2b_kernels_eval.hip, w2b_kernels_evalbits.hip, w2b_kernels_evalcodes.hip,
 w2b_kernels_evalbag.hip, w2b_kernels_evalvec.hip, w2b_kernels_evalcosmul.hip, w2b_kernels_evalclasses.hip,
-w2b_kernels_evaldocs.hip);
+w2b_kernels_evaldocs.hip, w2b_kernels_evalpairs.hip);
 there is no CPU path in this module.
 """
 import ctypes as C
@@ -295,6 +297,30 @@ class Evaluator:
         _lib.check(self._L.w2b_eval_docs_timing(self._h, C.byref(a), C.byref(s)))
         return a.value, s.value
 
+    def pairs(self, ids, offsets, parts=False):
+        """Pair similarity (w2b_eval_pairs; bits and codes handles): `offsets` has 2 * np + 1 entries, bag 2p of `ids` is side A
+        of pair p and bag 2p + 1 side B; an id < 0 is padding, a repeated row adds.  Returns the cosines of the pooled integer
+        vectors, float32 [np] (+0 for a pair with an empty side); with parts=True also int64 [np, 3] = J, N_A, N_B, the exact
+        integers the score is built from."""
+        ids, offsets = np.ascontiguousarray(ids, np.int32).ravel(), np.ascontiguousarray(offsets, np.int64).ravel()
+        if len(offsets) % 2 != 1:
+            raise ValueError("offsets must hold 2 * np + 1 entries")
+        n = len(offsets) // 2
+        score, triple = np.empty(n, np.float32), np.empty((n, 3), np.int64)
+        _lib.check(self._L.w2b_eval_pairs(self._h, len(ids), ids.ctypes.data_as(_lib.i32p), n, offsets.ctypes.data_as(_lib.i64p),
+                                          score.ctypes.data_as(_lib.f32p), triple.ctypes.data_as(_lib.i64p)))
+        return (score, triple) if parts else score
+
+    def similarity(self, a, b):
+        """The cosine of two words or two bags (gensim's similarity / n_similarity): `a` and `b` are a row or a list of rows."""
+        a, b = np.atleast_1d(np.asarray(a, np.int32)).ravel(), np.atleast_1d(np.asarray(b, np.int32)).ravel()
+        return float(self.pairs(np.concatenate([a, b]), [0, len(a), len(a) + len(b)])[0])
+
+    def pairs_text(self, text, details=True):
+        """stdout of `similarity FILE ... bits|codes [summary] < text` as bytes: every line is "A <tab> B <tab> gold"; one line
+        per pair (details=True), then the counts and Pearson's and Spearman's correlation with the gold column."""
+        return self._text(self._L.w2b_eval_pairs_text, text, int(bool(details)))
+
     def nearest_text(self, queries, k):
         """stdout of `nearest FILE k < queries` as bytes: one word per line = its neighbours, three = an analogy."""
         return self._text(self._L.w2b_eval_nearest_text, queries, int(k))
@@ -319,6 +345,18 @@ class Evaluator:
         ms, n, macs = C.c_double(), C.c_int64(), C.c_double()
         _lib.check(self._L.w2b_eval_timing_read(self._h, C.byref(ms), C.byref(n), C.byref(macs)))
         return ms.value, n.value, macs.value
+
+
+def rank_correlation(x, y):
+    """(Pearson's r, Spearman's rho) of two equally long sequences (w2b_rank_correlation: double arithmetic on the host, ties
+    share the mean of their ranks as in scipy's spearmanr); NaN with fewer than 2 values or a zero variance."""
+    x, y = np.ascontiguousarray(x, np.float64).ravel(), np.ascontiguousarray(y, np.float64).ravel()
+    if len(x) != len(y):
+        raise ValueError("x and y must have the same length")
+    r, rho = C.c_double(), C.c_double()
+    _lib.check(_lib.lib().w2b_rank_correlation(len(x), x.ctypes.data_as(_lib.f64p), y.ctypes.data_as(_lib.f64p), C.byref(r),
+                                               C.byref(rho)))
+    return r.value, rho.value
 
 
 def compute_accuracy(path, questions, bitlevel=0, threshold=0, fused=True, device=0):
