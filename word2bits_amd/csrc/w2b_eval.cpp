@@ -1,29 +1,30 @@
-// w2b_eval.cpp -- host side of include/word2bits_eval.h: the vector-file reader, the question-stream state
-// machine and the stdout transcript of the reference evaluator (ref src/compute-accuracy.c:80-188), around the
-// GPU scans in w2b_kernels_eval.hip (fp32 rows), w2b_kernels_evalbits.hip (bit-packed 1-bit rows) and
-// w2b_kernels_evalcodes.hip (bit-packed 2-bit rows); w2b_kernels_evalcombine.hip has what the signed multi-word question
-// adds to the first two, w2b_kernels_evalbag.hip the bag question on both packed forms, w2b_kernels_evalvec.hip
-// the float-vector question on them, w2b_kernels_evalcosmul.hip the 3CosMul scan on 1-bit rows, w2b_kernels_evalclasses.hip the
-// k-means word classes on both packed forms (whose wq = 1 / sqrt(N_k) the host builds like the bag question's), w2b_kernels_evaldocs.hip the document question on them, w2b_kernels_evalpairs.hip the pair question (whose cosine the host builds from the three integers the device sums, and whose rank correlations are host arithmetic in double).  No arithmetic on scores happens here (the exceptions are question weights: the bag
-// question's 1 / sqrt(N_T), built from the integer the device sums, and the vector question's wx with the fp32 handle's
-// vec = x * wx; and the 3CosMul table u = A / size of a bits handle) and there is no CPU fallback (w2b_codes_scores_host,
-// w2b_bag_scores_host, w2b_vector_scores_host, w2b_cosmul_scores_host, w2b_classes_host, w2b_docs_scores_host and w2b_pairs_host are the tests' twins of the kernels).
-#include "../../include/word2bits_eval.h"
-#include "../../include/word2bits_hip.h"
+// w2b_eval.cpp -- the device side of include/word2bits_eval.h: the one host unit of the evaluator that sees `struct
+// w2b_eval` and makes HIP calls.
+//   the handle      struct w2b_eval and eval_release; the accessors (w2b_eval_words, _size, _word, _lookup, _is_bits,
+//                   _is_codes, _docs_count) that the text forms read it through
+//   the loaders     the vector-file reader of the reference evaluator (ref src/compute-accuracy.c:80-112), bit-packed
+//                   files, the views of a live trainer; w2b_eval_get_matrix / _bits / _codes
+//   the scan        every list question goes through eval_scan_chunks: an input struct (Rows3, Terms, Bags, Vectors) puts
+//                   a chunk of questions on the device, a Scan* struct sizes the chunk and launches one form of the scan
+//                   (fp32 rows: w2b_kernels_eval.hip; 1-bit rows: _evalbits; 2-bit rows: _evalcodes; and _evalcombine,
+//                   _evalbag, _evalvec, _evalcosmul for the questions of those names)
+//   the drivers     documents (_evaldocs), pairs (_evalpairs) and word classes (_evalclasses), which chunk by themselves
+//   the setters     the scratch bound, the kernel variant, the timing read-outs
+// No arithmetic on scores happens here.  What the host does compute are question weights and tables, by the expressions
+// of w2b_eval_shared.h that the host twins use too: the bag question's and the classes' 1 / sqrt(N), the vector question's
+// wx (and the fp32 handle's vec = x * wx), the 3CosMul table u = A / size of a bits handle, w(r) by n3 of a codes handle,
+// and the pair question's cosine from the three integers the device sums.  There is no CPU fallback: the host twins of the
+// kernels (w2b_eval_twins.cpp) are the tests' yardstick, and the text forms (w2b_eval_text.cpp) call the entry points of
+// this file like any other user of the header.
+#include "w2b_eval_shared.h"
 #include "w2b_internal.h"
 #include "w2b_evalclasses.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <locale.h>
 #include <memory>
-#include <string>
 #include <unordered_map>
-#include <vector>
 
 namespace {
 constexpr int64_t kMaxW = 50;            // ref :24 max_w
@@ -31,10 +32,6 @@ constexpr int64_t kTile = 256;           // padding unit of rows / questions (co
 constexpr int64_t kChunkQ = 1 << 16;     // questions per launch
 constexpr int64_t kTopkScratch = 1ll << 30;   // default bound of the top-k slot scratch of one launch
 
-inline bool is_space(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }   // isspace, C locale
-inline char c_upper(char c) { return (c >= 'a' && c <= 'z') ? (char)(c - 32) : c; }     // toupper, C locale
-
-int efail(int code, const std::string &msg) { return w2b_internal_fail(code, msg.c_str()); }
 #define EHIP(x)                                                                                   \
   do {                                                                                            \
     hipError_t e_ = (x);                                                                          \
@@ -297,13 +294,6 @@ static int eval_finish(EvalPtr e, int32_t bitlevel, const float *rows, hipMemcpy
   return W2B_OK;
 }
 
-// w(r) by n3 (include/word2bits_eval.h, "codes mode"): (float)(1.0 / sqrt((double)(dim + 8 n3))), n3 = 0..dim
-static std::vector<float> codes_weights(int64_t dim) {
-  std::vector<float> w((size_t)dim + 1);
-  for (int64_t n3 = 0; n3 <= dim; n3++) w[(size_t)n3] = (float)(1.0 / sqrt((double)(dim + 8 * n3)));
-  return w;
-}
-
 // common tail of the bits and codes constructors: `host_bits` ([words][wpr], may be unaligned) is uploaded, or the rows
 // are produced on the device from the trainer's tables (u != null) on its stream; codes: then w(c) of every row
 static int eval_finish_bits(EvalPtr e, const unsigned char *host_bits, const float *u, const float *v, hipStream_t ts,
@@ -485,555 +475,6 @@ extern "C" int w2b_eval_get_bits(w2b_eval *e, uint64_t *out) {
   if (!e->bits) return efail(W2B_EINVAL, "w2b_eval_get_bits: not a bits handle");
   EHIP(hipSetDevice(e->device));
   if (e->words > 0) EHIP(hipMemcpy(out, e->B, (size_t)e->words * (size_t)e->wpr * 8, hipMemcpyDeviceToHost));
-  return W2B_OK;
-}
-
-// host twin of the bits kernels: I(c) of every row, from the three Hamming distances of the definition
-extern "C" int w2b_bits_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
-                                    int32_t *I_out) {
-  if (!packed || !I_out || words < 0 || dim < 1 || b1 < 0 || b2 < 0 || b3 < 0 || b1 >= words || b2 >= words || b3 >= words)
-    return efail(W2B_EINVAL, "w2b_bits_scores_host: bad argument");
-  const int64_t wpr = (dim + 63) / 64;
-  const uint64_t *r1 = packed + b1 * wpr, *r2 = packed + b2 * wpr, *r3 = packed + b3 * wpr;
-  for (int64_t c = 0; c < words; c++) {
-    const uint64_t *rc = packed + c * wpr;
-    int64_t h1 = 0, h2 = 0, h3 = 0;
-    for (int64_t w = 0; w < wpr; w++) {
-      const uint64_t valid = (w + 1) * 64 <= dim ? ~0ull : (1ull << (dim - w * 64)) - 1;    // padding bits do not count
-      h1 += __builtin_popcountll((r1[w] ^ rc[w]) & valid);
-      h2 += __builtin_popcountll((r2[w] ^ rc[w]) & valid);
-      h3 += __builtin_popcountll((r3[w] ^ rc[w]) & valid);
-    }
-    I_out[c] = (int32_t)(dim - 2 * (h2 - h1 + h3));
-  }
-  return W2B_OK;
-}
-
-namespace {
-// what w2b_eval_combine and its host twin refuse in one question's slots (null: nothing)
-const char *bad_terms(int32_t nt, const int32_t *rows, const int8_t *signs, int64_t words) {
-  int used = 0;
-  for (int32_t t = 0; t < nt; t++) {
-    if (signs[t] < -1 || signs[t] > 1) return "a sign must be -1, 0 or +1";
-    if (signs[t] == 0) continue;
-    if (rows[t] < 0 || rows[t] >= words) return "question row out of range";
-    used++;
-  }
-  return used ? nullptr : "a question needs at least one slot with a sign";
-}
-}  // namespace
-
-// host twin of the bits form of w2b_eval_combine: I(c) = sum over the used slots of sign * (dim - 2 * Hamming(r, c))
-extern "C" int w2b_bits_combine_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t nt,
-                                            const int32_t *rows, const int8_t *signs, int32_t *I_out) {
-  const std::string who = "w2b_bits_combine_scores_host";
-  if (!packed || !rows || !signs || !I_out || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
-  if (nt < 1 || nt > W2B_EVAL_MAX_TERMS) return efail(W2B_EINVAL, who + ": the number of terms must be 1..7");
-  if (const char *why = bad_terms(nt, rows, signs, words)) return efail(W2B_EINVAL, who + ": " + why);
-  const int64_t wpr = (dim + 63) / 64;
-  for (int64_t c = 0; c < words; c++) {
-    const uint64_t *rc = packed + c * wpr;
-    int64_t I = 0;
-    for (int32_t t = 0; t < nt; t++) {
-      if (signs[t] == 0) continue;
-      const uint64_t *rt = packed + (int64_t)rows[t] * wpr;
-      int64_t h = 0;
-      for (int64_t w = 0; w < wpr; w++) {
-        const uint64_t valid = (w + 1) * 64 <= dim ? ~0ull : (1ull << (dim - w * 64)) - 1;    // padding bits do not count
-        h += __builtin_popcountll((rt[w] ^ rc[w]) & valid);
-      }
-      I += signs[t] * (dim - 2 * h);
-    }
-    I_out[c] = (int32_t)I;
-  }
-  return W2B_OK;
-}
-
-// Host twin of the codes kernels.  The float sequence of the header, one rounding per operation: this file is built with
-// -ffp-contract=off and the function's body repeats it, so that no build fuses p * w + p.
-extern "C" int w2b_codes_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int64_t b1, int64_t b2, int64_t b3,
-                                     int32_t *J_out, float *score_out) {
-#pragma clang fp contract(off)
-  if (!packed || words < 0 || dim < 1 || b1 < 0 || b2 < 0 || b3 < 0 || b1 >= words || b2 >= words || b3 >= words)
-    return efail(W2B_EINVAL, "w2b_codes_scores_host: bad argument");
-  const int64_t nb = (dim + 63) / 64, wpr = 2 * nb;
-  const std::vector<float> wt = codes_weights(dim);
-  auto valid = [&](int64_t b) { return (b + 1) * 64 <= dim ? ~0ull : (1ull << (dim - b * 64)) - 1; };   // padding bits do not count
-  auto weight = [&](const uint64_t *r) {
-    int64_t n3 = 0;
-    for (int64_t b = 0; b < nb; b++) n3 += __builtin_popcountll(r[2 * b + 1] & valid(b));
-    return wt[(size_t)n3];
-  };
-  // sum_a t_x t_c over a block: |t_x t_c| is 1 + 2 m_x + 2 m_c + 4 m_x m_c, its sign that of s_x ^ s_c
-  auto dot = [&](const uint64_t *x, const uint64_t *c) {
-    int64_t j = 0;
-    for (int64_t b = 0; b < nb; b++) {
-      const uint64_t v = valid(b), neg = (x[2 * b] ^ c[2 * b]) & v, pos = ~neg & v;
-      const uint64_t mx = x[2 * b + 1], mc = c[2 * b + 1];
-      auto mag = [&](uint64_t m) {
-        return (int64_t)__builtin_popcountll(m) + 2 * __builtin_popcountll(m & mx) + 2 * __builtin_popcountll(m & mc) +
-               4 * __builtin_popcountll(m & mx & mc);
-      };
-      j += mag(pos) - mag(neg);
-    }
-    return (int32_t)j;
-  };
-  const uint64_t *r1 = packed + b1 * wpr, *r2 = packed + b2 * wpr, *r3 = packed + b3 * wpr;
-  const float w1 = weight(r1), w2 = weight(r2), w3 = weight(r3);
-  for (int64_t c = 0; c < words; c++) {
-    const uint64_t *rc = packed + c * wpr;
-    const int32_t j1 = dot(r1, rc), j2 = dot(r2, rc), j3 = dot(r3, rc);
-    if (J_out) {
-      J_out[c] = j1;
-      J_out[words + c] = j2;
-      J_out[2 * words + c] = j3;
-    }
-    if (score_out) {
-      const float p1 = (float)j1 * w1, p2 = (float)j2 * w2, p3 = (float)j3 * w3;
-      const float d = p2 - p1;
-      const float s = d + p3;
-      score_out[c] = s * weight(rc);
-    }
-  }
-  return W2B_OK;
-}
-
-namespace {
-constexpr int64_t kCosmulMaxBits = 1ll << 24;   // the largest 1-bit size whose agreement counts are exact in float32
-constexpr float kCosmulEps = 1e-6f;             // 0x358637BD
-
-// u by agreement count on 1-bit rows: (float)A / (float)dim, one correctly rounded division, A = 0..dim
-std::vector<float> cosmul_utab(int64_t dim) {
-  std::vector<float> u((size_t)dim + 1);
-  for (int64_t a = 0; a <= dim; a++) u[(size_t)a] = (float)a / (float)dim;
-  return u;
-}
-
-// score = (u2 * u3) / (u1 + eps), one rounding per operation
-inline float cosmul_score(float u1, float u2, float u3) {
-#pragma clang fp contract(off)
-  const float num = u2 * u3;
-  const float den = u1 + kCosmulEps;
-  return num / den;
-}
-}  // namespace
-
-// Host twin of the 3CosMul kernels.  The float sequence of the header, one rounding per operation (this file is built with
-// -ffp-contract=off, and the function says so again).
-extern "C" int w2b_cosmul_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t b1,
-                                      int64_t b2, int64_t b3, float *u_out, float *score_out) {
-#pragma clang fp contract(off)
-  const std::string who = "w2b_cosmul_scores_host";
-  if (!packed || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
-  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
-  if (bitlevel == 1 && dim > kCosmulMaxBits) return efail(W2B_EINVAL, who + ": size must be at most 2^24 on 1-bit rows");
-  if (b1 < 0 || b2 < 0 || b3 < 0 || b1 >= words || b2 >= words || b3 >= words)
-    return efail(W2B_EINVAL, who + ": question row out of range");
-  const int64_t b[3] = {b1, b2, b3};
-  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
-  auto valid = [&](int64_t blk) { return (blk + 1) * 64 <= dim ? ~0ull : (1ull << (dim - blk * 64)) - 1; };   // padding bits do not count
-  std::vector<float> u((size_t)(3 * words));
-  if (bitlevel == 1) {
-    const std::vector<float> ut = cosmul_utab(dim);
-    for (int t = 0; t < 3; t++) {
-      const uint64_t *rt = packed + b[t] * wpr;
-      for (int64_t c = 0; c < words; c++) {
-        const uint64_t *rc = packed + c * wpr;
-        int64_t h = 0;
-        for (int64_t w = 0; w < nb; w++) h += __builtin_popcountll((rt[w] ^ rc[w]) & valid(w));
-        u[(size_t)(t * words + c)] = ut[(size_t)(dim - h)];
-      }
-    }
-  } else {
-    std::vector<int32_t> J((size_t)(3 * words));
-    if (int rc = w2b_codes_scores_host(packed, words, dim, b1, b2, b3, J.data(), nullptr)) return rc;
-    const std::vector<float> wt = codes_weights(dim);
-    auto weight = [&](const uint64_t *r) {
-      int64_t n3 = 0;
-      for (int64_t blk = 0; blk < nb; blk++) n3 += __builtin_popcountll(r[2 * blk + 1] & valid(blk));
-      return wt[(size_t)n3];
-    };
-    for (int t = 0; t < 3; t++) {
-      const float wb = weight(packed + b[t] * wpr);
-      for (int64_t c = 0; c < words; c++) {
-        const float pj = (float)J[(size_t)(t * words + c)] * wb;
-        const float cs = pj * weight(packed + c * wpr);
-        const float one = 1.0f + cs;
-        u[(size_t)(t * words + c)] = one * 0.5f;
-      }
-    }
-  }
-  if (u_out) memcpy(u_out, u.data(), u.size() * 4);
-  if (score_out)
-    for (int64_t c = 0; c < words; c++)
-      score_out[c] = cosmul_score(u[(size_t)c], u[(size_t)(words + c)], u[(size_t)(2 * words + c)]);
-  return W2B_OK;
-}
-
-namespace {
-constexpr int64_t kBagMaxSize = 58254;   // the largest size with 9 * 4096 * size < 2^31
-
-// what w2b_eval_bag and its host twin refuse in one bag (null: nothing)
-const char *bad_bag(int64_t n, const int32_t *ids, int64_t words) {
-  if (n < 0 || n > W2B_EVAL_MAX_BAG) return "a bag holds at most 4096 ids";
-  for (int64_t i = 0; i < n; i++)
-    if (ids[i] >= words) return "bag id out of range";
-  return nullptr;
-}
-
-// wq of the header from N_T; a question whose vector is zero weighs nothing
-inline float bag_weight(unsigned long long nt) { return nt ? (float)(1.0 / sqrt((double)nt)) : 0.f; }
-}  // namespace
-
-// Host twin of the bag kernels: T from the unpacked rows, J in 64 bits, the float steps of the header one at a time (this
-// file is built with -ffp-contract=off, and the function says so again).
-extern "C" int w2b_bag_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n,
-                                   const int32_t *ids, int32_t *J_out, float *score_out) {
-#pragma clang fp contract(off)
-  const std::string who = "w2b_bag_scores_host";
-  if (!packed || words < 0 || dim < 1 || (n > 0 && !ids)) return efail(W2B_EINVAL, who + ": bad argument");
-  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
-  if (dim > kBagMaxSize) return efail(W2B_EINVAL, who + ": size must be at most 58254 (9 * 4096 * size < 2^31)");
-  if (const char *why = bad_bag(n, ids, words)) return efail(W2B_EINVAL, who + ": " + why);
-  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
-  auto t_of = [&](const uint64_t *r, int64_t a) -> int32_t {
-    const uint64_t bit = 1ull << (a & 63);
-    if (bitlevel == 1) return (r[a >> 6] & bit) ? -1 : 1;
-    return ((r[2 * (a >> 6) + 1] & bit) ? 3 : 1) * ((r[2 * (a >> 6)] & bit) ? -1 : 1);
-  };
-  std::vector<int32_t> T((size_t)dim, 0);
-  for (int64_t i = 0; i < n; i++)
-    if (ids[i] >= 0)
-      for (int64_t a = 0; a < dim; a++) T[(size_t)a] += t_of(packed + (int64_t)ids[i] * wpr, a);
-  unsigned long long nt = 0;
-  for (int64_t a = 0; a < dim; a++) nt += (unsigned long long)((int64_t)T[(size_t)a] * T[(size_t)a]);
-  const float wq = bag_weight(nt);
-  const std::vector<float> wt = bitlevel == 2 ? codes_weights(dim) : std::vector<float>();
-  for (int64_t c = 0; c < words; c++) {
-    const uint64_t *rc = packed + c * wpr;
-    int64_t j = 0, n3 = 0;
-    for (int64_t a = 0; a < dim; a++) {
-      const int32_t t = t_of(rc, a);
-      j += (int64_t)T[(size_t)a] * t;
-      n3 += t == 3 || t == -3;
-    }
-    if (J_out) J_out[c] = (int32_t)j;
-    if (!score_out) continue;
-    if (bitlevel == 1) {
-      score_out[c] = (float)(int32_t)j / (float)dim;
-    } else {
-      const float pj = (float)(int32_t)j * wq;
-      score_out[c] = pj * wt[(size_t)n3];
-    }
-  }
-  return W2B_OK;
-}
-
-namespace {
-// what w2b_eval_vectors and its host twin refuse in one question: the first column whose value is not finite, or neither 0
-// nor of a magnitude in 2^-60 .. 2^60 (-1: none)
-int64_t bad_vector_value(const float *x, int64_t dim) {
-  for (int64_t a = 0; a < dim; a++) {
-    const float m = fabsf(x[a]);
-    if (!(m == 0.f || (m >= 0x1p-60f && m <= 0x1p60f))) return a;       // (NaN fails every comparison)
-  }
-  return -1;
-}
-const char *const kVectorRange = "a value must be finite and either 0 or of a magnitude in 2^-60 .. 2^60";
-
-// wx of the header: nx in double, column by column; a question whose vector is zero weighs nothing
-float vector_weight(const float *x, int64_t dim, int32_t normalize) {
-#pragma clang fp contract(off)
-  double nx = 0.0;
-  for (int64_t a = 0; a < dim; a++) {
-    const double sq = (double)x[a] * (double)x[a];
-    nx = nx + sq;
-  }
-  if (nx == 0.0) return 0.f;
-  return normalize ? (float)(1.0 / sqrt(nx)) : 1.0f;
-}
-}  // namespace
-
-// Host twin of the vector kernels: the fmaf chain of the header in column order, then the two multiplies one at a time (this
-// file is built with -ffp-contract=off, and the function says so again).
-extern "C" int w2b_vector_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, const float *x,
-                                      int32_t normalize, float *S_out, float *score_out) {
-#pragma clang fp contract(off)
-  const std::string who = "w2b_vector_scores_host";
-  if (!packed || !x || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
-  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
-  if (normalize != 0 && normalize != 1) return efail(W2B_EINVAL, who + ": normalize must be 0 or 1");
-  const int64_t bad = bad_vector_value(x, dim);
-  if (bad >= 0) return efail(W2B_EINVAL, who + ": column " + std::to_string(bad) + ": " + kVectorRange);
-  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
-  const float wx = vector_weight(x, dim, normalize);
-  const std::vector<float> wt = bitlevel == 2 ? codes_weights(dim) : std::vector<float>();
-  const float wbits = (float)(1.0 / sqrt((double)dim));
-  for (int64_t c = 0; c < words; c++) {
-    const uint64_t *rc = packed + c * wpr;
-    float acc = 0.f;
-    int64_t n3 = 0;
-    for (int64_t a = 0; a < dim; a++) {
-      const uint64_t bit = 1ull << (a & 63);
-      float t = 1.f;
-      if (bitlevel == 2 && (rc[2 * (a >> 6) + 1] & bit)) t = 3.f, n3++;
-      if (rc[bitlevel * (a >> 6)] & bit) t = -t;
-      acc = fmaf(x[a], t, acc);
-    }
-    if (S_out) S_out[c] = acc;
-    if (!score_out) continue;
-    const float ps = acc * wx;
-    score_out[c] = ps * (bitlevel == 2 ? wt[(size_t)n3] : wbits);
-  }
-  return W2B_OK;
-}
-
-namespace {
-constexpr int64_t kDocsMaxSize = 1ll << 21;      // size below it: 1024 * size < 2^31 and ldexp(cos, 50) is an integer
-constexpr int64_t kDocsMaxDocs = 0x7FFFFF00ll;
-constexpr int64_t kDocsMaxAll = 1ll << 28;       // nq * n_docs of an all_scores request
-
-// what w2b_eval_docs_set, w2b_eval_docs and the host twin refuse in texts given as ids + offsets before they look at a handle
-// or a table (empty: nothing); `what` = "document" or "query"
-std::string bad_texts(int64_t n_ids, const int32_t *ids, int64_t n, const int64_t *offsets, const char *what) {
-  if (n < 0 || n_ids < 0 || (n > 0 && !offsets) || (n_ids > 0 && !ids)) return "bad argument";
-  if (n == 0 ? n_ids != 0 : (offsets[0] != 0 || offsets[n] != n_ids))
-    return std::string(what) + " offsets must start at 0 and end at the number of ids";
-  for (int64_t d = 0; d < n; d++) {
-    if (offsets[d + 1] < offsets[d] || offsets[d + 1] > n_ids) return std::string(what) + " offsets must not decrease";
-    if (offsets[d + 1] - offsets[d] > W2B_EVAL_MAX_DOC) return std::string("a ") + what + " holds at most 1024 positions";
-  }
-  return std::string();
-}
-bool bad_text_ids(int64_t n_ids, const int32_t *ids, int64_t words) {
-  for (int64_t i = 0; i < n_ids; i++)
-    if (ids[i] >= words) return true;
-  return false;
-}
-const char *const kDocsSize = "size must be below 2^21 (1024 * size < 2^31)";
-const char *const kDocsFp32 = "not available on an fp32 handle: load the file with bits or codes";
-
-// the float steps of the header: one directed score from its integer sum
-inline float docs_score(int32_t bitlevel, int64_t sum, int64_t m, int64_t dim) {
-#pragma clang fp contract(off)
-  if (bitlevel == 1) return (float)(int32_t)sum / (float)(int32_t)(m * dim);
-  const float div = (float)m * 0x1p50f;          // exact
-  return (float)sum / div;
-}
-}  // namespace
-
-// Host twin of the document kernels: every (query position, document position) pair from the packed rows themselves, the
-// maxima and the sums in 64-bit integers, the float steps of the header one at a time (this file is built with
-// -ffp-contract=off, and the function says so again).
-extern "C" int w2b_docs_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n_ids,
-                                    const int32_t *ids, int64_t n_docs, const int64_t *offsets, int64_t n_q,
-                                    const int32_t *qids, int32_t symmetric, int64_t *dir_out, float *score_out) {
-#pragma clang fp contract(off)
-  const std::string who = "w2b_docs_scores_host";
-  if (symmetric != 0 && symmetric != 1) return efail(W2B_EINVAL, who + ": symmetric must be 0 or 1");
-  if (n_q < 0 || (n_q > 0 && !qids)) return efail(W2B_EINVAL, who + ": bad argument");
-  if (n_q > W2B_EVAL_MAX_DOC) return efail(W2B_EINVAL, who + ": a query holds at most 1024 positions");
-  if (n_docs > kDocsMaxDocs) return efail(W2B_EINVAL, who + ": at most 0x7FFFFF00 documents");
-  const std::string why = bad_texts(n_ids, ids, n_docs, offsets, "document");
-  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
-  if (!packed || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
-  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
-  if (dim >= kDocsMaxSize) return efail(W2B_EINVAL, who + ": " + kDocsSize);
-  if (bad_text_ids(n_ids, ids, words)) return efail(W2B_EINVAL, who + ": document id out of range");
-  if (bad_text_ids(n_q, qids, words)) return efail(W2B_EINVAL, who + ": query id out of range");
-  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
-  auto valid = [&](int64_t b) { return (b + 1) * 64 <= dim ? ~0ull : (1ull << (dim - b * 64)) - 1; };   // padding bits do not count
-  const std::vector<float> wt = bitlevel == 2 ? codes_weights(dim) : std::vector<float>();
-  auto weight = [&](const uint64_t *r) {
-    int64_t n3 = 0;
-    for (int64_t b = 0; b < nb; b++) n3 += __builtin_popcountll(r[2 * b + 1] & valid(b));
-    return wt[(size_t)n3];
-  };
-  // I(x, c), or F(x, c) = (int64) ldexp(cos(x, c), 50)
-  auto pair = [&](const uint64_t *x, float wx, const uint64_t *c, float wc) -> int64_t {
-    if (bitlevel == 1) {
-      int64_t h = 0;
-      for (int64_t b = 0; b < nb; b++) h += __builtin_popcountll((x[b] ^ c[b]) & valid(b));
-      return dim - 2 * h;
-    }
-    int64_t j = 0;
-    for (int64_t b = 0; b < nb; b++) {
-      const uint64_t v = valid(b), neg = (x[2 * b] ^ c[2 * b]) & v, pos = ~neg & v;
-      const uint64_t mx = x[2 * b + 1], mc = c[2 * b + 1];
-      auto mag = [&](uint64_t m) {
-        return (int64_t)__builtin_popcountll(m) + 2 * __builtin_popcountll(m & mx) + 2 * __builtin_popcountll(m & mc) +
-               4 * __builtin_popcountll(m & mx & mc);
-      };
-      j += mag(pos) - mag(neg);
-    }
-    const float pj = (float)(int32_t)j * wx;
-    const float cs = pj * wc;
-    return (int64_t)ldexpf(cs, 50);
-  };
-  std::vector<const uint64_t *> qr;
-  std::vector<float> qw;
-  for (int64_t i = 0; i < n_q; i++)
-    if (qids[i] >= 0) {
-      qr.push_back(packed + (int64_t)qids[i] * wpr);
-      qw.push_back(bitlevel == 2 ? weight(qr.back()) : 0.f);
-    }
-  const int64_t mq = (int64_t)qr.size();
-  std::vector<int64_t> best_x((size_t)mq);
-  for (int64_t d = 0; d < n_docs; d++) {
-    int64_t md = 0, r_qd = 0, r_dq = 0;
-    for (int64_t i = offsets[d]; i < offsets[d + 1]; i++) {
-      if (ids[i] < 0 || mq == 0) continue;
-      const uint64_t *c = packed + (int64_t)ids[i] * wpr;
-      const float wc = bitlevel == 2 ? weight(c) : 0.f;
-      int64_t best_c = 0;
-      for (int64_t x = 0; x < mq; x++) {
-        const int64_t v = pair(qr[(size_t)x], qw[(size_t)x], c, wc);
-        if (md == 0 || v > best_x[(size_t)x]) best_x[(size_t)x] = v;
-        if (x == 0 || v > best_c) best_c = v;
-      }
-      r_dq += best_c;
-      md++;
-    }
-    if (md > 0)
-      for (int64_t x = 0; x < mq; x++) r_qd += best_x[(size_t)x];
-    if (dir_out) {
-      dir_out[d] = r_qd;
-      dir_out[n_docs + d] = r_dq;
-    }
-    if (!score_out) continue;
-    float sc = 0.f;
-    if (mq > 0 && md > 0) {
-      sc = docs_score(bitlevel, r_qd, mq, dim);
-      if (symmetric) {
-        const float s2 = docs_score(bitlevel, r_dq, md, dim);
-        sc = s2 < sc ? s2 : sc;
-      }
-    }
-    score_out[d] = sc;
-  }
-  return W2B_OK;
-}
-
-namespace {
-constexpr int64_t kPairsMaxSize = 1ll << 24;     // 12288^2 * size < 2^53: J, N_A, N_B are exact as doubles
-
-// what w2b_eval_pairs and its host twin refuse before they look at a handle or a table (empty: nothing)
-std::string bad_pairs(int64_t n_ids, const int32_t *ids, int64_t np, const int64_t *offsets, const float *score,
-                      const int64_t *parts) {
-  if (np < 0 || n_ids < 0 || (np > 0 && (!offsets || (!score && !parts))) || (n_ids > 0 && !ids)) return "bad argument";
-  if (np > (INT64_MAX >> 2)) return "bad argument";
-  if (np == 0 ? n_ids != 0 : (offsets[0] != 0 || offsets[2 * np] != n_ids)) return "offsets must start at 0 and end at n_ids";
-  for (int64_t b = 0; b < 2 * np; b++) {
-    if (offsets[b + 1] < offsets[b] || offsets[b + 1] > n_ids) return "offsets must not decrease";
-    if (offsets[b + 1] - offsets[b] > W2B_EVAL_MAX_BAG) return "a bag holds at most 4096 ids";
-  }
-  return std::string();
-}
-// the first pair with an id >= words (-1: none)
-int64_t bad_pair_id(const int32_t *ids, int64_t np, const int64_t *offsets, int64_t words) {
-  for (int64_t p = 0; p < np; p++)
-    for (int64_t i = offsets[2 * p]; i < offsets[2 * p + 2]; i++)
-      if (ids[i] >= words) return p;
-  return -1;
-}
-
-// the score of the header from the three integers; an empty pair scores +0
-inline float pair_score(int64_t j, int64_t na, int64_t nb) {
-#pragma clang fp contract(off)
-  if (na == 0 || nb == 0) return 0.f;
-  const double nn = (double)na * (double)nb;
-  const double root = sqrt(nn);
-  return (float)((double)j / root);
-}
-}  // namespace
-
-// Host twin of the pair kernels: both pooled vectors from the unpacked rows, the three sums in 64-bit integers, the double
-// steps of the header one at a time (this file is built with -ffp-contract=off, and pair_score says so again).
-extern "C" int w2b_pairs_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n_ids,
-                              const int32_t *ids, int64_t np, const int64_t *offsets, float *score, int64_t *parts) {
-  const std::string who = "w2b_pairs_host";
-  const std::string why = bad_pairs(n_ids, ids, np, offsets, score, parts);
-  if (!why.empty()) return efail(W2B_EINVAL, who + ": " + why);
-  if (!packed || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
-  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
-  if (dim > kPairsMaxSize) return efail(W2B_EINVAL, who + ": size must be at most 2^24");
-  const int64_t bad = bad_pair_id(ids, np, offsets, words);
-  if (bad >= 0) return efail(W2B_EINVAL, who + ": pair " + std::to_string(bad) + ": id out of range");
-  const int64_t nb = (dim + 63) / 64, wpr = nb * bitlevel;
-  auto t_of = [&](const uint64_t *r, int64_t a) -> int32_t {
-    const uint64_t bit = 1ull << (a & 63);
-    if (bitlevel == 1) return (r[a >> 6] & bit) ? -1 : 1;
-    return ((r[2 * (a >> 6) + 1] & bit) ? 3 : 1) * ((r[2 * (a >> 6)] & bit) ? -1 : 1);
-  };
-  std::vector<int32_t> T[2] = {std::vector<int32_t>((size_t)dim), std::vector<int32_t>((size_t)dim)};
-  for (int64_t p = 0; p < np; p++) {
-    for (int side = 0; side < 2; side++) {
-      std::fill(T[side].begin(), T[side].end(), 0);
-      for (int64_t i = offsets[2 * p + side]; i < offsets[2 * p + side + 1]; i++)
-        if (ids[i] >= 0)
-          for (int64_t a = 0; a < dim; a++) T[side][(size_t)a] += t_of(packed + (int64_t)ids[i] * wpr, a);
-    }
-    int64_t j = 0, na = 0, nbb = 0;
-    for (int64_t a = 0; a < dim; a++) {
-      const int64_t x = T[0][(size_t)a], y = T[1][(size_t)a];
-      j += x * y;
-      na += x * x;
-      nbb += y * y;
-    }
-    if (score) score[p] = pair_score(j, na, nbb);
-    if (parts) parts[3 * p] = j, parts[3 * p + 1] = na, parts[3 * p + 2] = nbb;
-  }
-  return W2B_OK;
-}
-
-namespace {
-// Pearson's r of the header; NaN with n < 2 or a zero variance
-double pearson_r(const std::vector<double> &x, const std::vector<double> &y) {
-#pragma clang fp contract(off)
-  const size_t n = x.size();
-  if (n < 2) return NAN;
-  if (*std::min_element(x.begin(), x.end()) == *std::max_element(x.begin(), x.end()) ||
-      *std::min_element(y.begin(), y.end()) == *std::max_element(y.begin(), y.end()))
-    return NAN;                                    // (a constant: its deviations from a rounded mean need not be zero)
-  double mx = 0, my = 0;
-  for (size_t i = 0; i < n; i++) mx += x[i], my += y[i];
-  mx /= (double)n;
-  my /= (double)n;
-  double sxy = 0, sxx = 0, syy = 0;
-  for (size_t i = 0; i < n; i++) {
-    const double dx = x[i] - mx, dy = y[i] - my;
-    sxy += dx * dy;
-    sxx += dx * dx;
-    syy += dy * dy;
-  }
-  if (!(sxx > 0) || !(syy > 0)) return NAN;
-  return sxy / sqrt(sxx * syy);
-}
-// 1-based ranks, equal values sharing the mean of their ranks
-std::vector<double> mean_ranks(const std::vector<double> &v) {
-  const size_t n = v.size();
-  std::vector<size_t> idx(n);
-  for (size_t i = 0; i < n; i++) idx[i] = i;
-  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return v[a] < v[b]; });
-  std::vector<double> r(n);
-  for (size_t i = 0; i < n;) {
-    size_t k = i;
-    while (k < n && v[idx[k]] == v[idx[i]]) k++;
-    const double mean = 0.5 * (double)(i + 1 + k);           // ranks i + 1 .. k
-    for (size_t t = i; t < k; t++) r[idx[t]] = mean;
-    i = k;
-  }
-  return r;
-}
-}  // namespace
-
-extern "C" int w2b_rank_correlation(int64_t n, const double *x, const double *y, double *pearson, double *spearman) {
-  if (n < 0 || (n > 0 && (!x || !y))) return efail(W2B_EINVAL, "w2b_rank_correlation: bad argument");
-  const std::vector<double> xv(x, x + n), yv(y, y + n);
-  bool nan = false;
-  for (int64_t i = 0; i < n; i++) nan |= std::isnan(xv[(size_t)i]) || std::isnan(yv[(size_t)i]);
-  if (pearson) *pearson = nan ? NAN : pearson_r(xv, yv);
-  if (spearman) *spearman = nan ? NAN : pearson_r(mean_ranks(xv), mean_ranks(yv));
   return W2B_OK;
 }
 
@@ -1770,6 +1211,7 @@ extern "C" int w2b_eval_docs_set(w2b_eval *e, int64_t n_ids, const int32_t *ids,
 extern "C" int64_t w2b_eval_docs_count(const w2b_eval *e) { return e ? e->docs_n : 0; }
 
 namespace {
+constexpr int64_t kDocsMaxAll = 1ll << 28;       // nq * n_docs of an all_scores request
 inline int64_t docs_pad16(int64_t m) { return (m + 15) / 16 * 16; }
 inline size_t docs_align(size_t b) { return (b + 255) / 256 * 256; }
 }  // namespace
@@ -2011,769 +1453,7 @@ extern "C" int w2b_eval_timing_read(w2b_eval *e, double *kernel_ms, int64_t *lau
   return W2B_OK;
 }
 
-// ------------------------------------------------------------------------------------ transcript
-namespace {
-// scanf("%s", st) over a buffer.  `hit_end` mirrors feof(stdin): it latches as soon as a read runs into the end
-// of the input, which also happens while reading a last token that has no trailing white space.
-struct TokenIn {
-  const char *p;
-  int64_t n, pos = 0;
-  bool hit_end = false;
-  bool next(std::string &st) {             // false: nothing read, st keeps its old contents
-    while (pos < n && is_space((unsigned char)p[pos])) pos++;
-    if (pos >= n) { hit_end = true; return false; }
-    const int64_t s = pos;
-    while (pos < n && !is_space((unsigned char)p[pos])) pos++;
-    if (pos >= n) hit_end = true;
-    st.assign(p + s, (size_t)(pos - s));
-    return true;
-  }
-};
-void upper_inplace(std::string &s) { for (char &c : s) c = c_upper(c); }
-
-struct Step {                // what the loop of ref :114-186 does, in stream order
-  enum Kind { SectionEnd, SectionName, Question } kind;
-  int qid;                   // QID at that moment
-  std::string text;          // section name / expected word (st4)
-  int64_t q;                 // index into the batched questions
-};
-
-void appendf(std::string &out, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-void appendf(std::string &out, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  const int n = vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  out.append(buf, (size_t)(n < (int)sizeof buf ? n : (int)sizeof buf - 1));
-}
-
-// a text result leaves the library as a malloc'ed, 0-terminated copy (w2b_eval_free_text)
-int text_out(const std::string &txt, const char *who, char **out, int64_t *out_len) {
-  char *buf = (char *)malloc(txt.size() + 1);
-  if (!buf) return efail(W2B_ENOMEM, std::string(who) + ": out of memory");
-  memcpy(buf, txt.data(), txt.size());
-  buf[txt.size()] = 0;
-  *out = buf;
-  if (out_len) *out_len = (int64_t)txt.size();
-  return W2B_OK;
-}
-}  // namespace
-
-// `answer(e, nq, b1, b2, b3, best)` scores all answerable questions at once: best[q] = the answer's row or -1
-template <class Answer>
-static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len, const char *who,
-                           Answer answer) {
-  if (!e || !out || len < 0 || (len > 0 && !questions)) return efail(W2B_EINVAL, std::string(who) + ": bad argument");
-  *out = nullptr;
-  TokenIn in{questions, len};
-  std::string st1, st2, st3, st4;
-  std::vector<Step> steps;
-  std::vector<int32_t> b1s, b2s, b3s;
-  int QID = 0, TQ = 0, TQS = 0;
-  // pass 1: parse the stream exactly like the scanf loop; collect the answerable questions
-  for (;;) {
-    in.next(st1);
-    upper_inplace(st1);
-    if (st1 == ":" || st1 == "EXIT" || in.hit_end) {                 // ref :119
-      steps.push_back({Step::SectionEnd, QID, std::string(), 0});
-      QID++;
-      in.next(st1);                                                   // section name, printed as read (ref :126-128)
-      if (in.hit_end) break;
-      steps.push_back({Step::SectionName, QID, st1, 0});
-      continue;
-    }
-    in.next(st2); upper_inplace(st2);
-    in.next(st3); upper_inplace(st3);
-    in.next(st4); upper_inplace(st4);
-    const int64_t r1 = w2b_eval_lookup(e, st1.c_str()), r2 = w2b_eval_lookup(e, st2.c_str()),
-                  r3 = w2b_eval_lookup(e, st3.c_str());
-    TQ++;
-    if (r1 == e->words || r2 == e->words || r3 == e->words) continue;  // ref :149-151
-    if (w2b_eval_lookup(e, st4.c_str()) == e->words) continue;          // ref :152-153
-    TQS++;
-    steps.push_back({Step::Question, QID, st4, (int64_t)b1s.size()});
-    b1s.push_back((int32_t)r1);
-    b2s.push_back((int32_t)r2);
-    b3s.push_back((int32_t)r3);
-  }
-  // the scan of ref :155-177 for all of them at once, on the GPU
-  std::vector<int32_t> best(b1s.size());
-  if (!b1s.empty()) {
-    const int rc = answer(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), best.data());
-    if (rc != W2B_OK) return rc;
-  }
-  // pass 2: replay the counters and print (ref :120-131,178-187)
-  std::string txt = "Starting eval...\n";
-  int TCN = 0, CCN = 0, TACN = 0, CACN = 0, SECN = 0, SYCN = 0, SEAC = 0, SYAC = 0;
-  for (const Step &s : steps) {
-    if (s.kind == Step::SectionEnd) {
-      if (TCN == 0) TCN = 1;
-      if (s.qid != 0) {
-        appendf(txt, "ACCURACY TOP1: %.2f %%  (%d / %d)\n", CCN / (float)TCN * 100, CCN, TCN);
-        appendf(txt, "Total accuracy: %.2f %%   Semantic accuracy: %.2f %%   Syntactic accuracy: %.2f %% \n",
-                CACN / (float)TACN * 100, SEAC / (float)SECN * 100, SYAC / (float)SYCN * 100);
-      }
-    } else if (s.kind == Step::SectionName) {
-      txt += s.text;
-      txt += ":\n";
-      TCN = 0;
-      CCN = 0;
-    } else {
-      const int32_t c = best[(size_t)s.q];
-      const char *bestw = c >= 0 ? e->vocab.data() + (int64_t)c * kMaxW : "";
-      if (s.text == bestw) {                                           // strcmp on the words (ref :178)
-        CCN++;
-        CACN++;
-        if (s.qid <= 5) SEAC++; else SYAC++;
-      }
-      if (s.qid <= 5) SECN++; else SYCN++;
-      TCN++;
-      TACN++;
-    }
-  }
-  appendf(txt, "Questions seen / total: %d %d   %.2f %% \n", TQS, TQ, TQS / (float)TQ * 100);
-  return text_out(txt, who, out, out_len);
-}
-
-extern "C" int w2b_eval_transcript(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len) {
-  return eval_transcript(e, questions, len, out, out_len, "w2b_eval_transcript",
-                         [](w2b_eval *ev, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t *best) {
-                           return w2b_eval_top1(ev, nq, b1, b2, b3, best, nullptr);
-                         });
-}
-
-extern "C" int w2b_eval_transcript_cosmul(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len) {
-  return eval_transcript(e, questions, len, out, out_len, "w2b_eval_transcript_cosmul",
-                         [](w2b_eval *ev, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t *best) {
-                           return w2b_eval_cosmul(ev, nq, b1, b2, b3, 1, best, nullptr);
-                         });
-}
-
-
-// ------------------------------------------------------------------------------------ nearest: the text form
-namespace {
-// one line of a query text: what was understood, or what to say instead
-struct QueryLine { std::string head; std::string error; int64_t q; };
-
-// the next line of queries[pos .. len) split on white space, every token upper-cased (ref :118); false at the end
-bool next_query_line(const char *queries, int64_t len, int64_t &pos, std::vector<std::string> &tok) {
-  if (pos >= len) return false;
-  int64_t end = pos;
-  while (end < len && queries[end] != '\n') end++;
-  tok.clear();
-  for (int64_t i = pos; i < end;) {
-    while (i < end && is_space((unsigned char)queries[i])) i++;
-    const int64_t s0 = i;
-    while (i < end && !is_space((unsigned char)queries[i])) i++;
-    if (i > s0) {
-      tok.emplace_back(queries + s0, (size_t)(i - s0));
-      upper_inplace(tok.back());
-    }
-  }
-  pos = end + 1;
-  return true;
-}
-
-std::string joined(const std::vector<std::string> &tok) {
-  std::string head;
-  for (size_t i = 0; i < tok.size(); i++) head += (i ? " " : "") + tok[i];
-  return head;
-}
-
-// the answer text: per line its head, then the error or the list of question `q` in best / bestd [..][k]
-std::string query_answers(const w2b_eval *e, const std::vector<QueryLine> &lines, int32_t k, const std::vector<int32_t> &best,
-                          const std::vector<float> &bestd) {
-  std::string txt;
-  for (const QueryLine &ln : lines) {
-    txt += ln.head;
-    if (!ln.error.empty()) {
-      txt += ": " + ln.error + "\n";
-      continue;
-    }
-    txt += ":\n";
-    for (int j = 0; j < k; j++) {
-      const int32_t c = best[(size_t)(ln.q * k + j)];
-      if (c < 0) break;
-      appendf(txt, "%d\t%s\t%.6f\n", j + 1, e->vocab.data() + (int64_t)c * kMaxW, (double)bestd[(size_t)(ln.q * k + j)]);
-    }
-  }
-  return txt;
-}
-}  // namespace
-
-extern "C" int w2b_eval_nearest_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out,
-                                     int64_t *out_len) {
-  if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_nearest_text: bad argument");
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_nearest_text: k must be 1..64");
-  *out = nullptr;
-  std::vector<QueryLine> lines;
-  std::vector<int32_t> b1s, b2s, b3s;
-  std::vector<std::string> tok;
-  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
-    if (tok.empty()) continue;
-    QueryLine ln{joined(tok), std::string(), -1};
-    if (tok.size() != 1 && tok.size() != 3) {
-      ln.error = "expected 1 or 3 words";
-    } else {
-      int64_t r[3] = {0, 0, 0};
-      for (size_t i = 0; i < tok.size() && ln.error.empty(); i++) {
-        r[i] = w2b_eval_lookup(e, tok[i].c_str());
-        if (r[i] == e->words) ln.error = "not in vocabulary: " + tok[i];
-      }
-      if (ln.error.empty()) {
-        if (tok.size() == 1) r[1] = r[2] = r[0];
-        ln.q = (int64_t)b1s.size();
-        b1s.push_back((int32_t)r[0]);
-        b2s.push_back((int32_t)r[1]);
-        b3s.push_back((int32_t)r[2]);
-      }
-    }
-    lines.push_back(ln);
-  }
-  std::vector<int32_t> best(b1s.size() * (size_t)k);
-  std::vector<float> bestd(b1s.size() * (size_t)k);
-  if (!b1s.empty()) {
-    const int rc = w2b_eval_topk(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), k, best.data(), bestd.data());
-    if (rc != W2B_OK) return rc;
-  }
-  const std::string txt = query_answers(e, lines, k, best, bestd);
-  return text_out(txt, "w2b_eval_nearest_text", out, out_len);
-}
-
-// the 3CosMul form: every non-empty line is three words A B C
-extern "C" int w2b_eval_cosmul_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out, int64_t *out_len) {
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_cosmul_text: k must be 1..64");
-  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_cosmul_text: bad argument");
-  if (!e) return efail(W2B_EINVAL, "w2b_eval_cosmul_text: null handle");
-  if (!e->bits && !e->codes)
-    return efail(W2B_EINVAL, "w2b_eval_cosmul_text: not available on an fp32 handle: load the file with bits or codes");
-  *out = nullptr;
-  std::vector<QueryLine> lines;
-  std::vector<int32_t> b1s, b2s, b3s;
-  std::vector<std::string> tok;
-  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
-    if (tok.empty()) continue;
-    QueryLine ln{joined(tok), std::string(), -1};
-    if (tok.size() != 3) {
-      ln.error = "expected 3 words";
-    } else {
-      int64_t r[3] = {0, 0, 0};
-      for (size_t i = 0; i < 3 && ln.error.empty(); i++) {
-        r[i] = w2b_eval_lookup(e, tok[i].c_str());
-        if (r[i] == e->words) ln.error = "not in vocabulary: " + tok[i];
-      }
-      if (ln.error.empty()) {
-        ln.q = (int64_t)b1s.size();
-        b1s.push_back((int32_t)r[0]);
-        b2s.push_back((int32_t)r[1]);
-        b3s.push_back((int32_t)r[2]);
-      }
-    }
-    lines.push_back(ln);
-  }
-  std::vector<int32_t> best(b1s.size() * (size_t)k);
-  std::vector<float> bestd(b1s.size() * (size_t)k);
-  if (!b1s.empty()) {
-    const int rc = w2b_eval_cosmul(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), k, best.data(), bestd.data());
-    if (rc != W2B_OK) return rc;
-  }
-  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_cosmul_text", out, out_len);
-}
-
-// the signed form: +WORD, -WORD or WORD, 1 to W2B_EVAL_MAX_TERMS of them per line
-extern "C" int w2b_eval_combine_text(w2b_eval *e, const char *queries, int64_t len, int32_t k, char **out,
-                                     int64_t *out_len) {
-  if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_combine_text: bad argument");
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_combine_text: k must be 1..64");
-  if (e->codes) return efail(W2B_EINVAL, "w2b_eval_combine_text: not available in codes mode");
-  *out = nullptr;
-  std::vector<QueryLine> lines;
-  std::vector<int32_t> rows;
-  std::vector<int8_t> signs;
-  std::vector<std::string> tok;
-  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
-    if (tok.empty()) continue;
-    QueryLine ln{joined(tok), std::string(), -1};
-    int32_t r[W2B_EVAL_MAX_TERMS] = {0};
-    int8_t sg[W2B_EVAL_MAX_TERMS] = {0};
-    if (tok.size() > W2B_EVAL_MAX_TERMS) ln.error = "expected 1 to 7 signed words";
-    for (size_t i = 0; i < tok.size() && ln.error.empty(); i++) {
-      const bool has_sign = tok[i][0] == '+' || tok[i][0] == '-';
-      const std::string word = tok[i].substr(has_sign ? 1 : 0);
-      const int64_t row = w2b_eval_lookup(e, word.c_str());
-      if (row == e->words) ln.error = "not in vocabulary: " + word;
-      r[i] = (int32_t)row;
-      sg[i] = tok[i][0] == '-' ? -1 : 1;
-    }
-    if (ln.error.empty()) {
-      ln.q = (int64_t)(rows.size() / W2B_EVAL_MAX_TERMS);
-      rows.insert(rows.end(), r, r + W2B_EVAL_MAX_TERMS);
-      signs.insert(signs.end(), sg, sg + W2B_EVAL_MAX_TERMS);
-    }
-    lines.push_back(ln);
-  }
-  const size_t nq = rows.size() / W2B_EVAL_MAX_TERMS;
-  std::vector<int32_t> best(nq * (size_t)k);
-  std::vector<float> bestd(nq * (size_t)k);
-  if (nq > 0) {
-    const int rc = w2b_eval_combine(e, (int64_t)nq, W2B_EVAL_MAX_TERMS, rows.data(), signs.data(), k, best.data(), bestd.data());
-    if (rc != W2B_OK) return rc;
-  }
-  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_combine_text", out, out_len);
-}
-
-// the bag form: every non-empty line is one bag of 1 to W2B_EVAL_MAX_BAG words
-extern "C" int w2b_eval_bag_text(w2b_eval *e, const char *queries, int64_t len, int32_t exclude_own, int32_t k, char **out,
-                                 int64_t *out_len) {
-  if (!e || !out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_bag_text: bad argument");
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_bag_text: k must be 1..64");
-  if (exclude_own != 0 && exclude_own != 1) return efail(W2B_EINVAL, "w2b_eval_bag_text: exclude_own must be 0 or 1");
-  if (!e->bits && !e->codes) return efail(W2B_EINVAL, "w2b_eval_bag_text: needs a bits or a codes handle");
-  *out = nullptr;
-  std::vector<QueryLine> lines;
-  std::vector<int32_t> ids;
-  std::vector<int64_t> offsets(1, 0);
-  std::vector<std::string> tok;
-  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
-    if (tok.empty()) continue;
-    QueryLine ln{joined(tok), std::string(), -1};
-    if (tok.size() > W2B_EVAL_MAX_BAG) ln.error = "expected 1 to 4096 words";
-    const size_t at = ids.size();
-    for (size_t i = 0; i < tok.size() && ln.error.empty(); i++) {
-      const int64_t row = w2b_eval_lookup(e, tok[i].c_str());
-      if (row == e->words) ln.error = "not in vocabulary: " + tok[i];
-      ids.push_back((int32_t)row);
-    }
-    if (ln.error.empty()) {
-      ln.q = (int64_t)offsets.size() - 1;
-      offsets.push_back((int64_t)ids.size());
-    } else {
-      ids.resize(at);
-    }
-    lines.push_back(ln);
-  }
-  const size_t nq = offsets.size() - 1;
-  std::vector<int32_t> best(nq * (size_t)k);
-  std::vector<float> bestd(nq * (size_t)k);
-  if (nq > 0) {
-    const int rc = w2b_eval_bag(e, (int64_t)ids.size(), ids.data(), (int64_t)nq, offsets.data(), exclude_own, k, best.data(),
-                                bestd.data());
-    if (rc != W2B_OK) return rc;
-  }
-  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_bag_text", out, out_len);
-}
-
-// the vector form: every non-empty line is `size` numbers
-extern "C" int w2b_eval_vectors_text(w2b_eval *e, const char *queries, int64_t len, int32_t normalize, int32_t k, char **out,
-                                     int64_t *out_len) {
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, "w2b_eval_vectors_text: k must be 1..64");
-  if (normalize != 0 && normalize != 1) return efail(W2B_EINVAL, "w2b_eval_vectors_text: normalize must be 0 or 1");
-  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, "w2b_eval_vectors_text: bad argument");
-  if (!e) return efail(W2B_EINVAL, "w2b_eval_vectors_text: null handle");
-  *out = nullptr;
-  static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-  if (!c_locale) return efail(W2B_ENOMEM, "w2b_eval_vectors_text: no C locale");
-  std::vector<QueryLine> lines;
-  std::vector<float> x, row((size_t)e->size);
-  std::vector<std::string> tok;
-  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
-    if (tok.empty()) continue;
-    QueryLine ln{"vector " + std::to_string(lines.size() + 1), std::string(), -1};
-    bool numbers = (int64_t)tok.size() == e->size;
-    for (size_t i = 0; i < tok.size() && numbers; i++) {
-      char *end = nullptr;
-      row[i] = strtof_l(tok[i].c_str(), &end, c_locale);
-      numbers = end == tok[i].c_str() + tok[i].size();
-    }
-    if (!numbers) {
-      ln.error = "expected " + std::to_string(e->size) + " numbers";
-    } else if (bad_vector_value(row.data(), e->size) >= 0) {
-      ln.error = "value out of range";
-    } else {
-      ln.q = (int64_t)(x.size() / (size_t)e->size);
-      x.insert(x.end(), row.begin(), row.end());
-    }
-    lines.push_back(ln);
-  }
-  const size_t nq = x.size() / (size_t)e->size;
-  std::vector<int32_t> best(nq * (size_t)k);
-  std::vector<float> bestd(nq * (size_t)k);
-  if (nq > 0) {
-    const int rc = w2b_eval_vectors(e, (int64_t)nq, x.data(), normalize, k, best.data(), bestd.data());
-    if (rc != W2B_OK) return rc;
-  }
-  return text_out(query_answers(e, lines, k, best, bestd), "w2b_eval_vectors_text", out, out_len);
-}
-
-// the corpus from text: one document per line, empty lines included; words that are not in the vocabulary are dropped
-extern "C" int w2b_eval_docs_set_text(w2b_eval *e, const char *text, int64_t len, int64_t *n_docs, int64_t *dropped) {
-  const std::string who = "w2b_eval_docs_set_text";
-  if (len < 0 || (len > 0 && !text)) return efail(W2B_EINVAL, who + ": bad argument");
-  if (!e) return efail(W2B_EINVAL, who + ": null handle");
-  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": " + kDocsFp32);
-  std::vector<int32_t> ids;
-  std::vector<int64_t> offsets(1, 0);
-  std::vector<std::string> tok;
-  int64_t lost = 0;
-  for (int64_t pos = 0; next_query_line(text, len, pos, tok);) {
-    for (const std::string &w : tok) {
-      const int64_t row = w2b_eval_lookup(e, w.c_str());
-      if (row == e->words) lost++;
-      else ids.push_back((int32_t)row);
-    }
-    if ((int64_t)ids.size() - offsets.back() > W2B_EVAL_MAX_DOC)
-      return efail(W2B_EINVAL, who + ": line " + std::to_string(offsets.size()) + ": a document holds at most 1024 words");
-    offsets.push_back((int64_t)ids.size());
-  }
-  if (int rc = w2b_eval_docs_set(e, (int64_t)ids.size(), ids.data(), (int64_t)offsets.size() - 1, offsets.data())) return rc;
-  if (n_docs) *n_docs = (int64_t)offsets.size() - 1;
-  if (dropped) *dropped = lost;
-  return W2B_OK;
-}
-
-// the document form: every non-empty line is one query text; an answer line names a document by its line number
-extern "C" int w2b_eval_docs_text(w2b_eval *e, const char *queries, int64_t len, int32_t symmetric, int32_t k, char **out,
-                                  int64_t *out_len) {
-  const std::string who = "w2b_eval_docs_text";
-  if (k < 1 || k > W2B_EVAL_MAX_K) return efail(W2B_EINVAL, who + ": k must be 1..64");
-  if (symmetric != 0 && symmetric != 1) return efail(W2B_EINVAL, who + ": symmetric must be 0 or 1");
-  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, who + ": bad argument");
-  if (!e) return efail(W2B_EINVAL, who + ": null handle");
-  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": " + kDocsFp32);
-  if (e->docs_n == 0) return efail(W2B_EINVAL, who + ": no corpus is set (w2b_eval_docs_set)");
-  *out = nullptr;
-  std::vector<QueryLine> lines;
-  std::vector<int32_t> ids;
-  std::vector<int64_t> offsets(1, 0);
-  std::vector<std::string> tok;
-  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
-    if (tok.empty()) continue;
-    QueryLine ln{joined(tok), std::string(), -1};
-    const size_t at = ids.size();
-    for (const std::string &w : tok) {
-      const int64_t row = w2b_eval_lookup(e, w.c_str());
-      if (row != e->words) ids.push_back((int32_t)row);
-    }
-    if (ids.size() == at) ln.error = "no word in vocabulary";
-    else if (ids.size() - at > W2B_EVAL_MAX_DOC) ln.error = "expected at most 1024 words";
-    if (ln.error.empty()) {
-      ln.q = (int64_t)offsets.size() - 1;
-      offsets.push_back((int64_t)ids.size());
-    } else {
-      ids.resize(at);
-    }
-    lines.push_back(ln);
-  }
-  const size_t nq = offsets.size() - 1;
-  std::vector<int32_t> best(nq * (size_t)k);
-  std::vector<float> bestd(nq * (size_t)k);
-  if (nq > 0) {
-    const int rc = w2b_eval_docs(e, (int64_t)ids.size(), ids.data(), (int64_t)nq, offsets.data(), symmetric, k, best.data(),
-                                 bestd.data(), nullptr);
-    if (rc != W2B_OK) return rc;
-  }
-  std::string txt;
-  for (const QueryLine &ln : lines) {
-    txt += ln.head;
-    if (!ln.error.empty()) {
-      txt += ": " + ln.error + "\n";
-      continue;
-    }
-    txt += ":\n";
-    for (int j = 0; j < k; j++) {
-      const int32_t d = best[(size_t)(ln.q * k + j)];
-      if (d < 0) break;
-      appendf(txt, "%d\t%lld\t%.6f\n", j + 1, (long long)d + 1, (double)bestd[(size_t)(ln.q * k + j)]);
-    }
-  }
-  return text_out(txt, who.c_str(), out, out_len);
-}
-
-namespace {
-// one pair line of w2b_eval_pairs_text: its fields as written, or its number when it is malformed
-struct PairLine {
-  bool malformed;
-  int64_t number, p;
-  std::string gold_text, a_text, b_text;
-  double gold;
-};
-
-// the blank-separated words of s, upper-cased
-std::vector<std::string> upper_words(const std::string &s) {
-  std::vector<std::string> tok;
-  for (size_t i = 0; i < s.size();) {
-    while (i < s.size() && is_space((unsigned char)s[i])) i++;
-    const size_t s0 = i;
-    while (i < s.size() && !is_space((unsigned char)s[i])) i++;
-    if (i > s0) {
-      tok.emplace_back(s, s0, i - s0);
-      upper_inplace(tok.back());
-    }
-  }
-  return tok;
-}
-
-std::string stripped(const std::string &s) {
-  size_t a = 0, b = s.size();
-  while (a < b && is_space((unsigned char)s[a])) a++;
-  while (b > a && is_space((unsigned char)s[b - 1])) b--;
-  return s.substr(a, b - a);
-}
-
-// the three fields of a pair line: the tab-separated parts when there is a tab, else the runs of non-blank characters
-std::vector<std::string> pair_fields(const std::string &line) {
-  std::vector<std::string> f;
-  if (line.find('\t') != std::string::npos) {
-    for (size_t i = 0;;) {
-      const size_t t = line.find('\t', i);
-      f.push_back(stripped(line.substr(i, t == std::string::npos ? t : t - i)));
-      if (t == std::string::npos) break;
-      i = t + 1;
-    }
-    return f;
-  }
-  for (size_t i = 0; i < line.size();) {
-    while (i < line.size() && is_space((unsigned char)line[i])) i++;
-    const size_t s0 = i;
-    while (i < line.size() && !is_space((unsigned char)line[i])) i++;
-    if (i > s0) f.emplace_back(line, s0, i - s0);
-  }
-  return f;
-}
-}  // namespace
-
-// the pair form: every pair line is A, B and a gold score; one batch, then the correlations of the scored pairs
-extern "C" int w2b_eval_pairs_text(w2b_eval *e, const char *pairs, int64_t len, int32_t details, char **out, int64_t *out_len) {
-  const std::string who = "w2b_eval_pairs_text";
-  if (!out || len < 0 || (len > 0 && !pairs)) return efail(W2B_EINVAL, who + ": bad argument");
-  if (!e) return efail(W2B_EINVAL, who + ": null handle");
-  if (!e->bits && !e->codes) return efail(W2B_EINVAL, who + ": not available on an fp32 handle: load the file with bits or codes");
-  *out = nullptr;
-  static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-  if (!c_locale) return efail(W2B_ENOMEM, who + ": no C locale");
-  std::vector<PairLine> lines;
-  std::vector<int32_t> ids;
-  std::vector<int64_t> offsets(1, 0);
-  int64_t looked = 0, oov = 0, malformed = 0, number = 0;
-  for (int64_t pos = 0; pos < len;) {
-    int64_t end = pos;
-    while (end < len && pairs[end] != '\n') end++;
-    std::string line(pairs + pos, (size_t)(end - pos));
-    pos = end + 1;
-    number++;
-    if (!line.empty() && line.back() == '\r') line.pop_back();
-    if (stripped(line).empty() || line[0] == '#') continue;
-    PairLine ln{true, number, -1, std::string(), std::string(), std::string(), 0.0};
-    const std::vector<std::string> f = pair_fields(line);
-    std::vector<std::string> wa, wb;
-    if (f.size() == 3 && !f[2].empty()) {
-      char *stop = nullptr;
-      ln.gold = strtod_l(f[2].c_str(), &stop, c_locale);
-      wa = upper_words(f[0]);
-      wb = upper_words(f[1]);
-      ln.malformed = stop != f[2].c_str() + f[2].size() || !std::isfinite(ln.gold) || wa.empty() || wb.empty() ||
-                     wa.size() > W2B_EVAL_MAX_BAG || wb.size() > W2B_EVAL_MAX_BAG;
-    }
-    if (ln.malformed) {
-      malformed++;
-    } else {
-      ln.a_text = f[0], ln.b_text = f[1], ln.gold_text = f[2];
-      ln.p = (int64_t)(offsets.size() - 1) / 2;
-      for (const std::vector<std::string> *side : {&wa, &wb}) {
-        for (const std::string &w : *side) {
-          const int64_t row = w2b_eval_lookup(e, w.c_str());
-          looked++;
-          if (row == e->words) oov++;
-          else ids.push_back((int32_t)row);
-        }
-        offsets.push_back((int64_t)ids.size());
-      }
-    }
-    lines.push_back(ln);
-  }
-  const int64_t np = (int64_t)(offsets.size() - 1) / 2;
-  std::vector<float> score((size_t)np);
-  std::vector<int64_t> parts((size_t)np * 3);
-  if (np > 0)
-    if (int rc = w2b_eval_pairs(e, (int64_t)ids.size(), ids.data(), np, offsets.data(), score.data(), parts.data())) return rc;
-  std::string txt;
-  std::vector<double> x, y;
-  int64_t skipped = 0;
-  for (const PairLine &ln : lines) {
-    if (ln.malformed) {
-      if (details) txt += "malformed line " + std::to_string(ln.number) + "\n";
-      continue;
-    }
-    const bool empty = parts[(size_t)(3 * ln.p + 1)] == 0 || parts[(size_t)(3 * ln.p + 2)] == 0;
-    if (empty) {
-      skipped++;
-      if (details) txt += "skipped";
-    } else {
-      x.push_back(ln.gold);
-      y.push_back((double)score[(size_t)ln.p]);
-      if (details) appendf(txt, "%.6f", (double)score[(size_t)ln.p]);
-    }
-    if (details) txt += "\t" + ln.gold_text + "\t" + ln.a_text + "\t" + ln.b_text + "\n";
-  }
-  double pearson = NAN, spearman = NAN;
-  if (int rc = w2b_rank_correlation((int64_t)x.size(), x.data(), y.data(), &pearson, &spearman)) return rc;
-  appendf(txt, "pairs: %lld scored, %lld skipped, %lld malformed\n", (long long)x.size(), (long long)skipped, (long long)malformed);
-  appendf(txt, "words: %lld looked up, %lld not in vocabulary\n", (long long)looked, (long long)oov);
-  for (const auto &c : {std::make_pair("pearson", pearson), std::make_pair("spearman", spearman)}) {
-    if (std::isnan(c.second)) txt += std::string(c.first) + ": nan\n";
-    else appendf(txt, "%s: %.6f\n", c.first, c.second);
-  }
-  return text_out(txt, who.c_str(), out, out_len);
-}
-
-extern "C" void w2b_eval_free_text(char *text) { free(text); }
-
 // ------------------------------------------------------------------------------------ word classes
-namespace {
-constexpr int64_t kClassesMaxWords = 5592405;                       // 3 * words < 2^24: (float)T is exact
-
-// what w2b_eval_classes and its host twin refuse: first what needs no table, then the table's shape, then `init`
-const char *bad_classes_args(int32_t n_classes, int32_t max_iters) {
-  if (n_classes < 1) return "n_classes must be at least 1";
-  if (max_iters < 0 || max_iters > 1000) return "max_iters must be 0..1000";
-  return nullptr;
-}
-const char *bad_classes_shape(int64_t words, int64_t size, int32_t n_classes) {
-  if (n_classes > W2B_EVAL_MAX_CLASSES || n_classes > words) return "n_classes must be at most min(words, 16384)";
-  if (words > kClassesMaxWords) return "words must be at most 5592405 (3 * words < 2^24)";
-  if ((unsigned __int128)9 * (unsigned __int128)words * (unsigned __int128)words * (unsigned __int128)size >=
-      ((unsigned __int128)1 << 63))
-    return "9 * words^2 * size must stay below 2^63";
-  return nullptr;
-}
-int64_t bad_classes_init(const int32_t *init, int64_t words, int32_t n_classes) {
-  if (init)
-    for (int64_t c = 0; c < words; c++)
-      if (init[c] < 0 || init[c] >= n_classes) return c;
-  return -1;
-}
-std::string classes_init_error(int64_t row) { return "init: row " + std::to_string(row) + ": class out of range"; }
-
-// wq_k of the header from N_k > 0: the expression of bag_weight
-inline float classes_weight(long long n) { return (float)(1.0 / sqrt((double)n)); }
-
-// The chains of one row against every class: Tf = (float)T transposed, [size][K]; t = the row's codes; acc [K].  Explicit
-// fmaf, strictly in column order per class.  The body is compiled twice, for a processor with FMA instructions (the
-// classes vectorise) and for any other one (a library call per step): the same correctly rounded operation either way.
-__attribute__((always_inline)) inline void classes_chains_body(const float *Tf, const int8_t *t, int64_t size, int32_t K,
-                                                               float *acc) {
-  for (int32_t k = 0; k < K; k++) acc[k] = 0.f;
-  for (int64_t a = 0; a < size; a++) {
-    const float ta = (float)t[a];
-    const float *row = Tf + a * K;
-    for (int32_t k = 0; k < K; k++) acc[k] = __builtin_fmaf(row[k], ta, acc[k]);
-  }
-}
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-__attribute__((target("avx2,fma"))) void classes_chains_fma(const float *Tf, const int8_t *t, int64_t size, int32_t K,
-                                                            float *acc) {
-  classes_chains_body(Tf, t, size, K, acc);
-}
-#endif
-void classes_chains_plain(const float *Tf, const int8_t *t, int64_t size, int32_t K, float *acc) {
-  classes_chains_body(Tf, t, size, K, acc);
-}
-
-// T [K][size] and counts [K] of the class array cl
-void classes_sums_host(const int8_t *t, int64_t words, int64_t size, int32_t K, const int32_t *cl, int32_t *T, int64_t *counts) {
-  std::fill(T, T + (size_t)K * (size_t)size, 0);
-  std::fill(counts, counts + K, (int64_t)0);
-  for (int64_t c = 0; c < words; c++) {
-    int32_t *Tk = T + (int64_t)cl[c] * size;
-    const int8_t *tc = t + c * size;
-    for (int64_t a = 0; a < size; a++) Tk[a] += tc[a];
-    counts[cl[c]]++;
-  }
-}
-}  // namespace
-
-// Host twin of the class kernels: the loop of the header, one step at a time (this file is built with -ffp-contract=off, and
-// the function says so again).
-extern "C" int w2b_classes_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int32_t n_classes,
-                                int32_t max_iters, const int32_t *init, int32_t *cls, float *score, int32_t *T_out,
-                                int64_t *counts, int32_t *iters_run, int64_t *moved) {
-#pragma clang fp contract(off)
-  const std::string who = "w2b_classes_host";
-  if (const char *why = bad_classes_args(n_classes, max_iters)) return efail(W2B_EINVAL, who + ": " + why);
-  if (!packed || !cls || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
-  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
-  if (const char *why = bad_classes_shape(words, dim, n_classes)) return efail(W2B_EINVAL, who + ": " + why);
-  const int64_t bad = bad_classes_init(init, words, n_classes);
-  if (bad >= 0) return efail(W2B_EINVAL, who + ": " + classes_init_error(bad));
-  const int32_t K = n_classes;
-  const int64_t wpr = (dim + 63) / 64 * bitlevel;
-  std::vector<int8_t> t((size_t)(words * dim));
-  for (int64_t c = 0; c < words; c++) {
-    const uint64_t *rc = packed + c * wpr;
-    for (int64_t a = 0; a < dim; a++) {
-      const uint64_t bit = 1ull << (a & 63);
-      int8_t v = 1;
-      if (bitlevel == 2 && (rc[2 * (a >> 6) + 1] & bit)) v = 3;
-      if (rc[bitlevel * (a >> 6)] & bit) v = (int8_t)-v;
-      t[(size_t)(c * dim + a)] = v;
-    }
-  }
-  std::vector<int32_t> cl((size_t)words), nw((size_t)words), T((size_t)K * (size_t)dim);
-  std::vector<float> sc((size_t)words, 0.f), Tf((size_t)K * (size_t)dim), wq((size_t)K), acc((size_t)K);
-  std::vector<int64_t> cnt((size_t)K);
-  std::vector<char> live((size_t)K);
-  for (int64_t c = 0; c < words; c++) cl[(size_t)c] = init ? init[c] : (int32_t)(c % K);
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-  const bool fma = __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
-#endif
-  int32_t it = 0;
-  int64_t mv = 0;
-  while (it < max_iters) {
-    classes_sums_host(t.data(), words, dim, K, cl.data(), T.data(), cnt.data());
-    for (int32_t k = 0; k < K; k++) {
-      long long n = 0;
-      for (int64_t a = 0; a < dim; a++) {
-        const long long v = T[(size_t)(k * dim + a)];
-        n += v * v;
-        Tf[(size_t)(a * K + k)] = (float)v;
-      }
-      live[(size_t)k] = n > 0;
-      wq[(size_t)k] = n > 0 ? classes_weight(n) : 0.f;
-    }
-    mv = 0;
-    for (int64_t c = 0; c < words; c++) {
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-      if (fma) classes_chains_fma(Tf.data(), t.data() + c * dim, dim, K, acc.data());
-      else
-#endif
-        classes_chains_plain(Tf.data(), t.data() + c * dim, dim, K, acc.data());
-      int32_t bk = -1;
-      float bd = 0.f;
-      for (int32_t k = 0; k < K; k++) {
-        if (!live[(size_t)k]) continue;
-        const float d = acc[(size_t)k] * wq[(size_t)k];
-        if (bk < 0 || d > bd) bk = k, bd = d;
-      }
-      if (bk < 0) bk = 0, bd = 0.f;
-      nw[(size_t)c] = bk;
-      sc[(size_t)c] = bd;
-      mv += bk != cl[(size_t)c];
-    }
-    cl.swap(nw);
-    it++;
-    if (mv == 0) break;
-  }
-  classes_sums_host(t.data(), words, dim, K, cl.data(), T.data(), cnt.data());
-  std::copy(cl.begin(), cl.end(), cls);
-  if (score) std::copy(sc.begin(), sc.end(), score);
-  if (T_out) std::copy(T.begin(), T.end(), T_out);
-  if (counts) std::copy(cnt.begin(), cnt.end(), counts);
-  if (iters_run) *iters_run = it;
-  if (moved) *moved = mv;
-  return W2B_OK;
-}
-
 namespace {
 // every device buffer of one w2b_eval_classes call, carved out of one allocation
 struct ClassesBuffers {
@@ -2910,23 +1590,4 @@ extern "C" int w2b_eval_classes_timing(w2b_eval *e, double *assign_ms, double *s
   if (assign_ms) *assign_ms = e->cls_assign_ms;
   if (sums_ms) *sums_ms = e->cls_sums_ms;
   return W2B_OK;
-}
-
-// word2vec's -classes file: one line "<word> <class>" per row, in row order
-extern "C" int w2b_eval_classes_text(w2b_eval *e, int32_t n_classes, int32_t max_iters, char **out, int64_t *out_len) {
-  const std::string who = "w2b_eval_classes_text";
-  if (const char *why = bad_classes_args(n_classes, max_iters)) return efail(W2B_EINVAL, who + ": " + why);
-  if (!e) return efail(W2B_EINVAL, who + ": null handle");
-  if (!out) return efail(W2B_EINVAL, who + ": bad argument");
-  std::vector<int32_t> cls((size_t)(e->words > 0 ? e->words : 1));
-  if (int rc = w2b_eval_classes(e, n_classes, max_iters, nullptr, cls.data(), nullptr, nullptr, nullptr, nullptr, nullptr))
-    return rc;
-  std::string txt;
-  for (int64_t c = 0; c < e->words; c++) {
-    txt += e->vocab.data() + c * kMaxW;
-    txt += ' ';
-    txt += std::to_string(cls[(size_t)c]);
-    txt += '\n';
-  }
-  return text_out(txt, who.c_str(), out, out_len);
 }

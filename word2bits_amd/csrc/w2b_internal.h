@@ -1,5 +1,6 @@
 // w2b_internal.h -- structures and launchers shared by the HIP kernels (w2b_kernels_*.hip) and the host side of the
-// C ABI (w2b_trainer.cpp, w2b_exchange.cpp, w2b_plan.cpp, w2b_eval.cpp, w2b_corpus.cpp).  Not part of the public interface (include/).
+// C ABI (w2b_trainer.cpp, w2b_exchange.cpp, w2b_plan.cpp, w2b_eval.cpp, w2b_embed.cpp).  Not part of the public interface (include/).
+// The host units that make no HIP call (w2b_corpus.cpp, w2b_eval_twins.cpp, w2b_eval_text.cpp) do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
