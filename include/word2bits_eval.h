@@ -571,6 +571,70 @@ int w2b_pairs_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t b
  * NULL input with n > 0. */
 int w2b_rank_correlation(int64_t n, const double *x, const double *y, double *pearson, double *spearman);
 
+/* ---- rank of a given row: its place in the complete answer list, on both packed modes --------------------------------------
+ * Every list question above returns at most W2B_EVAL_MAX_K rows.  This one asks where ONE given row stands, however far down:
+ * the position that mean reciprocal rank, hits@k, gensim's rank(w1, w2) and closer_than(w1, w2) (= rank - 1 rows) and a
+ * retrieval evaluation with one known correct row are made of.  It matters most on 1-bit models, whose integer scores tie in
+ * large blocks with the lowest row first: top-1 alone cannot tell "the answer was second" from "the answer was nowhere".
+ * bits and codes handles only, the additive rule (3CosAdd) only.
+ *
+ * For the question (b1, b2, b3) and the target row g, the COMPLETE LIST is what w2b_eval_topk would return if k were
+ * unbounded: the rows c other than b1, b2, b3 with score > 0 (bits: I(c) > 0), by score descending, equal scores in ascending
+ * row order.  The scores are those of the handle's mode: on a bits handle the exact integer I, on a codes handle the float32
+ * sequence ((p2 - p1) + p3) * w(c) of the codes section, bit for bit.
+ *     rank[q]   the 1-based place of g in that list, 0 when g is not in it (g is one of b1, b2, b3, or its score is not > 0).
+ *               For a ranked g:  rank = 1 + #{c not in {b1, b2, b3, g} : s(c) > s(g) or (s(c) == s(g) and c < g)}
+ *               (a row that beats a ranked g has a positive score automatically).
+ *     tied[q]   the number of OTHER rows of the list with exactly the target's score (equal I; equal float); 0 when rank is 0.
+ *               With it a caller turns the lowest-row convention into a mean rank over ties.  May be NULL.
+ *     score[q]  the score w2b_eval_topk reports for g: (float)I / (float)size on bits, the float on codes; 0 when rank is 0.
+ *               May be NULL.
+ * Three consequences:
+ *   - for k <= 64, 1 <= rank <= k exactly when w2b_eval_topk has g at best[q][rank - 1] with bestd == score bit for bit, and
+ *     rank == 0 or rank > k exactly when g is not in that list;
+ *   - one question asked with every row of the table as target gives each of 1..m exactly once, m the length of the complete
+ *     list, and 0 for the rest;
+ *   - inside a block of identical rows the ranks are consecutive in row order (the question's own rows left out of the run).
+ *
+ * Validation, in this order (as w2b_eval_cosmul): what needs no handle first -- nq < 0, or a NULL rank or input pointer with
+ * nq > 0, is W2B_EINVAL even with a NULL handle; nq == 0 is W2B_OK; then the handle (an fp32 handle is W2B_EINVAL "not
+ * available on an fp32 handle: load the file with bits or codes"); then the rows (a b1, b2, b3 or target outside [0, words) is
+ * W2B_EINVAL naming the question).  On any error no output is touched.  Handles made by *_from_trainer work like loaded ones.
+ *
+ * Scratch and timing: w2b_eval_set_topk_scratch bounds one launch (the questions' planes or operands plus 8 bytes of counters
+ * per question; a chunk is never smaller than 128 questions, and results never depend on the bound).  w2b_eval_timing_read
+ * counts one launch per chunk (target score and scan); macs is questions x rows x size on bits and three times that on codes.
+ *
+ * The kernels count, they do not select: word2bits_amd/csrc/w2b_kernels_evalbits.hip (k_bits_rank) and the RANK epilogue of
+ * k_codes_scan in w2b_kernels_evalcodes.hip; DESIGN.md 3.4d. */
+int w2b_eval_rank(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
+                  const int32_t *target, int32_t *rank, int32_t *tied /* or NULL */, float *score /* or NULL */);
+/* = w2b_eval_rank(rows, rows, rows, target): the place of target among the neighbours of rows[q] (gensim's rank) */
+int w2b_eval_neighbor_rank(w2b_eval *e, int64_t nq, const int32_t *rows, const int32_t *target, int32_t *rank, int32_t *tied,
+                           float *score);
+/* Host twin (pure C, no device) for one question on packed[words][bitlevel * ceil(dim / 64)], bitlevel 1 (bits) or 2 (codes),
+ * built on w2b_bits_scores_host / w2b_codes_scores_host.  tied and score may be NULL.  W2B_EINVAL for a bitlevel other than 1
+ * or 2 and for a row outside [0, words); on error nothing is written. */
+int w2b_rank_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t b1, int64_t b2, int64_t b3,
+                  int64_t target, int32_t *rank, int32_t *tied, float *score);
+/* The text form of `./nearest FILE k [bitlevel] [threshold] bits|codes rank`.  Every non-empty line is two words "A G" (the
+ * place of G among the neighbours of A) or four words "A B C G" (the place of G as the answer to A : B = C : ?); words are
+ * upper-cased and looked up as in w2b_eval_nearest_text.  The answer line is
+ * "<WORDS joined by one space>:\t<rank>\t<tied>\t<score %.6f>\n", with rank 0 "<WORDS>: no rank\n"; error lines are
+ * "<WORDS>: expected 2 or 4 words\n" and "<WORDS>: not in vocabulary: <WORD>\n" (the first such word).  All valid lines go
+ * through one w2b_eval_rank batch. */
+int w2b_eval_rank_text(w2b_eval *e, const char *queries, int64_t len, char **out, int64_t *out_len);
+/* `./compute_accuracy FILE <bitlevel> <threshold> bits|codes rank`: the bytes of w2b_eval_transcript (its lines come from
+ * the w2b_eval_top1 path as before, with the reference's comparison of words), and after every "Total accuracy: ..." line
+ *   "RANKS section: MRR <m>   hits@1 <d>   hits@5 <d>   hits@10 <d>   unranked <d>   (<d> questions)\n"
+ *   "RANKS total: MRR <m>   Semantic MRR <m>   Syntactic MRR <m>\n"
+ * The target of a question is w2b_eval_lookup(its fourth word); hits@n counts the questions with 1 <= rank <= n, unranked
+ * those with rank 0.  <m> is the sum in stream order, in double, of 1.0 / rank (rank 0 adds 0.0) divided by the double count
+ * of answered questions of that scope, printed %.4f; a scope without a question prints the three letters nan.  Removing the
+ * lines that begin with RANKS leaves w2b_eval_transcript's bytes; with a vocabulary of distinct words hits@1 equals the count
+ * of the ACCURACY TOP1 line. */
+int w2b_eval_transcript_rank(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,11 @@ SIGNATURES = {
     "w2b_eval_cosmul": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, C.c_int32, i32p, f32p]),
     "w2b_eval_cosmul_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.c_int32, C.POINTER(vp), i64p]),
     "w2b_eval_transcript_cosmul": (C.c_int, [vp, C.c_char_p, C.c_int64, C.POINTER(vp), i64p]),
+    "w2b_eval_rank": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, i32p, i32p, i32p, f32p]),
+    "w2b_eval_neighbor_rank": (C.c_int, [vp, C.c_int64, i32p, i32p, i32p, i32p, f32p]),
+    "w2b_rank_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p, i32p, f32p]),
+    "w2b_eval_rank_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.POINTER(vp), i64p]),
+    "w2b_eval_transcript_rank": (C.c_int, [vp, C.c_char_p, C.c_int64, C.POINTER(vp), i64p]),
     "w2b_cosmul_scores_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, f32p, f32p]),
     "w2b_eval_vectors": (C.c_int, [vp, C.c_int64, f32p, C.c_int32, C.c_int32, i32p, f32p]),
     "w2b_eval_vectors_text": (C.c_int, [vp, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(vp), i64p]),

@@ -8,7 +8,8 @@
 //                   a chunk of questions on the device, a Scan* struct sizes the chunk and launches one form of the scan
 //                   (fp32 rows: w2b_kernels_eval.hip; 1-bit rows: _evalbits; 2-bit rows: _evalcodes; and _evalcombine,
 //                   _evalbag, _evalvec, _evalcosmul for the questions of those names)
-//   the drivers     documents (_evaldocs), pairs (_evalpairs) and word classes (_evalclasses), which chunk by themselves
+//   the drivers     documents (_evaldocs), pairs (_evalpairs), word classes (_evalclasses) and the rank of a given row (the
+//                   count epilogues of _evalbits and _evalcodes), which chunk by themselves
 //   the setters     the scratch bound, the kernel variant, the timing read-outs
 // No arithmetic on scores happens here.  What the host does compute are question weights and tables, by the expressions
 // of w2b_eval_shared.h that the host twins use too: the bag question's and the classes' 1 / sqrt(N), the vector question's
@@ -86,6 +87,9 @@ struct w2b_eval {
   void *tk_buf = nullptr;
   size_t tk_bytes = 0;
   int64_t tk_budget = 0;                                // 0 = kTopkScratch
+  // w2b_eval_rank: per question of a chunk the two counters, their correction, the target's score and row (kRankBytes each)
+  void *rank_buf = nullptr;
+  int64_t rank_cap = 0;
 };
 
 static void eval_release(w2b_eval *e) {
@@ -106,6 +110,7 @@ static void eval_release(w2b_eval *e) {
   if (e->bag_T) (void)hipFree(e->bag_T);
   if (e->best) (void)hipFree(e->best);
   if (e->tk_buf) (void)hipFree(e->tk_buf);
+  if (e->rank_buf) (void)hipFree(e->rank_buf);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -1409,6 +1414,107 @@ extern "C" int w2b_eval_pairs(w2b_eval *e, int64_t n_ids, const int32_t *ids, in
   for (int64_t p = 0; p < np; p++) score[p] = pair_score(all[(size_t)(3 * p)], all[(size_t)(3 * p + 1)], all[(size_t)(3 * p + 2)]);
   if (parts) memcpy(parts, all.data(), all.size() * 8);
   return W2B_OK;
+}
+
+// ------------------------------------------------------------------------------------ rank of a given row
+// The place of a given row in the complete answer list (include/word2bits_eval.h, "rank of a given row"): the products of
+// the three-row scans with a count for an epilogue, so no selection state -- per question one 64-bit counter pair that the
+// scan adds to, what the question's own rows and the target itself added to it (the scan excludes nothing), and the
+// target's score.  A chunk is sized so that its planes or operands and its counters stay within the scratch bound, never
+// below 128 questions.  The results of all chunks are collected first: an error in a later chunk leaves the outputs untouched.
+namespace {
+constexpr int64_t kRankBytes = 32;   // device bytes per question: counters 8, correction 8, score 4, row 4, (bits) target acc and row 8
+}
+
+static int eval_rank(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, const int32_t *target,
+                     int32_t *rank, int32_t *tied, float *score, const std::string &who) {
+  if (nq < 0 || (nq > 0 && (!b1 || !b2 || !b3 || !target || !rank))) return efail(W2B_EINVAL, who + ": bad argument");
+  if (nq == 0) return W2B_OK;
+  if (!e) return efail(W2B_EINVAL, who + ": null handle");
+  if (!e->bits && !e->codes)
+    return efail(W2B_EINVAL, who + ": not available on an fp32 handle: load the file with bits or codes");
+  for (int64_t q = 0; q < nq; q++)
+    if (b1[q] < 0 || b1[q] >= e->words || b2[q] < 0 || b2[q] >= e->words || b3[q] < 0 || b3[q] >= e->words || target[q] < 0 ||
+        target[q] >= e->words)
+      return efail(W2B_EINVAL, who + ": question " + std::to_string(q) + ": row out of range");
+  EHIP(hipSetDevice(e->device));
+  const int64_t per_q = (e->bits ? e->wpr * 16 : (e->size + 31) / 32 * 96) + 8;     // planes / operands, and the counters
+  int64_t chunk = (e->tk_budget > 0 ? e->tk_budget : kTopkScratch) / per_q / 128 * 128;
+  if (chunk < 128) chunk = 128;
+  if (chunk > kChunkQ) chunk = kChunkQ;
+  std::vector<int32_t> r_rank((size_t)nq), r_tied((size_t)nq);
+  std::vector<float> r_score((size_t)nq);
+  std::vector<uint32_t> cnt, corr, ts;
+  const uint32_t *B32 = (const uint32_t *)e->B;
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int64_t n = (nq - q0 < chunk) ? nq - q0 : chunk;
+    const int64_t np = (n + kTile - 1) / kTile * kTile;
+    if (eval_reserve_questions(e, np) != W2B_OK) return efail(W2B_ENOMEM, who + ": device allocation failed");
+    if (np > e->rank_cap) {
+      if (e->rank_buf) (void)hipFree(e->rank_buf);
+      e->rank_buf = nullptr;
+      e->rank_cap = 0;
+      if (hipMalloc(&e->rank_buf, (size_t)(np * kRankBytes)) != hipSuccess) return efail(W2B_ENOMEM, who + ": device allocation failed");
+      e->rank_cap = np;
+    }
+    unsigned long long *d_cnt = (unsigned long long *)e->rank_buf;
+    uint32_t *d_corr = (uint32_t *)(d_cnt + np), *d_ts = d_corr + 2 * np, *d_tacc = d_ts + 2 * np;
+    int32_t *d_tgt = (int32_t *)(d_ts + np);
+    Rows3 in{b1, b2, b3};
+    if (int rc = in.upload(e, q0, n, np)) return rc;
+    EHIP(hipMemsetAsync(e->rank_buf, 0, (size_t)(np * kRankBytes), e->stream));
+    EHIP(hipMemcpyAsync(d_tgt, target + q0, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    EventPair ev;
+    EHIP(ev.create());
+    EHIP(hipEventRecord(ev.t[0], e->stream));
+    hipError_t le;
+    if (e->bits) {
+      le = w2b_launch_bits_planes(B32, (int)(2 * e->wpr), (int)e->size, (int)n, np, in.d1, in.d2, in.d3, e->P, e->stream);
+      if (le == hipSuccess)
+        le = w2b_launch_bits_rank(B32, (int)e->words, (int)e->size, e->P, np, (int)n, in.d1, in.d2, in.d3, d_tgt, d_cnt, d_corr,
+                                  (int *)d_ts, d_tacc, e->stream);
+    } else {
+      le = w2b_launch_codes_operands(B32, (int)e->size, (int)n, e->wrow, in.d1, in.d2, in.d3, e->P, e->Q, e->stream);
+      if (le == hipSuccess)
+        le = w2b_launch_codes_rank(B32, (int)e->words, (int)e->size, e->wrow, e->P, e->Q, (int)n, in.d1, in.d2, in.d3, d_tgt,
+                                   (float *)d_ts, d_corr, d_cnt, e->stream);
+    }
+    if (le == hipSuccess) le = hipEventRecord(ev.t[1], e->stream);
+    cnt.assign((size_t)(2 * n), 0u);
+    corr.assign((size_t)(2 * n), 0u);
+    ts.assign((size_t)n, 0u);
+    if (le == hipSuccess) le = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream);
+    if (le == hipSuccess) le = hipMemcpyAsync(corr.data(), d_corr, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream);
+    if (le == hipSuccess) le = hipMemcpyAsync(ts.data(), d_ts, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream);
+    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
+    float ms = 0;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, ev.t[0], ev.t[1]);
+    if (le != hipSuccess) return efail(W2B_EHIP, who + ": " + hipGetErrorString(le));
+    e->kernel_ms += ms;
+    e->launches++;
+    e->macs += (e->codes ? 3.0 : 1.0) * (double)n * (double)e->words * (double)e->size;
+    for (int64_t i = 0; i < n; i++) {
+      const uint32_t t = ts[(size_t)i];
+      const bool ranked = t != 0u;          // both score forms are > 0 for a ranked target
+      r_rank[(size_t)(q0 + i)] = ranked ? (int32_t)(1u + cnt[(size_t)(2 * i)] - corr[(size_t)(2 * i)]) : 0;
+      r_tied[(size_t)(q0 + i)] = ranked ? (int32_t)(cnt[(size_t)(2 * i + 1)] - corr[(size_t)(2 * i + 1)]) : 0;
+      r_score[(size_t)(q0 + i)] = !ranked ? 0.f : e->bits ? (float)(int32_t)t / (float)e->size : f32_score((unsigned long long)t << 32);
+    }
+  }
+  memcpy(rank, r_rank.data(), (size_t)nq * 4);
+  if (tied) memcpy(tied, r_tied.data(), (size_t)nq * 4);
+  if (score) memcpy(score, r_score.data(), (size_t)nq * 4);
+  return W2B_OK;
+}
+
+extern "C" int w2b_eval_rank(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,
+                             const int32_t *target, int32_t *rank, int32_t *tied, float *score) {
+  return eval_rank(e, nq, b1, b2, b3, target, rank, tied, score, "w2b_eval_rank");
+}
+
+extern "C" int w2b_eval_neighbor_rank(w2b_eval *e, int64_t nq, const int32_t *rows, const int32_t *target, int32_t *rank,
+                                      int32_t *tied, float *score) {
+  return eval_rank(e, nq, rows, rows, rows, target, rank, tied, score, "w2b_eval_neighbor_rank");
 }
 
 extern "C" int w2b_eval_top1(w2b_eval *e, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3,

@@ -36,6 +36,15 @@ __device__ __forceinline__ i32x4 codes_row_frag(const uint32_t *__restrict__ B, 
   return codes_unpack16((p[0] >> (16 * h)) & 0xFFFFu, (p[2] >> (16 * h)) & 0xFFFFu, vb);
 }
 
+// The additive score of a (question, row) pair from the three integers J_i (include/word2bits_eval.h, "codes mode"):
+//   p_i = (float)J_i * w(b_i),  score = ((p2 - p1) + p3) * w(c)
+// one rounding per operation.  The scan's epilogue and the one-lane-per-question kernel that scores a given row ahead of the
+// rank scan both call these two, so that the two floats of one pair are the same bits.
+__device__ __forceinline__ float codes_term(int j, float w) { return __fmul_rn((float)j, w); }
+__device__ __forceinline__ float codes_add_score(float p1, float p2, float p3, float wc) {
+  return __fmul_rn(__fadd_rn(__fsub_rn(p2, p1), p3), wc);
+}
+
 __device__ __forceinline__ unsigned long long codes_key(float d, int c) {
   return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
 }

@@ -2,7 +2,7 @@
 // transcript of the reference evaluator (ref src/compute-accuracy.c:114-187), and the *_text form of every other question.
 // Parsing and printing only.  The unit is written against the public header: a handle is an opaque pointer here, read
 // through w2b_eval_word / _words / _size / _is_bits / _is_codes / _docs_count / _lookup, and the GPU is reached through the
-// array entry points (w2b_eval_top1, _topk, _cosmul, _combine, _bag, _vectors, _docs_set, _docs, _pairs, _classes) alone.
+// array entry points (w2b_eval_top1, _topk, _cosmul, _rank, _combine, _bag, _vectors, _docs_set, _docs, _pairs, _classes) alone.
 // What it refuses in the words of those entry points comes from w2b_eval_shared.h.
 #include "w2b_eval_shared.h"
 
@@ -63,17 +63,30 @@ int text_out(const std::string &txt, const char *who, char **out, int64_t *out_l
 }
 }  // namespace
 
-// `answer(e, nq, b1, b2, b3, best)` scores all answerable questions at once: best[q] = the answer's row or -1
+namespace {
+// "<m>" of the RANKS lines: a mean of reciprocal ranks, or the letters nan for a scope without a question (a computed NaN
+// would print with the platform's sign)
+std::string mean_text(double sum, int n) {
+  if (n == 0) return "nan";
+  std::string t;
+  appendf(t, "%.4f", sum / (double)n);
+  return t;
+}
+}  // namespace
+
+// `answer(e, nq, b1, b2, b3, best)` scores all answerable questions at once: best[q] = the answer's row or -1.  `ranks`:
+// the RANKS lines of w2b_eval_transcript_rank after every "Total accuracy" line, from one w2b_eval_rank batch with each
+// question's expected word as the target.
 template <class Answer>
 static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len, const char *who,
-                           Answer answer) {
+                           Answer answer, bool ranks = false) {
   if (!e || !out || len < 0 || (len > 0 && !questions)) return efail(W2B_EINVAL, std::string(who) + ": bad argument");
   *out = nullptr;
   const int64_t words = w2b_eval_words(e);
   TokenIn in{questions, len};
   std::string st1, st2, st3, st4;
   std::vector<Step> steps;
-  std::vector<int32_t> b1s, b2s, b3s;
+  std::vector<int32_t> b1s, b2s, b3s, tgts;
   int QID = 0, TQ = 0, TQS = 0;
   // pass 1: parse the stream exactly like the scanf loop; collect the answerable questions
   for (;;) {
@@ -94,9 +107,11 @@ static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char
                   r3 = w2b_eval_lookup(e, st3.c_str());
     TQ++;
     if (r1 == words || r2 == words || r3 == words) continue;          // ref :149-151
-    if (w2b_eval_lookup(e, st4.c_str()) == words) continue;           // ref :152-153
+    const int64_t r4 = w2b_eval_lookup(e, st4.c_str());
+    if (r4 == words) continue;                                        // ref :152-153
     TQS++;
     steps.push_back({Step::Question, QID, st4, (int64_t)b1s.size()});
+    tgts.push_back((int32_t)r4);
     b1s.push_back((int32_t)r1);
     b2s.push_back((int32_t)r2);
     b3s.push_back((int32_t)r3);
@@ -107,9 +122,17 @@ static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char
     const int rc = answer(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), best.data());
     if (rc != W2B_OK) return rc;
   }
+  std::vector<int32_t> rank(b1s.size());
+  if (ranks && !b1s.empty()) {
+    const int rc = w2b_eval_rank(e, (int64_t)b1s.size(), b1s.data(), b2s.data(), b3s.data(), tgts.data(), rank.data(), nullptr, nullptr);
+    if (rc != W2B_OK) return rc;
+  }
   // pass 2: replay the counters and print (ref :120-131,178-187)
   std::string txt = "Starting eval...\n";
   int TCN = 0, CCN = 0, TACN = 0, CACN = 0, SECN = 0, SYCN = 0, SEAC = 0, SYAC = 0;
+  // RANKS: sums of 1 / rank in stream order and question counts, of the section, of all, semantic and syntactic questions
+  double rs_sec = 0, rs_all = 0, rs_sem = 0, rs_syn = 0;
+  int rn_sec = 0, rn_all = 0, rn_sem = 0, rn_syn = 0, hits1 = 0, hits5 = 0, hits10 = 0, unranked = 0;
   for (const Step &s : steps) {
     if (s.kind == Step::SectionEnd) {
       if (TCN == 0) TCN = 1;
@@ -117,12 +140,20 @@ static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char
         appendf(txt, "ACCURACY TOP1: %.2f %%  (%d / %d)\n", CCN / (float)TCN * 100, CCN, TCN);
         appendf(txt, "Total accuracy: %.2f %%   Semantic accuracy: %.2f %%   Syntactic accuracy: %.2f %% \n",
                 CACN / (float)TACN * 100, SEAC / (float)SECN * 100, SYAC / (float)SYCN * 100);
+        if (ranks) {
+          appendf(txt, "RANKS section: MRR %s   hits@1 %d   hits@5 %d   hits@10 %d   unranked %d   (%d questions)\n",
+                  mean_text(rs_sec, rn_sec).c_str(), hits1, hits5, hits10, unranked, rn_sec);
+          appendf(txt, "RANKS total: MRR %s   Semantic MRR %s   Syntactic MRR %s\n", mean_text(rs_all, rn_all).c_str(),
+                  mean_text(rs_sem, rn_sem).c_str(), mean_text(rs_syn, rn_syn).c_str());
+        }
       }
     } else if (s.kind == Step::SectionName) {
       txt += s.text;
       txt += ":\n";
       TCN = 0;
       CCN = 0;
+      rs_sec = 0;
+      rn_sec = hits1 = hits5 = hits10 = unranked = 0;
     } else {
       const int32_t c = best[(size_t)s.q];
       const char *bestw = c >= 0 ? w2b_eval_word(e, c) : "";
@@ -134,6 +165,14 @@ static int eval_transcript(w2b_eval *e, const char *questions, int64_t len, char
       if (s.qid <= 5) SECN++; else SYCN++;
       TCN++;
       TACN++;
+      if (ranks) {
+        const int32_t r = rank[(size_t)s.q];
+        const double rr = r > 0 ? 1.0 / (double)r : 0.0;
+        rs_sec += rr, rn_sec++;
+        rs_all += rr, rn_all++;
+        if (s.qid <= 5) rs_sem += rr, rn_sem++; else rs_syn += rr, rn_syn++;
+        hits1 += r == 1, hits5 += r >= 1 && r <= 5, hits10 += r >= 1 && r <= 10, unranked += r == 0;
+      }
     }
   }
   appendf(txt, "Questions seen / total: %d %d   %.2f %% \n", TQS, TQ, TQS / (float)TQ * 100);
@@ -152,6 +191,18 @@ extern "C" int w2b_eval_transcript_cosmul(w2b_eval *e, const char *questions, in
                          [](w2b_eval *ev, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t *best) {
                            return w2b_eval_cosmul(ev, nq, b1, b2, b3, 1, best, nullptr);
                          });
+}
+
+extern "C" int w2b_eval_transcript_rank(w2b_eval *e, const char *questions, int64_t len, char **out, int64_t *out_len) {
+  const char *who = "w2b_eval_transcript_rank";
+  if (!out || len < 0 || (len > 0 && !questions)) return efail(W2B_EINVAL, std::string(who) + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, std::string(who) + ": null handle");
+  if (!w2b_eval_is_bits(e) && !w2b_eval_is_codes(e)) return efail(W2B_EINVAL, std::string(who) + ": " + kDocsFp32);
+  return eval_transcript(e, questions, len, out, out_len, who,
+                         [](w2b_eval *ev, int64_t nq, const int32_t *b1, const int32_t *b2, const int32_t *b3, int32_t *best) {
+                           return w2b_eval_top1(ev, nq, b1, b2, b3, best, nullptr);
+                         },
+                         true);
 }
 
 // ------------------------------------------------------------------------------------ the forms that answer with lists
@@ -277,6 +328,55 @@ extern "C" int w2b_eval_cosmul_text(w2b_eval *e, const char *queries, int64_t le
       },
       [&](int64_t nq, int32_t *best, float *bestd) { return w2b_eval_cosmul(e, nq, b[0].data(), b[1].data(), b[2].data(), k, best, bestd); },
       true, out, out_len);
+}
+
+// the rank form: every non-empty line is "A G" (G among the neighbours of A) or "A B C G" (G as the answer to A : B = C : ?)
+extern "C" int w2b_eval_rank_text(w2b_eval *e, const char *queries, int64_t len, char **out, int64_t *out_len) {
+  const char *who = "w2b_eval_rank_text";
+  if (!out || len < 0 || (len > 0 && !queries)) return efail(W2B_EINVAL, std::string(who) + ": bad argument");
+  if (!e) return efail(W2B_EINVAL, std::string(who) + ": null handle");
+  if (!w2b_eval_is_bits(e) && !w2b_eval_is_codes(e)) return efail(W2B_EINVAL, std::string(who) + ": " + kDocsFp32);
+  *out = nullptr;
+  std::vector<QueryLine> lines;
+  std::vector<std::string> tok;
+  std::vector<int32_t> b[3], tgt;
+  for (int64_t pos = 0; next_query_line(queries, len, pos, tok);) {
+    if (tok.empty()) continue;
+    QueryLine ln{joined(tok), std::string(), -1};
+    if (tok.size() != 2 && tok.size() != 4) {
+      ln.error = "expected 2 or 4 words";
+    } else {
+      const std::string g = tok.back();
+      tok.pop_back();                                   // one or three words: the question's rows
+      three_rows(e, tok, b, ln);
+      if (ln.error.empty()) {
+        const int64_t r = w2b_eval_lookup(e, g.c_str());
+        if (r == w2b_eval_words(e)) {
+          ln.error = "not in vocabulary: " + g;
+          for (auto &v : b) v.pop_back();
+        } else {
+          tgt.push_back((int32_t)r);
+          ln.q = (int64_t)tgt.size() - 1;
+        }
+      }
+    }
+    lines.push_back(ln);
+  }
+  std::vector<int32_t> rank(tgt.size()), tied(tgt.size());
+  std::vector<float> score(tgt.size());
+  if (!tgt.empty()) {
+    const int rc = w2b_eval_rank(e, (int64_t)tgt.size(), b[0].data(), b[1].data(), b[2].data(), tgt.data(), rank.data(),
+                                 tied.data(), score.data());
+    if (rc != W2B_OK) return rc;
+  }
+  std::string txt;
+  for (const QueryLine &ln : lines) {
+    txt += ln.head;
+    if (!ln.error.empty()) txt += ": " + ln.error + "\n";
+    else if (rank[(size_t)ln.q] == 0) txt += ": no rank\n";
+    else appendf(txt, ":\t%d\t%d\t%.6f\n", rank[(size_t)ln.q], tied[(size_t)ln.q], (double)score[(size_t)ln.q]);
+  }
+  return text_out(txt, who, out, out_len);
 }
 
 // the signed form: +WORD, -WORD or WORD, 1 to W2B_EVAL_MAX_TERMS of them per line; a question always takes all the slots

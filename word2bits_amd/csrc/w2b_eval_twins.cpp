@@ -157,6 +157,47 @@ extern "C" int w2b_cosmul_scores_host(const uint64_t *packed, int64_t words, int
   return W2B_OK;
 }
 
+// Host twin of the rank question: the definition of the header on the scores of w2b_bits_scores_host / w2b_codes_scores_host,
+// one question.  Equal scores are equal integers on 1-bit rows and equal floats on 2-bit rows.
+extern "C" int w2b_rank_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t b1, int64_t b2,
+                             int64_t b3, int64_t target, int32_t *rank, int32_t *tied, float *score) {
+  const std::string who = "w2b_rank_host";
+  if (!packed || !rank || words < 0 || dim < 1) return efail(W2B_EINVAL, who + ": bad argument");
+  if (bitlevel != 1 && bitlevel != 2) return efail(W2B_EINVAL, who + ": bitlevel must be 1 or 2");
+  if (b1 < 0 || b2 < 0 || b3 < 0 || target < 0 || b1 >= words || b2 >= words || b3 >= words || target >= words)
+    return efail(W2B_EINVAL, who + ": row out of range");
+  std::vector<int32_t> I;
+  std::vector<float> S;
+  if (bitlevel == 1) {
+    I.resize((size_t)words);
+    if (int rc = w2b_bits_scores_host(packed, words, dim, b1, b2, b3, I.data())) return rc;
+  } else {
+    S.resize((size_t)words);
+    if (int rc = w2b_codes_scores_host(packed, words, dim, b1, b2, b3, nullptr, S.data())) return rc;
+  }
+  // -1 / 0 / +1: does row c stand behind / with / before a row of the target's score?
+  auto cmp = [&](int64_t c) {
+    if (bitlevel == 1) return I[(size_t)c] > I[(size_t)target] ? 1 : I[(size_t)c] == I[(size_t)target] ? 0 : -1;
+    return S[(size_t)c] > S[(size_t)target] ? 1 : S[(size_t)c] == S[(size_t)target] ? 0 : -1;
+  };
+  const bool own = target == b1 || target == b2 || target == b3;
+  const bool ranked = !own && (bitlevel == 1 ? I[(size_t)target] > 0 : S[(size_t)target] > 0.0f);
+  int32_t r = 0, t = 0;
+  if (ranked) {
+    r = 1;
+    for (int64_t c = 0; c < words; c++) {
+      if (c == b1 || c == b2 || c == b3 || c == target) continue;
+      const int k = cmp(c);
+      if (k > 0 || (k == 0 && c < target)) r++;
+      if (k == 0) t++;
+    }
+  }
+  *rank = r;
+  if (tied) *tied = t;
+  if (score) *score = !ranked ? 0.0f : bitlevel == 1 ? (float)I[(size_t)target] / (float)dim : S[(size_t)target];
+  return W2B_OK;
+}
+
 // Host twin of the bag kernels: T from the unpacked rows, J in 64 bits, the float steps of the header one at a time (this
 // file is built with -ffp-contract=off, and the function says so again).
 extern "C" int w2b_bag_scores_host(const uint64_t *packed, int64_t words, int64_t dim, int32_t bitlevel, int64_t n,

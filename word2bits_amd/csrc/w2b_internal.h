@@ -210,6 +210,18 @@ hipError_t w2b_launch_codes_scan_cosmul(const uint32_t *B, int words, int dim, c
 hipError_t w2b_launch_cosmul_bits(const uint32_t *B, int words, int dim, const float *utab, int nq, const int *b1,
                                   const int *b2, const int *b3, int k, int splits, int rows_per_split,
                                   unsigned long long *slots, unsigned long long *out, hipStream_t s);
+// The rank of a given row on bit-packed rows (include/word2bits_eval.h, "rank of a given row"): the arguments of the top-1
+// forms (P / T / Wq as w2b_launch_bits_planes / w2b_launch_codes_operands leave them) and the questions' target rows.  cnt
+// [nq] (ZEROED by the caller) receives (rows with exactly the target's score << 32 | rows that stand before the target),
+// counted over ALL rows; corr [nq][2] receives what the question's own rows and the target itself added to (before, equal),
+// tscore [nq] the target's score (1-bit rows: the integer I; 2-bit rows: the float), 0 when the target has no rank.  Each is
+// two launches: one lane per question for the target's score and corr, then the scan.
+hipError_t w2b_launch_bits_rank(const uint32_t *B, int words, int dim, const uint32_t *P, long long nqp, int nq,
+                                const int *b1, const int *b2, const int *b3, const int *target, unsigned long long *cnt,
+                                unsigned int *corr, int *tscore, unsigned int *tacc /* [nq][2] scratch */, hipStream_t s);
+hipError_t w2b_launch_codes_rank(const uint32_t *B, int words, int dim, const float *wrow, const void *T, const float *Wq,
+                                 int nq, const int *b1, const int *b2, const int *b3, const int *target, float *tscore,
+                                 unsigned int *corr, unsigned long long *cnt, hipStream_t s);
 // The bag question on bit-packed rows (w2b_kernels_evalbag.hip; include/word2bits_eval.h, "bag questions").  bitlevel 1: B =
 // the 1-bit rows (nw = 2 * ceil(dim / 64) halves), 2: the 2-bit rows and wrow as above.  ids / off = the chunk's bags, off
 // [nq + 1] rebased to ids[0]; T = the two digit planes of the pooled vectors in fragment order (w2b_bag_operand_bytes, ZEROED

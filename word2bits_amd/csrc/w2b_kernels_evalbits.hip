@@ -15,7 +15,8 @@
 // through the constant cache, and a lane needs no cross-lane step: it carries its own best (top-1) or its own list of
 // the k best (top-k, in LDS).  gridDim.y splits the rows so that the device is full; the partial results meet in a
 // 64-bit atomic max (top-1) or in k_bits_merge (top-k).  Rows are visited in ascending order and a later row has to be
-// strictly better, so equal scores resolve to the lowest row exactly as the answer list demands.
+// strictly better, so equal scores resolve to the lowest row exactly as the answer list demands.  The rank of a given row
+// (k_bits_rank) carries no best and no list: two counts per lane, met in an integer atomic add.
 // (BT1, BTK, bits_key and dispatch_nw: w2b_eval_bits.hpp, shared with the scan of signed sums.)
 #include "w2b_eval_bits.hpp"
 
@@ -37,6 +38,13 @@ __global__ void k_bits_planes(const uint32_t *__restrict__ B, int nw, int dim, i
   }
 }
 
+// a workgroup-uniform address, kept apart from the lane's offset so that a load takes it as its scalar base
+__device__ __forceinline__ const uint32_t *scalar_base(const uint32_t *u) {
+  const unsigned long long a = (unsigned long long)u;
+  return (const uint32_t *)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a));
+}
+
 // the planes of one lane: NW > 0 in registers, NW == 0 left in memory (any row length)
 template <int NW>
 struct Planes {
@@ -46,6 +54,9 @@ struct Planes {
   int nw;
   uint32_t n3;
 
+  // SBASE: every load as (uniform address of the half)[q], a scalar base and ONE 32-bit lane offset, instead of (P + q)[uniform
+  // offset], a pair of address registers per load in flight
+  template <bool SBASE = false>
   __device__ __forceinline__ void load(const uint32_t *__restrict__ P, long long nqp_, int nw_, int q) {
     p = P + q;
     nqp = nqp_;
@@ -54,8 +65,8 @@ struct Planes {
     if constexpr (NW > 0) {
 #pragma unroll
       for (int w = 0; w < NW; w++) {
-        sg[w] = p[(long long)w * nqp];
-        m3[w] = p[(long long)(NW + w) * nqp];
+        sg[w] = SBASE ? scalar_base(P + (long long)w * nqp)[(uint32_t)q] : p[(long long)w * nqp];
+        m3[w] = SBASE ? scalar_base(P + (long long)(NW + w) * nqp)[(uint32_t)q] : p[(long long)(NW + w) * nqp];
         n3 += __builtin_popcount(m3[w]);
       }
     } else {
@@ -108,6 +119,66 @@ k_bits_top1(const uint32_t *__restrict__ B, int words, int nw, int dim, const ui
     }
   }
   if (brow >= 0) atomicMax(&best[q], bits_key(c, bacc, brow));
+}
+
+// The place of a given row (include/word2bits_eval.h, "rank of a given row"): the shape of k_bits_top1 with a count for an
+// epilogue.  k_bits_rank_targets, one lane per question with the planes left in memory, runs first: acc of the target row
+// (a per-lane address: vector loads), whether the target ranks at all (I = c - 2 acc > 0 and not one of the question's
+// rows), and what the rows that the answer list leaves out -- the question's distinct rows and the target itself -- will
+// add to the two counts of the scan, which excludes nothing.  The scan's row loop is then acc and two counts: the rows that
+// stand before the target (a smaller acc, or the same acc and a lower row: acc < t + (row < g)) and the rows with exactly
+// its acc -- three compares and three adds with carry, no ballot, no branch, no LDS.
+// The row ranges' counts meet in one 64-bit integer add per lane (low half: before, high half: equal; neither overflows
+// 32 bits), so the sum cannot depend on the split.
+constexpr uint32_t kNoRank = 0xFFFFFFFFu;     // tacc of a target without a rank (an acc is at most 3 * dim)
+
+__global__ void __launch_bounds__(BT1)
+k_bits_rank_targets(const uint32_t *__restrict__ B, int nw, int dim, const uint32_t *__restrict__ P, long long nqp, int nq,
+                    const int *__restrict__ b1, const int *__restrict__ b2, const int *__restrict__ b3,
+                    const int *__restrict__ target, uint2 *__restrict__ tacc, uint2 *__restrict__ corr, int *__restrict__ tscore) {
+  const int q = blockIdx.x * BT1 + threadIdx.x;
+  if (q >= nq) return;
+  Planes<0> pl;
+  pl.load(P, nqp, nw, q);
+  const uint32_t c = (uint32_t)dim + 2 * pl.n3;
+  const int g = target[q];
+  const int own[3] = {b1[q], b2[q], b3[q]};
+  const uint32_t ta = pl.acc(B + (long long)g * nw);
+  const bool ranked = ta < ((c + 1) >> 1) && g != own[0] && g != own[1] && g != own[2];
+  uint32_t before = 0, equal = 1;                        // the target itself has its own acc
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    if ((i > 0 && own[i] == own[0]) || (i > 1 && own[i] == own[1])) continue;
+    const uint32_t a = pl.acc(B + (long long)own[i] * nw);
+    before += a < ta + (own[i] < g ? 1u : 0u) ? 1u : 0u;
+    equal += a == ta ? 1u : 0u;
+  }
+  tacc[q] = make_uint2(ranked ? ta : kNoRank, (uint32_t)g);
+  tscore[q] = ranked ? (int)(c - 2 * ta) : 0;
+  corr[q] = ranked ? make_uint2(before, equal) : make_uint2(0u, 0u);
+}
+
+template <int NW>
+__global__ void __launch_bounds__(BT1)
+k_bits_rank(const uint32_t *__restrict__ B, int words, int nw, const uint32_t *__restrict__ P, long long nqp, int nq,
+            const uint2 *__restrict__ tacc, int rpb, unsigned long long *__restrict__ cnt) {
+  const int q = blockIdx.x * BT1 + threadIdx.x;
+  if (q >= nq) return;
+  Planes<NW> pl;
+  pl.template load<true>(P, nqp, nw, q);
+  const uint2 tq = tacc[q];                // one load: (acc of the target, the target's row)
+  const uint32_t ta = tq.x;
+  const int g = (int)tq.y;
+  uint32_t before = 0, equal = 0;
+  const int r0 = blockIdx.y * rpb, r1 = min(words, r0 + rpb);
+  // (one row per trip like top-1: the loop vectoriser would interleave four over a second copy of the planes)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+  for (int r = r0; r < r1; r++) {
+    const uint32_t a = pl.acc(B + (long long)r * pl.nw);
+    before += a < ta + (r < g ? 1u : 0u) ? 1u : 0u;
+    equal += a == ta ? 1u : 0u;
+  }
+  if (ta != kNoRank && (before | equal) != 0u) atomicAdd(&cnt[q], ((unsigned long long)equal << 32) | before);
 }
 
 // Top-k: the lane's k best so far as (acc << 32 | row), unordered, in LDS; `wacc`/`wpos` follow the worst of them (the
@@ -217,6 +288,25 @@ hipError_t w2b_launch_bits_top1(const uint32_t *B, int words, int dim, const uin
   return dispatch_nw<kMaxNW>(nw, [&](auto n) {
     constexpr int NW = decltype(n)::value;
     hipLaunchKernelGGL((k_bits_top1<NW>), grid, dim3(BT1), 0, s, B, words, nw, dim, P, nqp, nq, b1, b2, b3, rpb, best);
+    return hipGetLastError();
+  });
+}
+
+hipError_t w2b_launch_bits_rank(const uint32_t *B, int words, int dim, const uint32_t *P, long long nqp, int nq,
+                                const int *b1, const int *b2, const int *b3, const int *target, unsigned long long *cnt,
+                                unsigned int *corr, int *tscore, unsigned int *tacc /* [nq][2] */, hipStream_t s) {
+  if (nq <= 0 || words <= 0) return hipSuccess;
+  const int nw = (dim + 63) / 64 * 2;
+  const unsigned qblocks = (unsigned)((nq + BT1 - 1) / BT1);
+  hipLaunchKernelGGL(k_bits_rank_targets, dim3(qblocks), dim3(BT1), 0, s, B, nw, dim, P, nqp, nq, b1, b2, b3, target, (uint2 *)tacc,
+                     (uint2 *)corr, tscore);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  int splits = 1, rpb = 1;
+  w2b_bits_layout(words, nq, 0, 0, &splits, &rpb);
+  const dim3 grid(qblocks, (unsigned)splits);
+  return dispatch_nw<kMaxNW>(nw, [&](auto n) {
+    constexpr int NW = decltype(n)::value;
+    hipLaunchKernelGGL((k_bits_rank<NW>), grid, dim3(BT1), 0, s, B, words, nw, P, nqp, nq, (const uint2 *)tacc, rpb, cnt);
     return hipGetLastError();
   });
 }

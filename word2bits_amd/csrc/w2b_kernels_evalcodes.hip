@@ -87,11 +87,27 @@ __global__ void k_codes_operands(const uint32_t *__restrict__ B, int nw, int dim
 // like every other one of theirs.)
 constexpr float kCosmulEps = 1e-6f;    // 0x358637BD
 
-template <int KS, int R, bool CHUNKED, bool TOPK, bool COSMUL = false>
+// RANK: the place of a given row (include/word2bits_eval.h, "rank of a given row"): the same three accumulator tiles and
+// the same float, compared with the question's target score and row instead of selected.  A lane counts the rows that
+// stand before the target and the rows with exactly its score in two registers over the workgroup's rows of one question
+// tile and adds them to the question's 64-bit counter once (low half: before, high half: equal).  Per score that is one
+// compare and one add (score >= target's); which of those tie with the target, and from which side, is worked out again
+// from the accumulators in the few tiles where a tie was seen.  Nothing is excluded
+// here: the question's own rows and the target itself are counted like any row, and k_codes_rank_targets has put what
+// they add into `corr`.  A row past the vocabulary scores 0 and a ranked target's score is > 0, so padding counts nothing.
+struct RankArgs {
+  const int *target;              // [nq]
+  const float *tscore;            // [nq] the target's score, 0 = the target has no rank
+  unsigned long long *cnt;        // [nq], zeroed
+};
+
+template <int KS, int R, bool CHUNKED, bool TOPK, bool COSMUL = false, bool RANK = false>
 __global__ void __launch_bounds__(CT, 1)
 k_codes_scan(const uint32_t *__restrict__ B, int nw, int words, const float *__restrict__ wrow, const i32x4 *__restrict__ T,
              const float *__restrict__ Wq, int ks, int nq, int qtiles, int qt_per_y, const int *__restrict__ b1,
-             const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ best, const TopkArgs tk) {
+             const int *__restrict__ b2, const int *__restrict__ b3, unsigned long long *__restrict__ best, const TopkArgs tk,
+             const RankArgs rk) {
+  static_assert(!RANK || (!TOPK && !COSMUL), "the rank epilogue belongs to the additive top-1 shape");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l32 = lane & 31, h = lane >> 5;
   const int tile0 = ((int)blockIdx.x * 4 + wave) * R, r0 = tile0 * CROWS;
   const int qt0 = (int)blockIdx.y * qt_per_y, qt1 = min(qtiles, qt0 + qt_per_y);
@@ -118,8 +134,16 @@ k_codes_scan(const uint32_t *__restrict__ B, int nw, int words, const float *__r
     const int q = qt * 32 + l32;
     const bool live = q < nq;
     const float w1 = Wq[q], w2 = Wq[nqp + q], w3 = Wq[2 * nqp + q];
-    const int e1 = live ? b1[q] : -1, e2 = live ? b2[q] : -1, e3 = live ? b3[q] : -1;
-    const unsigned long long seen = live ? ld_key(&best[q]) : ~0ull;     // possibly stale: then it is only lower
+    int e1 = -1, e2 = -1, e3 = -1, tg = 0;
+    unsigned long long seen = ~0ull;
+    float ts = 0.f;
+    if constexpr (RANK) {
+      ts = live ? rk.tscore[q] : 0.f;
+      tg = live ? rk.target[q] : 0;
+    } else {
+      e1 = live ? b1[q] : -1, e2 = live ? b2[q] : -1, e3 = live ? b3[q] : -1;
+      seen = live ? ld_key(&best[q]) : ~0ull;     // possibly stale: then it is only lower
+    }
 
     i32x16 acc[3][R];
 #pragma unroll
@@ -149,8 +173,11 @@ k_codes_scan(const uint32_t *__restrict__ B, int nw, int words, const float *__r
     }
 
     // Accumulator e of tile r in lane l: row r0 + 32 r + 8 (e / 4) + 4 (l / 32) + e % 4, question l % 32.
+    auto row_of = [&](int r, int e, int hh) { return r0 + r * CROWS + 8 * (e >> 2) + 4 * hh + (e & 3); };
     float d[R][16];
     float mr[R];
+    unsigned before = 0, equal = 0;                 // RANK: this lane's two counts of the question tile
+    bool tie = false;                               // RANK: one of this lane's rows has exactly the target's score
 #pragma unroll
     for (int r = 0; r < R; r++) {
       mr[r] = 0.f;
@@ -160,23 +187,51 @@ k_codes_scan(const uint32_t *__restrict__ B, int nw, int words, const float *__r
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int e = 4 * g + i;
-          const float p1 = __fmul_rn((float)acc[0][r][e], w1), p2 = __fmul_rn((float)acc[1][r][e], w2),
-                      p3 = __fmul_rn((float)acc[2][r][e], w3);
+          const float p1 = codes_term(acc[0][r][e], w1), p2 = codes_term(acc[1][r][e], w2), p3 = codes_term(acc[2][r][e], w3);
           if constexpr (COSMUL) {
             const float u1 = __fmul_rn(__fadd_rn(1.0f, __fmul_rn(p1, wc[i])), 0.5f),
                         u2 = __fmul_rn(__fadd_rn(1.0f, __fmul_rn(p2, wc[i])), 0.5f),
                         u3 = __fmul_rn(__fadd_rn(1.0f, __fmul_rn(p3, wc[i])), 0.5f);
             d[r][e] = __fdiv_rn(__fmul_rn(u2, u3), __fadd_rn(u1, kCosmulEps));
           } else {
-            d[r][e] = __fmul_rn(__fadd_rn(__fsub_rn(p2, p1), p3), wc[i]);
+            d[r][e] = codes_add_score(p1, p2, p3, wc[i]);
           }
-          mr[r] = __builtin_fmaxf(mr[r], d[r][e]);
+          if constexpr (RANK) {                     // counted as it is made: no score outlives its step
+            before += d[r][e] >= ts ? 1u : 0u;      // (the rows that tie with the target are sorted out below)
+            tie |= d[r][e] == ts;
+          } else {
+            mr[r] = __builtin_fmaxf(mr[r], d[r][e]);
+          }
         }
       }
     }
-    auto row_of = [&](int r, int e, int hh) { return r0 + r * CROWS + 8 * (e >> 2) + 4 * hh + (e & 3); };
 
-    if constexpr (!TOPK) {
+    if constexpr (RANK) {
+      if (!__any(ts > 0.f)) continue;
+      if (__any(tie && ts > 0.f)) {
+        // Rare: the tile that holds the target itself, and rows identical to it.  The scores again, from the accumulators:
+        // a row with the target's score counts as equal, and stands before the target only from a lower row.
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const int trel = tg - (r0 + r * CROWS + 4 * h);      // the target's row relative to this lane's first row of the tile
+#pragma unroll
+          for (int g = 0; g < 4; g++) {
+            const cf32x4 wc = *(const cf32x4 *)(wrow + r0 + r * CROWS + 8 * g + 4 * h);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+              const int e = 4 * g + i;
+              const float dd = codes_add_score(codes_term(acc[0][r][e], w1), codes_term(acc[1][r][e], w2),
+                                               codes_term(acc[2][r][e], w3), wc[i]);
+              equal += dd == ts ? 1u : 0u;
+              before -= (dd == ts && 8 * g + i >= trel) ? 1u : 0u;   // row_of(r, e, h) >= tg
+            }
+          }
+        }
+      }
+      before += __shfl_xor(before, 32, 64);
+      equal += __shfl_xor(equal, 32, 64);
+      if (h == 0 && ts > 0.f && (before | equal) != 0u) atomicAdd(&rk.cnt[q], ((unsigned long long)equal << 32) | before);
+    } else if constexpr (!TOPK) {
       // can any of this wavefront's scores still improve its question's key?  (equal scores: a lower row may)
       float m = mr[0];
 #pragma unroll
@@ -332,13 +387,13 @@ hipError_t codes_scan(const uint32_t *B, int words, int dim, const float *wrow, 
     const dim3 grid((unsigned)gx, (unsigned)gy);
     if constexpr (COSMUL)
       hipLaunchKernelGGL((k_codes_scan<KS, R, CH, true, true>), grid, dim3(CT), 0, s, B, nw, words, wrow, (const i32x4 *)T, Wq, ks,
-                         nq, qtiles, per_y, b1, b2, b3, best, tk);
+                         nq, qtiles, per_y, b1, b2, b3, best, tk, RankArgs{});
     else if (k > 0)
       hipLaunchKernelGGL((k_codes_scan<KS, R, CH, true>), grid, dim3(CT), 0, s, B, nw, words, wrow, (const i32x4 *)T, Wq, ks, nq,
-                         qtiles, per_y, b1, b2, b3, best, tk);
+                         qtiles, per_y, b1, b2, b3, best, tk, RankArgs{});
     else
       hipLaunchKernelGGL((k_codes_scan<KS, R, CH, false>), grid, dim3(CT), 0, s, B, nw, words, wrow, (const i32x4 *)T, Wq, ks, nq,
-                         qtiles, per_y, b1, b2, b3, best, tk);
+                         qtiles, per_y, b1, b2, b3, best, tk, RankArgs{});
     return hipGetLastError();
   });
   if (e != hipSuccess || k <= 0) return e;
@@ -360,4 +415,86 @@ hipError_t w2b_launch_codes_scan_cosmul(const uint32_t *B, int words, int dim, c
                                         unsigned char *cnt, unsigned long long *out, hipStream_t s) {
   if (k < 1) return hipErrorInvalidValue;
   return codes_scan<true>(B, words, dim, wrow, T, Wq, nq, b1, b2, b3, k, bound, bkt, keys, cnt, out, s);
+}
+
+// ---------------------------------------------------------------------------------------------- rank of a given row
+namespace {
+
+// J(x, c) = sum_a t_x[a] t_c[a] of two packed rows by popcounts on their 32-bit halves (the one-word path of the pair
+// question, w2b_kernels_evalpairs.hip): |t_x t_c| = 1 + 2 m_x + 2 m_c + 4 m_x m_c, its sign that of s_x ^ s_c.
+__device__ __forceinline__ int codes_dot(const uint32_t *__restrict__ x, const uint32_t *__restrict__ c, int nw, int dim) {
+  int j = 0;
+  for (int b = 0; 4 * b < nw; b++) {
+    const int cols = dim - 64 * b;                                    // >= 1
+    const uint32_t v[2] = {cols >= 32 ? ~0u : (1u << cols) - 1u, cols >= 64 ? ~0u : (cols <= 32 ? 0u : (1u << (cols - 32)) - 1u)};
+#pragma unroll
+    for (int hh = 0; hh < 2; hh++) {
+      const uint32_t s = x[4 * b + hh] ^ c[4 * b + hh], pos = ~s & v[hh], neg = s & v[hh];
+      const uint32_t mx = x[4 * b + 2 + hh], mc = c[4 * b + 2 + hh], mm = mx & mc;
+      j += (__builtin_popcount(pos) - __builtin_popcount(neg)) + 2 * (__builtin_popcount(pos & mx) - __builtin_popcount(neg & mx)) +
+           2 * (__builtin_popcount(pos & mc) - __builtin_popcount(neg & mc)) + 4 * (__builtin_popcount(pos & mm) - __builtin_popcount(neg & mm));
+    }
+  }
+  return j;
+}
+
+// One lane per question, ahead of the rank scan: the target's score by the scan's own float sequence (0 when the target is
+// one of the question's rows or its score is not > 0), and what the rows that the answer list leaves out -- the question's
+// distinct rows and the target itself -- add to the scan's two counts, which excludes nothing.
+__global__ void __launch_bounds__(256)
+k_codes_rank_targets(const uint32_t *__restrict__ B, int nw, int dim, int nq, const float *__restrict__ wrow,
+                     const int *__restrict__ b1, const int *__restrict__ b2, const int *__restrict__ b3,
+                     const int *__restrict__ target, float *__restrict__ tscore, uint2 *__restrict__ corr) {
+  const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (q >= nq) return;
+  const int e1 = b1[q], e2 = b2[q], e3 = b3[q], g = target[q];
+  const uint32_t *r1 = B + (long long)e1 * nw, *r2 = B + (long long)e2 * nw, *r3 = B + (long long)e3 * nw;
+  const float w1 = wrow[e1], w2 = wrow[e2], w3 = wrow[e3];
+  auto score = [&](int c) {
+    const uint32_t *rc = B + (long long)c * nw;
+    return codes_add_score(codes_term(codes_dot(r1, rc, nw, dim), w1), codes_term(codes_dot(r2, rc, nw, dim), w2),
+                           codes_term(codes_dot(r3, rc, nw, dim), w3), wrow[c]);
+  };
+  const float ts = score(g);
+  const bool ranked = g != e1 && g != e2 && g != e3 && ts > 0.f;
+  uint32_t before = 0, equal = 1;                        // the target itself has its own score
+  const int own[3] = {e1, e2, e3};
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    if ((i > 0 && own[i] == own[0]) || (i > 1 && own[i] == own[1])) continue;
+    const float so = score(own[i]);
+    equal += so == ts ? 1u : 0u;
+    before += (so > ts || (so == ts && own[i] < g)) ? 1u : 0u;
+  }
+  tscore[q] = ranked ? ts : 0.f;
+  corr[q] = ranked ? make_uint2(before, equal) : make_uint2(0u, 0u);
+}
+
+}  // namespace
+
+// The rank of a given row on 2-bit rows: T / Wq as w2b_launch_codes_operands leaves them; tscore [nq] and corr [nq] are
+// written here, cnt [nq] (zeroed by the caller) receives (rows with the target's score << 32 | rows before the target), own
+// rows and target included; corr holds their share of both.
+hipError_t w2b_launch_codes_rank(const uint32_t *B, int words, int dim, const float *wrow, const void *T, const float *Wq,
+                                 int nq, const int *b1, const int *b2, const int *b3, const int *target, float *tscore,
+                                 unsigned int *corr, unsigned long long *cnt, hipStream_t s) {
+  if (nq <= 0 || words <= 0) return hipSuccess;
+  const int ks = (dim + 31) / 32, nw = (dim + 63) / 64 * 4, qtiles = (nq + 31) / 32;
+  hipLaunchKernelGGL(k_codes_rank_targets, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, B, nw, dim, nq, wrow, b1, b2, b3,
+                     target, tscore, (uint2 *)corr);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const RankArgs rk{target, tscore, cnt};
+  return dispatch_ks(ks, [&](auto ksmax, auto tiles, auto chunked) {
+    constexpr int KS = decltype(ksmax)::value, R = decltype(tiles)::value;
+    constexpr bool CH = decltype(chunked)::value;
+    const int gx = (words + 4 * R * CROWS - 1) / (4 * R * CROWS);      // the grid of codes_scan
+    int gy = (1024 + gx - 1) / gx;
+    if (gy > qtiles) gy = qtiles;
+    const int per_y = (qtiles + gy - 1) / gy;
+    gy = (qtiles + per_y - 1) / per_y;
+    hipLaunchKernelGGL((k_codes_scan<KS, R, CH, false, false, true>), dim3((unsigned)gx, (unsigned)gy), dim3(CT), 0, s, B, nw, words,
+                       wrow, (const i32x4 *)T, Wq, ks, nq, qtiles, per_y, b1, b2, b3, (unsigned long long *)nullptr, TopkArgs{}, rk);
+    return hipGetLastError();
+  });
 }

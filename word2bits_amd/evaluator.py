@@ -9,6 +9,7 @@
     rows, scores = ev.bag([3, 17, 4, 9, 9], [0, 2, 5], 10)           # two bags of rows pooled: nearest to each sum
     rows, scores = ev.vectors(hidden, 10)                            # float vectors [nq, size] of one's own: nearest to each
     rows, scores = ev.cosmul(b1, b2, b3, 10)                         # analogies by the multiplicative rule 3CosMul
+    rank = ev.rank(b1, b2, b3, expected)                             # where the expected answer stands, however far down
     cls = ev.classes(500)                                            # word classes by k-means (word2vec's -classes)
     ev.set_docs(ids, offsets); docs, scores = ev.docs(qids, qoffsets, 10)   # corpus texts nearest to query texts (RWMD)
     cos = ev.pairs([3, 17, 4, 9, 9], [0, 1, 2, 3, 5])                # given pairs of words / bags: (3, 17) and ([4], [9, 9])
@@ -145,6 +146,36 @@ class Evaluator:
     def cosmul_text(self, queries, k):
         """stdout of `nearest FILE k ... bits|codes cosmul < queries` as bytes: every line is three words A B C."""
         return self._text(self._L.w2b_eval_cosmul_text, queries, int(k))
+
+    def rank(self, b1, b2, b3, target, details=False):
+        """The place of row target[q] in the complete answer list of the question (b1, b2, b3) (w2b_eval_rank; bits and codes
+        handles, the additive rule): 1-based, 0 when the target is one of the question's rows or its score is not > 0.
+        Returns int32 [nq], or with details=True (rank, tied, score): `tied` = other rows of the list with exactly the
+        target's score, `score` = what topk reports for the target (0 without a rank)."""
+        rows = [np.ascontiguousarray(x, np.int32).ravel() for x in (b1, b2, b3, target)]
+        if len({len(x) for x in rows}) != 1:
+            raise ValueError("b1, b2, b3 and target must have the same length")
+        return self._rank(self._L.w2b_eval_rank, rows, details)
+
+    def neighbor_rank(self, rows, target, details=False):
+        """The place of target[q] among the neighbours of rows[q] (gensim's rank; closer_than is rank - 1 rows):
+        rank(rows, rows, rows, target)."""
+        rows = [np.ascontiguousarray(x, np.int32).ravel() for x in (rows, target)]
+        if len(rows[0]) != len(rows[1]):
+            raise ValueError("rows and target must have the same length")
+        return self._rank(self._L.w2b_eval_neighbor_rank, rows, details)
+
+    def _rank(self, fn, rows, details):
+        n = len(rows[0])
+        rank, tied, score = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        p = lambda a: a.ctypes.data_as(_lib.i32p)
+        _lib.check(fn(self._h, n, *map(p, rows), p(rank), p(tied) if details else None,
+                      score.ctypes.data_as(_lib.f32p) if details else None))
+        return (rank, tied, score) if details else rank
+
+    def rank_text(self, queries):
+        """stdout of `nearest FILE k ... bits|codes rank < queries` as bytes: every line is two words A G or four A B C G."""
+        return self._text(self._L.w2b_eval_rank_text, queries)
 
     def neighbors(self, rows, k):
         """The k nearest rows of each row in `rows` (the row itself excluded): topk(rows, rows, rows, k)."""
@@ -331,10 +362,14 @@ class Evaluator:
 
     def transcript(self, questions, method="add"):
         """stdout of `compute_accuracy FILE bitlevel threshold < questions` as bytes.  method="cosmul" (bits and codes
-        handles) answers every question by 3CosMul instead: `compute_accuracy FILE ... bits|codes cosmul`."""
-        if method not in ("add", "cosmul"):
-            raise ValueError('method must be "add" or "cosmul"')
-        return self._text(self._L.w2b_eval_transcript_cosmul if method == "cosmul" else self._L.w2b_eval_transcript, questions)
+        handles) answers every question by 3CosMul instead: `compute_accuracy FILE ... bits|codes cosmul`.  method="rank"
+        (bits and codes handles) keeps the additive transcript and adds the lines that begin with RANKS (mean reciprocal
+        rank, hits@1 / 5 / 10, unranked) after every "Total accuracy" line: `compute_accuracy FILE ... bits|codes rank`."""
+        fns = {"add": self._L.w2b_eval_transcript, "cosmul": self._L.w2b_eval_transcript_cosmul,
+               "rank": self._L.w2b_eval_transcript_rank}
+        if method not in fns:
+            raise ValueError('method must be "add", "cosmul" or "rank"')
+        return self._text(fns[method], questions)
 
     def set_kernel(self, variant):
         """1 = f32 MFMA kernel (default), 0 = the same fused chain on the vector ALU (cross-check)"""
