@@ -1,11 +1,12 @@
 /*
  * word2bits_embed.h -- C ABI of the packed embedding layer: row lookup and bag pooling on the MI355X, straight from the
- * bit-packed table of a 1-bit or 2-bit model (the .w2bp layout of include/word2bits_corpus.h).
+ * bit-packed table of a 1-bit or 2-bit model (the .w2bp layout of include/word2bits_corpus.h), and the output projection
+ * (logits) of a batch of float vectors against the same packed rows.
  *
  * The consumer of a packed model that is not the evaluator: a downstream model asks for the rows of a batch of token ids,
  * or for their sum / mean per sentence ("bag").  The rows stay packed on the device, [rows][w2b_packed_words_per_row(dim,
  * bitlevel)] 64-bit words, 1/32 (1/16) of the float table; no float table is ever built, on either side.  The kernels are in
- * word2bits_amd/csrc/w2b_kernels_embed.hip, the host side in w2b_embed.cpp.
+ * word2bits_amd/csrc/w2b_kernels_embed.hip and w2b_kernels_embedproj.hip, the host side in w2b_embed.cpp.
  *
  * No CPU fallback: W2B_ENOGPU when no device is visible (the *_host functions below are the tests' twins of the kernels,
  * as w2b_bits_scores_host is for the bits kernels).  Error codes and w2b_last_error() are those of word2bits_hip.h.
@@ -51,9 +52,27 @@
  *   workgroup walking all its segments when the list of long bags is full), the result is the one above, bit for bit.
  *   Two consequences: with every weight 1.0f all partial sums are integers below 2^24, so sum / mean equal
  *   w2b_embed_bag bit for bit; scaling every weight by 2^s (staying in range) scales sum and mean exactly.
+ * Projection (w2b_embed_project*; the tied output layer, sampled-softmax scoring, re-ranking of a candidate list): the
+ *   other direction through the same table, logits[i][j] = x[i] . E[cand[j]].  Table, bitlevel, t_r[a] and q as for the bag.
+ *   Input: x is float32 [n][dim].  In the host form every value must be finite and either 0 or 2^-60 <= |x| <= 2^60, else
+ *   W2B_EINVAL naming the vector and the column: the rule of w2b_eval_vectors, for the same reason (every term and every
+ *   partial sum is then 0 or between 2^-83 and 2^86, nothing is subnormal and nothing overflows).
+ *   Candidates: cand is int32 [m], or NULL, which means every row in row order; m must then be rows.  A candidate id < 0
+ *   is padding: its output column is +0.0 throughout.  The same row may stand several times.  In the host form an id >=
+ *   rows is W2B_EINVAL.
+ *   Result, float32, for vector i and candidate j with row r = cand[j]:
+ *       S = +0;  for a = 0 .. dim - 1:  S = fmaf(x[i][a], (float)t_r[a], S)
+ *                   one fused multiply-add per column, strictly sequential in a, one accumulator per (vector, candidate):
+ *                   the chain of w2b_eval_vectors
+ *       out[i][j] = S * q                                          ONE float32 multiply, rounded on its own
+ *   Output: dense [n][m] without padding; BF16 / F16 are that float32 result rounded to nearest even.
+ *   Three consequences: with x = the unit vector of column a, out[.][j] is the value lookup(cand[j])[a] bit for bit (1 * q
+ *   and 3 * 0.25 are exact); S equals the S_out of w2b_vector_scores_host for the same row and vector bit for bit; scaling
+ *   every x by 2^s (staying in range) scales every output exactly.
  *
  * ---- out of scope --------------------------------------------------------------------------------------------------
- * Gradients or training through the lookup (the table is read-only); bitlevels other than 1 and 2; a handle built from
+ * Gradients or training through the lookup (the table is read-only); gradients with respect to x through the projection
+ * (a product over the rows, which needs an order contract of its own); bitlevels other than 1 and 2; a handle built from
  * a live trainer (w2b_export_packed + w2b_embed_create does it in two calls); float input files.
  */
 #ifndef WORD2BITS_EMBED_H
@@ -134,6 +153,29 @@ int w2b_embed_bag_weighted(w2b_embed *e, int64_t n_ids, const int32_t *ids, cons
 int w2b_embed_reserve_weights(w2b_embed *e, int64_t max_ids, void **weights_dev);   /* float[max_ids] */
 int w2b_embed_bag_weighted_device(w2b_embed *e, int64_t n_ids, int64_t n_bags, int32_t mode, int32_t dtype);
 
+/* Projection, the semantics above.  Host form: validated before anything is launched, in this order: what needs no handle
+ * (n or m negative or beyond 2^24 vectors / 0x7FFFFF00 candidates, dtype, x == NULL with n > 0, out == NULL with n > 0 and
+ * m > 0), then the handle, then the candidates (cand == NULL with m != rows; the first id >= rows), then the first refused
+ * value of x; each is W2B_EINVAL with its cause in w2b_last_error(), and `out` is untouched.  n == 0 or m == 0 is W2B_OK.
+ * out is [n][m] of float (F32) or uint16_t patterns (BF16, F16).  Large calls run in chunks of whole vectors x whole
+ * candidate ranges, about 64 MiB of output per launch; the result does not depend on the chunking.
+ * Device form: w2b_embed_reserve_project hands out x_dev = float[max_n][dim], cand_dev = int64[max_m] and out_dev =
+ * [max_n][max_m] of `dtype`, buffers of their own beside those of w2b_embed_reserve and w2b_embed_reserve_weights: a pointer
+ * goes stale only when that buffer itself grows (a call that asks for no more than is there returns the same pointers).
+ * The caller fills x_dev (and cand_dev), launches, and reads out_dev -- dense [n][m] for the n and m of the call -- after
+ * w2b_embed_synchronize.  use_cand = 0 means all rows: m must be rows, so max_m must have been >= rows.  W2B_EINVAL when
+ * n, m or dtype exceed what was reserved.  No content of the staging makes a kernel read or write outside its buffers: a
+ * candidate >= rows gives a +0.0 column and is counted once in w2b_embed_bad_ids.  The values of x are NOT checked there:
+ * what a NaN, an infinity or a value outside 2^-60 .. 2^60 produces is simply what the chain produces on the device.
+ * w2b_embed_timing_read counts one launch per call (per chunk of the host form); its bytes are n x dim x 4 for x, m x words
+ * per row x 8 for the rows (read once per launch), 8 per candidate id when candidates are given, and the output bytes. */
+int w2b_embed_project(w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand /* or NULL */,
+                      int32_t dtype, void *out);
+int w2b_embed_reserve_project(w2b_embed *e, int64_t max_n, int64_t max_m, int32_t dtype,
+                              void **x_dev /* float[max_n][dim] */, void **cand_dev /* int64[max_m] */,
+                              void **out_dev /* [max_n][max_m] of dtype */);
+int w2b_embed_project_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t dtype);
+
 /* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form. */
 int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                           int64_t n, const int32_t *ids, float *out);
@@ -143,6 +185,9 @@ int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_
 int w2b_embed_bag_weighted_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                                 int64_t n_ids, const int32_t *ids, const float *weights,
                                 int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
+/* the projection: explicit fmaf per column, then the one multiply (w2b_embed_twins.cpp, a host-only unit) */
+int w2b_embed_project_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
+                           const float *x, int64_t m, const int32_t *cand, float *out);
 
 #ifdef __cplusplus
 }

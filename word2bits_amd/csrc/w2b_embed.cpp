@@ -1,11 +1,14 @@
 // w2b_embed.cpp -- host side of include/word2bits_embed.h: the handle, the .w2bp loader, validation, the device staging
 // (one set of buffers handed to the caller by w2b_embed_reserve, a separate bounded one for the host form), the chunking
-// of host-form calls (weighted bags stage their weights beside the ids), timing, and the host twins of the kernels in w2b_kernels_embed.hip.  The table stays packed on the
+// of host-form calls (weighted bags stage their weights beside the ids), timing, and the host twins of the kernels in w2b_kernels_embed.hip.
+// The projection (w2b_kernels_embedproj.hip) has staging of its own in both forms; its twin is in the host-only w2b_embed_twins.cpp and
+// what both must refuse in w2b_embed_shared.h.  The table stays packed on the
 // device; no float table exists on either side and there is no CPU fallback (the *_host twins are for tests).
 #include "../../include/word2bits_embed.h"
 #include "../../include/word2bits_corpus.h"
 #include "../../include/word2bits_hip.h"
 #include "w2b_internal.h"
+#include "w2b_embed_shared.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,6 +42,13 @@ struct Staging {
   void *wscratch = nullptr;
   int64_t cap_weights = 0, wscratch_bytes = 0;
 };
+// device staging of one form of the projection: buffers of their own, each of which only moves when it grows itself
+struct ProjStaging {
+  float *x = nullptr;                        // [cap_n][dim]
+  long long *cand = nullptr;                 // [cap_m]
+  void *out = nullptr, *operands = nullptr;  // [n][m] of a dtype; the vectors in fragment order (for cap_n vectors)
+  int64_t cap_n = 0, cap_m = 0, out_bytes = 0, operand_bytes = 0;
+};
 struct Pending { hipEvent_t a, b; };
 }  // namespace
 
@@ -53,6 +63,7 @@ struct w2b_embed {
   uint64_t *T = nullptr;                     // [rows][wpr], the file's layout
   unsigned long long *bad = nullptr;         // device counter
   Staging user, host;
+  ProjStaging puser, phost;
   std::vector<Pending> pending;
   double kernel_ms = 0, bytes = 0;
   int64_t launches = 0;
@@ -69,6 +80,14 @@ void free_staging(Staging &s) {
   s = Staging();
 }
 
+void free_project(ProjStaging &s) {
+  if (s.x) (void)hipFree(s.x);
+  if (s.cand) (void)hipFree(s.cand);
+  if (s.out) (void)hipFree(s.out);
+  if (s.operands) (void)hipFree(s.operands);
+  s = ProjStaging();
+}
+
 void embed_release(w2b_embed *e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
@@ -76,6 +95,8 @@ void embed_release(w2b_embed *e) {
   for (Pending &p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   free_staging(e->user);
   free_staging(e->host);
+  free_project(e->puser);
+  free_project(e->phost);
   if (e->T) (void)hipFree(e->T);
   if (e->bad) (void)hipFree(e->bad);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -205,6 +226,21 @@ int ensure_weighted(w2b_embed *e, Staging &s, int64_t max_ids, int64_t n_ids, in
   return W2B_OK;
 }
 
+// the projection's buffers for max_n vectors, max_m candidates and out_bytes of output; only ever grow, each on its own
+int ensure_project(w2b_embed *e, ProjStaging &s, int64_t max_n, int64_t max_m, int64_t out_bytes) {
+  if (max_n > s.cap_n || !s.x)
+    if (int rc = grow(e, s.x, s.cap_n, max_n * e->dim * 4, max_n)) return rc;
+  const int64_t need = (int64_t)w2b_embed_project_operand_bytes((int)e->dim, s.cap_n);
+  if (need > s.operand_bytes || !s.operands)
+    if (int rc = grow(e, s.operands, s.operand_bytes, need, need)) return rc;
+  if (max_m > s.cap_m || !s.cand)
+    if (int rc = grow(e, s.cand, s.cap_m, max_m * 8, max_m)) return rc;
+  out_bytes = (out_bytes + 15) / 16 * 16;
+  if (out_bytes > s.out_bytes || !s.out)
+    if (int rc = grow(e, s.out, s.out_bytes, out_bytes, out_bytes)) return rc;
+  return W2B_OK;
+}
+
 int fold_pending(w2b_embed *e) {
   EHIP(hipStreamSynchronize(e->stream));
   for (Pending &p : e->pending) {
@@ -261,6 +297,16 @@ int launch_bag_weighted(w2b_embed *e, Staging &s, int64_t n_ids, int64_t n_bags,
   return timed(e, bytes, [&] {
     return w2b_launch_embed_bag_weighted(e->T, e->rows, (int)e->dim, e->bitlevel, s.ids, s.weights, n_ids, s.offsets, n_bags,
                                          mode, dtype, s.out, e->bad, s.wscratch, e->stream);
+  });
+}
+
+// n vectors against m candidates: those of s.cand, or the rows cand_base .. cand_base + m when !use_cand
+int launch_project(w2b_embed *e, ProjStaging &s, int64_t n, int64_t m, bool use_cand, int64_t cand_base, int32_t dtype) {
+  const double bytes = (double)n * (double)e->dim * 4 + (double)m * (double)e->wpr * 8 + (use_cand ? (double)m * 8 : 0.0) +
+                       (double)n * (double)m * elem_size(dtype);
+  return timed(e, bytes, [&] {
+    return w2b_launch_embed_project(e->T, e->rows, (int)e->dim, e->bitlevel, s.x, (int)n, use_cand ? s.cand : nullptr, cand_base,
+                                    (int)m, dtype, s.operands, s.out, e->bad, e->stream);
   });
 }
 }  // namespace
@@ -421,7 +467,81 @@ extern "C" int w2b_embed_bag_weighted(w2b_embed *e, int64_t n_ids, const int32_t
   return W2B_OK;
 }
 
+extern "C" int w2b_embed_project(w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand, int32_t dtype,
+                                 void *out) {
+  const char *who = "w2b_embed_project";
+  const int es = elem_size(dtype);
+  if (int rc = project_check_args(who, n, x, m, es != 0, out)) return rc;
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_project: null handle");
+  if (int rc = project_check_cand(who, e->rows, m, cand)) return rc;
+  if (int rc = project_check_values(who, n, e->dim, x)) return rc;
+  if (n == 0 || m == 0) return W2B_OK;
+  EHIP(hipSetDevice(e->device));
+  // whole vectors x whole candidate ranges, about kHostOutBytes of output per launch
+  const int64_t nv = n < 4096 ? n : 4096;
+  int64_t cm = kHostOutBytes / (es * nv);
+  if (cm > kHostIds) cm = kHostIds;
+  if (cm >= 64) cm = cm / 64 * 64;
+  cm = cm < 1 ? 1 : (cm > m ? m : cm);
+  std::vector<long long> wide;
+  std::vector<char> part;
+  for (int64_t i0 = 0; i0 < n; i0 += nv) {
+    const int64_t ci = n - i0 < nv ? n - i0 : nv;
+    if (int rc = ensure_project(e, e->phost, nv, cm, nv * cm * es)) return rc;
+    EHIP(hipMemcpyAsync(e->phost.x, x + i0 * e->dim, (size_t)(ci * e->dim) * 4, hipMemcpyHostToDevice, e->stream));
+    for (int64_t j0 = 0; j0 < m; j0 += cm) {
+      const int64_t cj = m - j0 < cm ? m - j0 : cm;
+      if (cand) {
+        wide.assign(cand + j0, cand + j0 + cj);
+        EHIP(hipMemcpyAsync(e->phost.cand, wide.data(), (size_t)cj * 8, hipMemcpyHostToDevice, e->stream));
+      }
+      if (int rc = launch_project(e, e->phost, ci, cj, cand != nullptr, j0, dtype)) return rc;
+      if (cj == m) {                                       // the chunk's rows are the caller's rows
+        EHIP(hipMemcpyAsync((char *)out + i0 * m * es, e->phost.out, (size_t)(ci * m * es), hipMemcpyDeviceToHost, e->stream));
+        EHIP(hipStreamSynchronize(e->stream));
+      } else {                                             // a range of columns: through host memory, row by row
+        part.resize((size_t)(ci * cj * es));
+        EHIP(hipMemcpyAsync(part.data(), e->phost.out, part.size(), hipMemcpyDeviceToHost, e->stream));
+        EHIP(hipStreamSynchronize(e->stream));
+        for (int64_t i = 0; i < ci; i++)
+          memcpy((char *)out + ((i0 + i) * m + j0) * es, part.data() + i * cj * es, (size_t)(cj * es));
+      }
+    }
+  }
+  return W2B_OK;
+}
+
 // ------------------------------------------------------------------------------------ device form
+extern "C" int w2b_embed_reserve_project(w2b_embed *e, int64_t max_n, int64_t max_m, int32_t dtype, void **x_dev,
+                                         void **cand_dev, void **out_dev) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_project: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_reserve_project: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (max_n < 0 || max_n > kProjectMaxVectors || max_m < 0 || max_m > 0x7FFFFF00ll || max_n * max_m > (1ll << 40))
+    return efail(W2B_EINVAL, "w2b_embed_reserve_project: bad sizes");
+  EHIP(hipSetDevice(e->device));
+  if (int rc = ensure_project(e, e->puser, max_n, max_m, max_n * max_m * es)) return rc;
+  if (x_dev) *x_dev = e->puser.x;
+  if (cand_dev) *cand_dev = e->puser.cand;
+  if (out_dev) *out_dev = e->puser.out;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_project_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t dtype) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_project_device: null handle");
+  const int es = elem_size(dtype);
+  if (!es) return efail(W2B_EINVAL, "w2b_embed_project_device: dtype is none of W2B_EMBED_F32 / BF16 / F16");
+  if (n < 0 || m < 0) return efail(W2B_EINVAL, "w2b_embed_project_device: negative count");
+  if (use_cand != 0 && use_cand != 1) return efail(W2B_EINVAL, "w2b_embed_project_device: use_cand must be 0 or 1");
+  if (n == 0 || m == 0) return W2B_OK;
+  const ProjStaging &s = e->puser;
+  if (!s.x || !s.cand || !s.out || n > s.cap_n || m > s.cap_m || n * m * es > s.out_bytes)
+    return efail(W2B_EINVAL, "w2b_embed_project_device: more than w2b_embed_reserve_project has set aside");
+  if (!use_cand && m != e->rows) return efail(W2B_EINVAL, "w2b_embed_project_device: without candidates m must be rows");
+  EHIP(hipSetDevice(e->device));
+  return launch_project(e, e->puser, n, m, use_cand != 0, 0, dtype);
+}
+
 extern "C" int w2b_embed_reserve(w2b_embed *e, int64_t max_ids, int64_t max_bags, int32_t dtype, void **ids_dev,
                                  void **offsets_dev, void **out_dev) {
   if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve: null handle");

@@ -1,0 +1,52 @@
+// w2b_embed_twins.cpp -- the host twin of the packed embedding's projection kernel (include/word2bits_embed.h,
+// "Projection"): what every GPU test of w2b_embed_project compares the kernel against.  It restates the header's definition
+// on the packed rows themselves, one fused multiply-add per column.  No handle, no stream and no device call: the unit
+// includes no device header, and a program that links nothing but this file and a w2b_internal_fail of its own can run it
+// under a host sanitizer (tests/host/embed_project_twin_main.cpp, `make host-check`).  What it refuses comes from
+// w2b_embed_shared.h, as for the host form.  (The twins of lookup and bags are in w2b_embed.cpp.)
+#include "w2b_embed_shared.h"
+
+#include <cmath>
+#include <vector>
+
+// S = +0; S = fmaf(x[i][a], (float)t_r[a], S) for a = 0 .. dim - 1; out[i][j] = S * q.  The multiply is one float32 operation:
+// this file is built with -ffp-contract=off and the function says so again.
+extern "C" int w2b_embed_project_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
+                                      const float *x, int64_t m, const int32_t *cand, float *out) {
+#pragma clang fp contract(off)
+  const char *who = "w2b_embed_project_host";
+  if (int rc = project_check_args(who, n, x, m, true, out)) return rc;
+  if (!packed) return w2b_internal_fail(W2B_EINVAL, "w2b_embed_project_host: null table");
+  if (rows < 0 || rows > 0x7FFFFF00ll || dim < 1 || dim > (1 << 24))
+    return w2b_internal_fail(W2B_EINVAL, "w2b_embed_project_host: unsupported rows / dim");
+  if (bitlevel != 1 && bitlevel != 2) return w2b_internal_fail(W2B_EUNSUPPORTED, "w2b_embed_project_host: bitlevel must be 1 or 2");
+  if (int rc = project_check_cand(who, rows, m, cand)) return rc;
+  if (int rc = project_check_values(who, n, dim, x)) return rc;
+  if (n == 0 || m == 0) return W2B_OK;
+  const int64_t wpr = (dim + 63) / 64 * bitlevel;
+  uint32_t qbits = bitlevel == 1 ? 0x3EAAAAABu : 0x3E800000u;
+  float q;
+  memcpy(&q, &qbits, 4);
+  std::vector<float> t((size_t)dim);
+  for (int64_t j = 0; j < m; j++) {
+    const int64_t r = cand ? (int64_t)cand[j] : j;
+    if (r < 0) {                                             // padding: a column of +0.0
+      for (int64_t i = 0; i < n; i++) out[i * m + j] = 0.f;
+      continue;
+    }
+    const uint64_t *row = packed + r * wpr;
+    for (int64_t a = 0; a < dim; a++) {
+      const uint64_t *blk = row + (a >> 6) * bitlevel;
+      const int sg = (int)((blk[0] >> (a & 63)) & 1u);
+      const int mag = bitlevel == 2 && ((blk[1] >> (a & 63)) & 1u) ? 3 : 1;
+      t[(size_t)a] = (float)(sg ? -mag : mag);
+    }
+    for (int64_t i = 0; i < n; i++) {
+      const float *xi = x + i * dim;
+      float S = 0.f;
+      for (int64_t a = 0; a < dim; a++) S = fmaf(xi[a], t[(size_t)a], S);      // strictly sequential, one accumulator
+      out[i * m + j] = S * q;
+    }
+  }
+  return W2B_OK;
+}

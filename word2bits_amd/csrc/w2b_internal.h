@@ -1,6 +1,6 @@
 // w2b_internal.h -- structures and launchers shared by the HIP kernels (w2b_kernels_*.hip) and the host side of the
 // C ABI (w2b_trainer.cpp, w2b_exchange.cpp, w2b_plan.cpp, w2b_eval.cpp, w2b_embed.cpp).  Not part of the public interface (include/).
-// The host units that make no HIP call (w2b_corpus.cpp, w2b_eval_twins.cpp, w2b_eval_text.cpp) do not include it.
+// The host units that make no HIP call (w2b_corpus.cpp, w2b_eval_twins.cpp, w2b_eval_text.cpp, w2b_embed_twins.cpp) do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -291,6 +291,13 @@ long long w2b_embed_bagw_scratch(long long n_ids, long long n_bags, int dim, int
 hipError_t w2b_launch_embed_bag_weighted(const uint64_t *T, long long rows, int dim, int bitlevel, const long long *ids,
                                          const float *weights, long long n_ids, const long long *offsets, long long n_bags,
                                          int mode, int dtype, void *out, unsigned long long *bad, void *scratch, hipStream_t s);
+// the projection (w2b_kernels_embedproj.hip; include/word2bits_embed.h, "Projection"): x = the vectors [n][dim] on the device,
+// cand = int64 candidate rows [m] or nullptr, then candidate j is row cand_base + j; X = w2b_embed_project_operand_bytes(dim, n)
+// bytes of operand staging (written by the launch itself); out = dense [n][m] of dtype.  Two kernels: the operands, the product.
+size_t w2b_embed_project_operand_bytes(int dim, long long n);
+hipError_t w2b_launch_embed_project(const uint64_t *T, long long rows, int dim, int bitlevel, const float *x, int n,
+                                    const long long *cand, long long cand_base, int m, int dtype, void *X, void *out,
+                                    unsigned long long *bad, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

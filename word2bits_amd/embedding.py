@@ -6,8 +6,11 @@
     x = emb.torch_lookup(token_ids, dtype=torch.bfloat16)       # torch tensor on the device, ids from any device
     s = emb.torch_bag(token_ids, offsets, mode="sum")
     v = emb.torch_bag(token_ids, offsets, mode="mean", per_sample_weights=sif)   # weighted pooling (SIF, TF-IDF, a mask)
+    logits = emb.torch_project(hidden)                          # [..., rows]: the tied output layer, from the packed rows
+    scores = emb.torch_project(hidden, candidates=cand, dtype=torch.bfloat16)    # [..., m]: a candidate list only
 
-Lookup and pooling run on the MI355X (w2b_kernels_embed.hip); there is no CPU path in this module.
+Lookup, pooling and the projection run on the MI355X (w2b_kernels_embed.hip, w2b_kernels_embedproj.hip); there is no CPU
+path in this module.
 """
 import ctypes as C
 
@@ -112,6 +115,25 @@ class PackedEmbedding:
                                          offsets.ctypes.data_as(_lib.i64p), m, code, C.c_void_p(out.ctypes.data)))
         return out
 
+    def project(self, x, candidates=None, dtype="float32"):
+        """Logits of the vectors `x` (float array [..., dim], cast to float32) against the rows `candidates` (int array
+        [m]; < 0 = padding, a column of +0.0) or against every row: numpy x.shape[:-1] + (m,).  The projection of the
+        header: one float32 fmaf chain per (vector, candidate), a defined result bit for bit."""
+        code = _dtype_code(dtype)
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim < 1 or x.shape[-1] != self.dim:
+            raise ValueError("x must be [..., %d]" % self.dim)
+        n = x.size // self.dim
+        if candidates is None:
+            m, cand_p = self.rows, None
+        else:
+            cand = np.ascontiguousarray(candidates, np.int32).ravel()
+            m, cand_p = cand.size, cand.ctypes.data_as(_lib.i32p)
+        out = self._out(x.shape[:-1] + (m,), code)
+        _lib.check(self._L.w2b_embed_project(self._h, n, x.ctypes.data_as(_lib.f32p), m, cand_p, code,
+                                             C.c_void_p(out.ctypes.data)))
+        return out
+
     # ---- device form: library-owned staging, viewed by torch
     def reserve(self, max_ids, max_bags=0, dtype="float32"):
         """(ids_dev, offsets_dev, out_dev) addresses of the library's staging buffers (w2b_embed_reserve)."""
@@ -135,6 +157,16 @@ class PackedEmbedding:
     def bag_weighted_device(self, n_ids, n_bags, mode="sum", dtype="float32"):
         _lib.check(self._L.w2b_embed_bag_weighted_device(self._h, int(n_ids), int(n_bags), _mode_code(mode),
                                                          _dtype_code(dtype)))
+
+    def reserve_project(self, max_n, max_m, dtype="float32"):
+        """(x_dev, cand_dev, out_dev) addresses of the projection's staging buffers (w2b_embed_reserve_project): buffers of
+        their own, each of which moves only when it grows itself."""
+        p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        _lib.check(self._L.w2b_embed_reserve_project(self._h, int(max_n), int(max_m), _dtype_code(dtype), *map(C.byref, p)))
+        return tuple(x.value for x in p)
+
+    def project_device(self, n, m, use_candidates=True, dtype="float32"):
+        _lib.check(self._L.w2b_embed_project_device(self._h, int(n), int(m), 1 if use_candidates else 0, _dtype_code(dtype)))
 
     def synchronize(self):
         _lib.check(self._L.w2b_embed_synchronize(self._h))
@@ -170,6 +202,20 @@ class PackedEmbedding:
     def staging_weights(self, max_ids):
         """torch view of the weights buffer: float32 [max_ids]; valid until a later call reserves more weights."""
         return self._view(self.reserve_weights(max_ids), max(int(max_ids), 1), "<f4")[:int(max_ids)]
+
+    def staging_project(self, max_n, max_m, dtype="float32"):
+        """torch views of the projection's staging buffers: x float32 [max_n, dim], candidates int64 [max_m], out flat
+        [max_n * max_m] of `dtype` (a call of n vectors and m candidates leaves out[:n * m].view(n, m)); each valid until
+        a later call makes that buffer grow."""
+        import torch
+        code = _dtype_code(dtype)
+        max_n, max_m = int(max_n), int(max_m)
+        x_p, cand_p, out_p = self.reserve_project(max_n, max_m, dtype)
+        out = self._view(out_p, max(max_n * max_m, 1), ("<f4", "<i2", "<f2")[code])
+        if code == 1:
+            out = out.view(torch.bfloat16)
+        return (self._view(x_p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim),
+                self._view(cand_p, max(max_m, 1), "<i8")[:max_m], out[:max_n * max_m])
 
     def _finish(self, out, copy, what):
         self.synchronize()
@@ -215,6 +261,25 @@ class PackedEmbedding:
             else:
                 self.bag_device(n, nb, mode, dtype)
         return self._finish(out[:nb], copy, "torch_bag")
+
+    def torch_project(self, x, candidates=None, dtype=None, copy=True):
+        """Logits of `x` (torch tensor [..., dim] on any device, cast to float32) against `candidates` (integer tensor [m]
+        on any device, cast to int64) or every row: tensor x.shape[:-1] + (m,) on this handle's device.  A candidate >=
+        rows raises; copy=False returns the view of the library's buffer, valid until the next call on this handle."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if x.dim() < 1 or x.shape[-1] != self.dim:
+            raise ValueError("x must be [..., %d]" % self.dim)
+        n = x.numel() // self.dim
+        m = self.rows if candidates is None else candidates.numel()
+        x_t, cand_t, out = self.staging_project(n, m, dtype)
+        if n and m:
+            x_t.copy_(x.reshape(n, self.dim))                 # copy_ casts to float32
+            if candidates is not None:
+                cand_t.copy_(candidates.reshape(-1))
+            torch.cuda.synchronize()                          # the library's stream does not wait for torch's
+            self.project_device(n, m, candidates is not None, dtype)
+        return self._finish(out[:n * m].view(tuple(x.shape[:-1]) + (m,)), copy, "torch_project")
 
     def timing(self):
         """(kernel ms, launches, bytes moved: packed words (and weights) read + output written) since the last call."""
