@@ -1,12 +1,14 @@
 /*
  * word2bits_embed.h -- C ABI of the packed embedding layer: row lookup and bag pooling on the MI355X, straight from the
  * bit-packed table of a 1-bit or 2-bit model (the .w2bp layout of include/word2bits_corpus.h), and the output projection
- * (logits) of a batch of float vectors against the same packed rows.
+ * (logits) of a batch of float vectors against the same packed rows, with its back-projection (the gradient with respect
+ * to those vectors; the expected embedding under a distribution over rows).
  *
  * The consumer of a packed model that is not the evaluator: a downstream model asks for the rows of a batch of token ids,
  * or for their sum / mean per sentence ("bag").  The rows stay packed on the device, [rows][w2b_packed_words_per_row(dim,
  * bitlevel)] 64-bit words, 1/32 (1/16) of the float table; no float table is ever built, on either side.  The kernels are in
- * word2bits_amd/csrc/w2b_kernels_embed.hip and w2b_kernels_embedproj.hip, the host side in w2b_embed.cpp.
+ * word2bits_amd/csrc/w2b_kernels_embed.hip, w2b_kernels_embedproj.hip and w2b_kernels_embedback.hip, the host side in
+ * w2b_embed.cpp.
  *
  * No CPU fallback: W2B_ENOGPU when no device is visible (the *_host functions below are the tests' twins of the kernels,
  * as w2b_bits_scores_host is for the bits kernels).  Error codes and w2b_last_error() are those of word2bits_hip.h.
@@ -69,11 +71,34 @@
  *   Three consequences: with x = the unit vector of column a, out[.][j] is the value lookup(cand[j])[a] bit for bit (1 * q
  *   and 3 * 0.25 are exact); S equals the S_out of w2b_vector_scores_host for the same row and vector bit for bit; scaling
  *   every x by 2^s (staying in range) scales every output exactly.
+ * Back-projection (w2b_embed_backproject*; the gradient of the projection with respect to x, and the expected embedding
+ *   p @ E under a distribution over rows or candidates): dx[i][a] = sum over j of g[i][j] * E[cand[j]][a].  Table, bitlevel,
+ *   t_r[a], q and the candidate rules are those of the projection: cand is int32 [m], or NULL, which means every row in row
+ *   order, and m must then be rows; an id < 0 is padding; the same row may stand several times; in the host form an id >=
+ *   rows is W2B_EINVAL.  Input: g is float32 [n][m].  Output: dx is float32 [n][dim], dense; there is no 16-bit output (x is
+ *   float32, so its gradient is too).
+ *   The order is part of the contract, and it is the weighted bag's: per vector i and column a the candidate positions
+ *   0 .. m - 1, padding included, are cut into segments of W2B_EMBED_WSEG consecutive positions counted from position 0.
+ *   With r = cand[j]:
+ *       segment s:  P_s = +0;  for the positions j of s in order with cand[j] >= 0:  P_s = fmaf(g[i][j], (float)t_r[a], P_s)
+ *       bag:        S = +0;  for s in order:  S = S + P_s          each ONE float32 add, rounded on its own
+ *       dx[i][a] = S * q                                           ONE float32 multiply
+ *   g at a padding position is ignored and may hold anything, NaN included.  In the device form the same holds for a
+ *   candidate >= rows: it contributes nothing and is counted once in w2b_embed_bad_ids.  In the host form a g on a
+ *   candidate >= 0 must be finite and either 0 or 2^-60 <= |g| <= 2^60, else W2B_EINVAL naming the vector and the candidate
+ *   position; the device form does not look at the values: what a NaN or a value out of range produces is what the chain
+ *   produces on the device, as for x in the projection.  m == 0 gives +0.0 rows.
+ *   Four consequences: (a) for m <= W2B_EMBED_MAX_BAG, dx[i] equals w2b_embed_bag_weighted with ids = cand (or 0 .. rows - 1),
+ *   weights = g[i], one bag per vector, mode sum, bit for bit; (b) with g[i] the unit vector of position j, dx[i] is
+ *   lookup(cand[j]) bit for bit; (c) scaling every g by 2^s (staying in range) scales dx exactly; (d) it is the adjoint of
+ *   the projection: at bitlevel 2, where q is exact, and with small integers, so that every sum is exact,
+ *   sum_ij g[i][j] * project(x)[i][j] == sum_ia x[i][a] * dx[i][a] holds exactly.
  *
  * ---- out of scope --------------------------------------------------------------------------------------------------
- * Gradients or training through the lookup (the table is read-only); gradients with respect to x through the projection
- * (a product over the rows, which needs an order contract of its own); bitlevels other than 1 and 2; a handle built from
- * a live trainer (w2b_export_packed + w2b_embed_create does it in two calls); float input files.
+ * Gradients or training through the lookup (the table is read-only); gradients with respect to the table through the
+ * projection, and second derivatives (the back-projection is once-differentiable: it is not itself recorded); bitlevels
+ * other than 1 and 2; a handle built from a live trainer (w2b_export_packed + w2b_embed_create does it in two calls);
+ * float input files.
  */
 #ifndef WORD2BITS_EMBED_H
 #define WORD2BITS_EMBED_H
@@ -176,6 +201,28 @@ int w2b_embed_reserve_project(w2b_embed *e, int64_t max_n, int64_t max_m, int32_
                               void **out_dev /* [max_n][max_m] of dtype */);
 int w2b_embed_project_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t dtype);
 
+/* Back-projection, the semantics above.  Host form: validated before anything is launched, in the projection's order: what
+ * needs no handle (n or m negative or beyond 2^24 vectors / 0x7FFFFF00 candidates, g == NULL with n > 0 and m > 0, dx == NULL
+ * with n > 0), then the handle, then the candidates (cand == NULL with m != rows; the first id >= rows), then the first
+ * refused value of g; each is W2B_EINVAL with its cause in w2b_last_error(), and `dx` is untouched.  n == 0 is W2B_OK; m == 0
+ * writes +0.0 rows.  Large calls run in chunks of whole vectors x candidate ranges that are multiples of W2B_EMBED_WSEG,
+ * about 64 MiB of g per launch, S carried from one range to the next; the result does not depend on the chunking.
+ * Device form: w2b_embed_reserve_backproject hands out g_dev = float[max_n][max_m], cand_dev = int64[max_m] and dx_dev =
+ * float[max_n][dim], buffers of their own beside those of the three other reserve calls: a pointer goes stale only when that
+ * buffer itself grows (a call that asks for no more than is there returns the same pointers).  The caller fills g_dev --
+ * dense [n][m] for the n and m of the call -- (and cand_dev), launches, and reads dx_dev, dense [n][dim], after
+ * w2b_embed_synchronize.  use_cand = 0 means all rows: m must be rows.  W2B_EINVAL when n or m exceed what was reserved.  No
+ * content of the staging makes a kernel read or write outside its buffers.  The device scratch for the segments' partial
+ * sums is at most 64 MiB, whatever m is: when a call's segments go through it (few vectors x columns, many segments), the
+ * driver launches ranges of segments in order and the finishing step carries S; both ways give the same bits.
+ * w2b_embed_timing_read counts one launch per call (per chunk of the host form); its bytes are n x m x 4 for g, m x words per
+ * row x 8 for the rows, 8 per candidate id when candidates are given, and n x dim x 4 of output. */
+int w2b_embed_backproject(w2b_embed *e, int64_t n, const float *g, int64_t m, const int32_t *cand /* or NULL */, float *dx);
+int w2b_embed_reserve_backproject(w2b_embed *e, int64_t max_n, int64_t max_m,
+                                  void **g_dev /* float[max_n][max_m] */, void **cand_dev /* int64[max_m] */,
+                                  void **dx_dev /* float[max_n][dim] */);
+int w2b_embed_backproject_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand);
+
 /* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form. */
 int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                           int64_t n, const int32_t *ids, float *out);
@@ -188,6 +235,9 @@ int w2b_embed_bag_weighted_host(const uint64_t *packed, int64_t rows, int64_t di
 /* the projection: explicit fmaf per column, then the one multiply (w2b_embed_twins.cpp, a host-only unit) */
 int w2b_embed_project_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
                            const float *x, int64_t m, const int32_t *cand, float *out);
+/* the back-projection: explicit fmaf per candidate position, the segments and the steps exactly as stated above */
+int w2b_embed_backproject_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
+                               const float *g, int64_t m, const int32_t *cand, float *dx);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 // (one set of buffers handed to the caller by w2b_embed_reserve, a separate bounded one for the host form), the chunking
 // of host-form calls (weighted bags stage their weights beside the ids), timing, and the host twins of the kernels in w2b_kernels_embed.hip.
 // The projection (w2b_kernels_embedproj.hip) has staging of its own in both forms; its twin is in the host-only w2b_embed_twins.cpp and
-// what both must refuse in w2b_embed_shared.h.  The table stays packed on the
+// what both must refuse in w2b_embed_shared.h; the same holds for the back-projection (w2b_kernels_embedback.hip), whose scratch for
+// the segments' partial sums follows the call.  The table stays packed on the
 // device; no float table exists on either side and there is no CPU fallback (the *_host twins are for tests).
 #include "../../include/word2bits_embed.h"
 #include "../../include/word2bits_corpus.h"
@@ -49,6 +50,14 @@ struct ProjStaging {
   void *out = nullptr, *operands = nullptr;  // [n][m] of a dtype; the vectors in fragment order (for cap_n vectors)
   int64_t cap_n = 0, cap_m = 0, out_bytes = 0, operand_bytes = 0;
 };
+// device staging of one form of the back-projection: buffers of their own again; the scratch follows the call
+struct BackStaging {
+  float *g = nullptr;                        // [cap_n][cap_m] reserved; a call's g is dense [n][m]
+  long long *cand = nullptr;                 // [cap_m]
+  float *dx = nullptr;                       // [cap_n][dim]
+  void *scratch = nullptr;                   // the segments' partial sums, when the driver sends them through the scratch
+  int64_t g_elems = 0, cap_m = 0, cap_n = 0, scratch_bytes = 0;
+};
 struct Pending { hipEvent_t a, b; };
 }  // namespace
 
@@ -64,6 +73,7 @@ struct w2b_embed {
   unsigned long long *bad = nullptr;         // device counter
   Staging user, host;
   ProjStaging puser, phost;
+  BackStaging buser, bhost;
   std::vector<Pending> pending;
   double kernel_ms = 0, bytes = 0;
   int64_t launches = 0;
@@ -88,6 +98,14 @@ void free_project(ProjStaging &s) {
   s = ProjStaging();
 }
 
+void free_back(BackStaging &s) {
+  if (s.g) (void)hipFree(s.g);
+  if (s.cand) (void)hipFree(s.cand);
+  if (s.dx) (void)hipFree(s.dx);
+  if (s.scratch) (void)hipFree(s.scratch);
+  s = BackStaging();
+}
+
 void embed_release(w2b_embed *e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
@@ -97,6 +115,8 @@ void embed_release(w2b_embed *e) {
   free_staging(e->host);
   free_project(e->puser);
   free_project(e->phost);
+  free_back(e->buser);
+  free_back(e->bhost);
   if (e->T) (void)hipFree(e->T);
   if (e->bad) (void)hipFree(e->bad);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -241,6 +261,18 @@ int ensure_project(w2b_embed *e, ProjStaging &s, int64_t max_n, int64_t max_m, i
   return W2B_OK;
 }
 
+// the back-projection's buffers for max_n vectors and max_m candidates (g holds max_n * max_m values); only ever grow, each
+// on its own
+int ensure_back(w2b_embed *e, BackStaging &s, int64_t max_n, int64_t max_m) {
+  if (max_n * max_m > s.g_elems || !s.g)
+    if (int rc = grow(e, s.g, s.g_elems, max_n * max_m * 4, max_n * max_m)) return rc;
+  if (max_m > s.cap_m || !s.cand)
+    if (int rc = grow(e, s.cand, s.cap_m, max_m * 8, max_m)) return rc;
+  if (max_n > s.cap_n || !s.dx)
+    if (int rc = grow(e, s.dx, s.cap_n, max_n * e->dim * 4, max_n)) return rc;
+  return W2B_OK;
+}
+
 int fold_pending(w2b_embed *e) {
   EHIP(hipStreamSynchronize(e->stream));
   for (Pending &p : e->pending) {
@@ -307,6 +339,23 @@ int launch_project(w2b_embed *e, ProjStaging &s, int64_t n, int64_t m, bool use_
   return timed(e, bytes, [&] {
     return w2b_launch_embed_project(e->T, e->rows, (int)e->dim, e->bitlevel, s.x, (int)n, use_cand ? s.cand : nullptr, cand_base,
                                     (int)m, dtype, s.operands, s.out, e->bad, e->stream);
+  });
+}
+
+// n vectors of s.g (dense, m apart) against m candidate positions that begin a segment: those of s.cand, or the rows
+// cand_base .. cand_base + m when !use_cand.  The scratch follows the call (it waits for the stream only when it has to grow).
+int launch_backproject(w2b_embed *e, BackStaging &s, int64_t n, int64_t m, bool use_cand, int64_t cand_base, bool first,
+                       bool last) {
+  int use_scratch = 0, segs = 1;
+  long long need = 0;
+  w2b_embed_backproject_plan((int)e->dim, n, m, &use_scratch, &segs, &need);
+  if (need > s.scratch_bytes)
+    if (int rc = grow(e, s.scratch, s.scratch_bytes, need, need)) return rc;
+  const double bytes = (double)n * (double)m * 4 + (double)m * (double)e->wpr * 8 + (use_cand ? (double)m * 8 : 0.0) +
+                       (double)n * (double)e->dim * 4;
+  return timed(e, bytes, [&] {
+    return w2b_launch_embed_backproject(e->T, e->rows, (int)e->dim, e->bitlevel, s.g, m, n, use_cand ? s.cand : nullptr, cand_base,
+                                        (int)m, first, last, s.dx, use_scratch, segs, s.scratch, e->bad, e->stream);
   });
 }
 }  // namespace
@@ -511,7 +560,79 @@ extern "C" int w2b_embed_project(w2b_embed *e, int64_t n, const float *x, int64_
   return W2B_OK;
 }
 
+extern "C" int w2b_embed_backproject(w2b_embed *e, int64_t n, const float *g, int64_t m, const int32_t *cand, float *dx) {
+  const char *who = "w2b_embed_backproject";
+  if (int rc = backproject_check_args(who, n, g, m, dx)) return rc;
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_backproject: null handle");
+  if (int rc = project_check_cand(who, e->rows, m, cand)) return rc;
+  if (int rc = backproject_check_values(who, n, m, cand, g)) return rc;
+  if (n == 0) return W2B_OK;
+  if (m == 0) {
+    memset(dx, 0, (size_t)(n * e->dim) * 4);
+    return W2B_OK;
+  }
+  EHIP(hipSetDevice(e->device));
+  // whole vectors x candidate ranges that are multiples of W2B_EMBED_WSEG, about kHostOutBytes of g per launch (and of dx
+  // per range of vectors); S is carried in the device's dx from one candidate range to the next
+  int64_t nv = kHostOutBytes / (e->dim * 4);
+  nv = nv < 1 ? 1 : (nv > 4096 ? 4096 : nv);
+  if (nv > n) nv = n;
+  int64_t cm = kHostOutBytes / (4 * nv) / W2B_EMBED_WSEG * W2B_EMBED_WSEG;   // (at least 4096: nv <= 4096)
+  if (cm > kHostIds) cm = kHostIds;
+  if (cm > m) cm = m;
+  std::vector<long long> wide;
+  for (int64_t i0 = 0; i0 < n; i0 += nv) {
+    const int64_t ci = n - i0 < nv ? n - i0 : nv;
+    if (int rc = ensure_back(e, e->bhost, nv, cm)) return rc;
+    for (int64_t j0 = 0; j0 < m; j0 += cm) {
+      const int64_t cj = m - j0 < cm ? m - j0 : cm;
+      if (cand) {
+        wide.assign(cand + j0, cand + j0 + cj);
+        EHIP(hipMemcpyAsync(e->bhost.cand, wide.data(), (size_t)cj * 8, hipMemcpyHostToDevice, e->stream));
+      }
+      EHIP(hipMemcpy2DAsync(e->bhost.g, (size_t)cj * 4, g + i0 * m + j0, (size_t)m * 4, (size_t)cj * 4, (size_t)ci,
+                            hipMemcpyHostToDevice, e->stream));
+      if (int rc = launch_backproject(e, e->bhost, ci, cj, cand != nullptr, j0, j0 == 0, j0 + cj == m)) return rc;
+      EHIP(hipStreamSynchronize(e->stream));               // (wide and the staging are written again for the next range)
+    }
+    EHIP(hipMemcpyAsync(dx + i0 * e->dim, e->bhost.dx, (size_t)(ci * e->dim) * 4, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+  }
+  return W2B_OK;
+}
+
 // ------------------------------------------------------------------------------------ device form
+extern "C" int w2b_embed_reserve_backproject(w2b_embed *e, int64_t max_n, int64_t max_m, void **g_dev, void **cand_dev,
+                                             void **dx_dev) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_backproject: null handle");
+  if (max_n < 0 || max_n > kProjectMaxVectors || max_m < 0 || max_m > 0x7FFFFF00ll || max_n * max_m > (1ll << 40) ||
+      max_n * e->dim > (1ll << 40))
+    return efail(W2B_EINVAL, "w2b_embed_reserve_backproject: bad sizes");
+  EHIP(hipSetDevice(e->device));
+  if (int rc = ensure_back(e, e->buser, max_n, max_m)) return rc;
+  if (g_dev) *g_dev = e->buser.g;
+  if (cand_dev) *cand_dev = e->buser.cand;
+  if (dx_dev) *dx_dev = e->buser.dx;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_backproject_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_backproject_device: null handle");
+  if (n < 0 || m < 0) return efail(W2B_EINVAL, "w2b_embed_backproject_device: negative count");
+  if (use_cand != 0 && use_cand != 1) return efail(W2B_EINVAL, "w2b_embed_backproject_device: use_cand must be 0 or 1");
+  if (n == 0) return W2B_OK;
+  BackStaging &s = e->buser;
+  if (!s.g || !s.cand || !s.dx || n > s.cap_n || m > s.cap_m || n * m > s.g_elems)
+    return efail(W2B_EINVAL, "w2b_embed_backproject_device: more than w2b_embed_reserve_backproject has set aside");
+  if (!use_cand && m != e->rows) return efail(W2B_EINVAL, "w2b_embed_backproject_device: without candidates m must be rows");
+  EHIP(hipSetDevice(e->device));
+  if (m == 0) {                                            // an empty sum: +0.0 rows, no launch
+    EHIP(hipMemsetAsync(s.dx, 0, (size_t)(n * e->dim) * 4, e->stream));
+    return W2B_OK;
+  }
+  return launch_backproject(e, s, n, m, use_cand != 0, 0, true, true);
+}
+
 extern "C" int w2b_embed_reserve_project(w2b_embed *e, int64_t max_n, int64_t max_m, int32_t dtype, void **x_dev,
                                          void **cand_dev, void **out_dev) {
   if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_project: null handle");

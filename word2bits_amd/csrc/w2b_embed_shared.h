@@ -1,6 +1,6 @@
-// w2b_embed_shared.h -- what the host form of the packed embedding's projection (w2b_embed.cpp) and its host twin
-// (w2b_embed_twins.cpp) must refuse identically, written once: the validators of w2b_embed_project with their messages, in
-// the order include/word2bits_embed.h states.  Host arithmetic only: no device header, no handle.  Every definition has
+// w2b_embed_shared.h -- what the host forms of the packed embedding's projection and back-projection (w2b_embed.cpp) and
+// their host twins (w2b_embed_twins.cpp) must refuse identically, written once: the validators of w2b_embed_project and
+// w2b_embed_backproject with their messages, in the order include/word2bits_embed.h states.  Host arithmetic only: no device header, no handle.  Every definition has
 // internal linkage, so the library exports none of them.
 #pragma once
 #include "../../include/word2bits_embed.h"
@@ -56,6 +56,34 @@ inline int project_check_values(const char *who, int64_t n, int64_t dim, const f
       return w2b_internal_fail(W2B_EINVAL, msg);
     }
   }
+  return W2B_OK;
+}
+
+// the back-projection (w2b_embed_backproject*): its checks that need no handle and no table
+inline int backproject_check_args(const char *who, int64_t n, const float *g, int64_t m, const void *dx) {
+  const std::string w(who);
+  if (n < 0 || n > kProjectMaxVectors) return w2b_internal_fail(W2B_EINVAL, (w + ": bad vector count").c_str());
+  if (m < 0 || m > 0x7FFFFF00ll) return w2b_internal_fail(W2B_EINVAL, (w + ": bad candidate count").c_str());
+  if (n > 0 && m > 0 && !g) return w2b_internal_fail(W2B_EINVAL, (w + ": null g").c_str());
+  if (n > 0 && !dx) return w2b_internal_fail(W2B_EINVAL, (w + ": null output").c_str());
+  return W2B_OK;
+}
+
+// the first g on a candidate >= 0 (every position when cand is NULL) that is not finite, or neither 0 nor within 2^-60 .. 2^60
+inline int backproject_check_values(const char *who, int64_t n, int64_t m, const int32_t *cand, const float *g) {
+  for (int64_t i = 0; i < n; i++)
+    for (int64_t j = 0; j < m; j++) {
+      if (cand && cand[j] < 0) continue;
+      uint32_t bits;
+      memcpy(&bits, g + i * m + j, 4);
+      const uint32_t a = bits & 0x7FFFFFFFu;
+      if (a != 0u && (a < 0x21800000u || a > 0x5D800000u)) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: vector %lld, candidate %lld: %g is not finite, or neither 0 nor within 2^-60 .. 2^60", who,
+                 (long long)i, (long long)j, (double)g[i * m + j]);
+        return w2b_internal_fail(W2B_EINVAL, msg);
+      }
+    }
   return W2B_OK;
 }
 }  // namespace

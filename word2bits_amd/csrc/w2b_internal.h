@@ -298,6 +298,15 @@ size_t w2b_embed_project_operand_bytes(int dim, long long n);
 hipError_t w2b_launch_embed_project(const uint64_t *T, long long rows, int dim, int bitlevel, const float *x, int n,
                                     const long long *cand, long long cand_base, int m, int dtype, void *X, void *out,
                                     unsigned long long *bad, hipStream_t s);
+// the back-projection (w2b_kernels_embedback.hip; include/word2bits_embed.h, "Back-projection"): g = [n][.] on the device, ldg
+// floats between two vectors; the m candidate positions of a launch begin a segment, position j is row cand[j] or, when cand
+// is nullptr, cand_base + j; first / last = the positions begin / end the call's whole list (S is carried in dx between
+// launches).  w2b_embed_backproject_plan chooses the path and the scratch (at most 64 MiB, whatever m is) for n vectors.
+void w2b_embed_backproject_plan(int dim, long long n, long long m, int *use_scratch, int *segs, long long *scratch_bytes);
+hipError_t w2b_launch_embed_backproject(const uint64_t *T, long long rows, int dim, int bitlevel, const float *g,
+                                        long long ldg, long long n, const long long *cand, long long cand_base, int m,
+                                        int first, int last, float *dx, int use_scratch, int segs, void *part,
+                                        unsigned long long *bad, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

@@ -8,9 +8,11 @@
     v = emb.torch_bag(token_ids, offsets, mode="mean", per_sample_weights=sif)   # weighted pooling (SIF, TF-IDF, a mask)
     logits = emb.torch_project(hidden)                          # [..., rows]: the tied output layer, from the packed rows
     scores = emb.torch_project(hidden, candidates=cand, dtype=torch.bfloat16)    # [..., m]: a candidate list only
+    loss(emb.torch_project(hidden.requires_grad_())).backward() # hidden.grad comes from the packed rows too (no float table)
+    mean = emb.torch_backproject(probs)                         # [..., dim]: the expected embedding probs @ E
 
-Lookup, pooling and the projection run on the MI355X (w2b_kernels_embed.hip, w2b_kernels_embedproj.hip); there is no CPU
-path in this module.
+Lookup, pooling, the projection and its back-projection run on the MI355X (w2b_kernels_embed.hip,
+w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip); there is no CPU path in this module.
 """
 import ctypes as C
 
@@ -34,6 +36,32 @@ def _mode_code(mode):
     if mode not in MODES:
         raise ValueError("mode must be 'sum' or 'mean'")
     return MODES[mode]
+
+
+_PROJECT_FUNCTION = None
+
+
+def _project_function():
+    """The autograd hook of PackedEmbedding.torch_project, defined on first use (torch is imported lazily throughout)."""
+    global _PROJECT_FUNCTION
+    if _PROJECT_FUNCTION is None:
+        import torch
+
+        class PackedProject(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, emb, candidates, dtype):
+                ctx.emb, ctx.candidates = emb, candidates
+                ctx.x_shape, ctx.x_dtype, ctx.x_device = x.shape, x.dtype, x.device
+                return emb.torch_project(x.detach(), candidates, dtype, copy=True)
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, grad_out):
+                dx = ctx.emb.torch_backproject(grad_out, ctx.candidates)
+                return dx.reshape(ctx.x_shape).to(device=ctx.x_device, dtype=ctx.x_dtype), None, None, None
+
+        _PROJECT_FUNCTION = PackedProject
+    return _PROJECT_FUNCTION
 
 
 class PackedEmbedding:
@@ -134,6 +162,25 @@ class PackedEmbedding:
                                              C.c_void_p(out.ctypes.data)))
         return out
 
+    def backproject(self, g, candidates=None):
+        """The back-projection of the header: dx[i] = sum over j of g[i][j] * row candidates[j] (`g` float array [..., m],
+        cast to float32; candidates int array [m], < 0 = padding whose g is ignored, or every row): numpy float32
+        g.shape[:-1] + (dim,).  The gradient of project() with respect to x, and the expected embedding p @ E; one defined
+        result bit for bit (the weighted bag's segment rule)."""
+        g = np.ascontiguousarray(g, np.float32)
+        if candidates is None:
+            m, cand_p = self.rows, None
+        else:
+            cand = np.ascontiguousarray(candidates, np.int32).ravel()
+            m, cand_p = cand.size, cand.ctypes.data_as(_lib.i32p)
+        if g.ndim < 1 or g.shape[-1] != m:
+            raise ValueError("g must be [..., %d]" % m)
+        n = int(np.prod(g.shape[:-1]))
+        out = np.empty(g.shape[:-1] + (self.dim,), np.float32)
+        _lib.check(self._L.w2b_embed_backproject(self._h, n, g.ctypes.data_as(_lib.f32p), m, cand_p,
+                                                 out.ctypes.data_as(_lib.f32p)))
+        return out
+
     # ---- device form: library-owned staging, viewed by torch
     def reserve(self, max_ids, max_bags=0, dtype="float32"):
         """(ids_dev, offsets_dev, out_dev) addresses of the library's staging buffers (w2b_embed_reserve)."""
@@ -167,6 +214,16 @@ class PackedEmbedding:
 
     def project_device(self, n, m, use_candidates=True, dtype="float32"):
         _lib.check(self._L.w2b_embed_project_device(self._h, int(n), int(m), 1 if use_candidates else 0, _dtype_code(dtype)))
+
+    def reserve_backproject(self, max_n, max_m):
+        """(g_dev, cand_dev, dx_dev) addresses of the back-projection's staging buffers (w2b_embed_reserve_backproject):
+        buffers of their own, each of which moves only when it grows itself."""
+        p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        _lib.check(self._L.w2b_embed_reserve_backproject(self._h, int(max_n), int(max_m), *map(C.byref, p)))
+        return tuple(x.value for x in p)
+
+    def backproject_device(self, n, m, use_candidates=True):
+        _lib.check(self._L.w2b_embed_backproject_device(self._h, int(n), int(m), 1 if use_candidates else 0))
 
     def synchronize(self):
         _lib.check(self._L.w2b_embed_synchronize(self._h))
@@ -217,6 +274,16 @@ class PackedEmbedding:
         return (self._view(x_p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim),
                 self._view(cand_p, max(max_m, 1), "<i8")[:max_m], out[:max_n * max_m])
 
+    def staging_backproject(self, max_n, max_m):
+        """torch views of the back-projection's staging buffers: g float32 flat [max_n * max_m] (a call of n vectors and m
+        candidates reads g[:n * m].view(n, m)), candidates int64 [max_m], dx float32 [max_n, dim]; each valid until a later
+        call makes that buffer grow."""
+        max_n, max_m = int(max_n), int(max_m)
+        g_p, cand_p, dx_p = self.reserve_backproject(max_n, max_m)
+        return (self._view(g_p, max(max_n * max_m, 1), "<f4")[:max_n * max_m],
+                self._view(cand_p, max(max_m, 1), "<i8")[:max_m],
+                self._view(dx_p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim))
+
     def _finish(self, out, copy, what):
         self.synchronize()
         bad = self.bad_ids()
@@ -265,11 +332,16 @@ class PackedEmbedding:
     def torch_project(self, x, candidates=None, dtype=None, copy=True):
         """Logits of `x` (torch tensor [..., dim] on any device, cast to float32) against `candidates` (integer tensor [m]
         on any device, cast to int64) or every row: tensor x.shape[:-1] + (m,) on this handle's device.  A candidate >=
-        rows raises; copy=False returns the view of the library's buffer, valid until the next call on this handle."""
+        rows raises; copy=False returns the view of the library's buffer, valid until the next call on this handle.
+        Differentiable with respect to x, once: when x requires a gradient (and grad mode is on) the result is a copy that
+        carries a grad_fn, whose backward is torch_backproject of the incoming gradient (cast to float32), returned with
+        x's shape, dtype and device.  The table gets no gradient."""
         import torch
         dtype = torch.float32 if dtype is None else dtype
         if x.dim() < 1 or x.shape[-1] != self.dim:
             raise ValueError("x must be [..., %d]" % self.dim)
+        if x.requires_grad and torch.is_grad_enabled():
+            return _project_function().apply(x, self, candidates, dtype)
         n = x.numel() // self.dim
         m = self.rows if candidates is None else candidates.numel()
         x_t, cand_t, out = self.staging_project(n, m, dtype)
@@ -280,6 +352,26 @@ class PackedEmbedding:
             torch.cuda.synchronize()                          # the library's stream does not wait for torch's
             self.project_device(n, m, candidates is not None, dtype)
         return self._finish(out[:n * m].view(tuple(x.shape[:-1]) + (m,)), copy, "torch_project")
+
+    def torch_backproject(self, g, candidates=None, copy=True):
+        """The back-projection of `g` (torch tensor [..., m] on any device, cast to float32) through `candidates` (integer
+        tensor [m] on any device, cast to int64; < 0 = padding whose g is ignored) or every row: float32 tensor
+        g.shape[:-1] + (dim,) on this handle's device.  A candidate >= rows raises; copy=False returns the view of the
+        library's buffer, valid until the next call on this handle."""
+        import torch
+        m = self.rows if candidates is None else candidates.numel()
+        if g.dim() < 1 or g.shape[-1] != m:
+            raise ValueError("g must be [..., %d]" % m)
+        n = g.numel() // m if m else int(np.prod(tuple(g.shape[:-1])))
+        g_t, cand_t, dx = self.staging_backproject(n, m)
+        if n:
+            if m:
+                g_t[:n * m].view(n, m).copy_(g.reshape(n, m))     # copy_ casts to float32
+                if candidates is not None:
+                    cand_t.copy_(candidates.reshape(-1))
+            torch.cuda.synchronize()                              # the library's stream does not wait for torch's
+            self.backproject_device(n, m, candidates is not None or m == 0)
+        return self._finish(dx[:n].view(tuple(g.shape[:-1]) + (self.dim,)), copy, "torch_backproject")
 
     def timing(self):
         """(kernel ms, launches, bytes moved: packed words (and weights) read + output written) since the last call."""
