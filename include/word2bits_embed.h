@@ -2,12 +2,13 @@
  * word2bits_embed.h -- C ABI of the packed embedding layer: row lookup and bag pooling on the MI355X, straight from the
  * bit-packed table of a 1-bit or 2-bit model (the .w2bp layout of include/word2bits_corpus.h), and the output projection
  * (logits) of a batch of float vectors against the same packed rows, with its back-projection (the gradient with respect
- * to those vectors; the expected embedding under a distribution over rows).
+ * to those vectors; the expected embedding under a distribution over rows), and the softmax cross-entropy of that projection
+ * with its gradient, computed without the logits ever being stored.
  *
  * The consumer of a packed model that is not the evaluator: a downstream model asks for the rows of a batch of token ids,
  * or for their sum / mean per sentence ("bag").  The rows stay packed on the device, [rows][w2b_packed_words_per_row(dim,
  * bitlevel)] 64-bit words, 1/32 (1/16) of the float table; no float table is ever built, on either side.  The kernels are in
- * word2bits_amd/csrc/w2b_kernels_embed.hip, w2b_kernels_embedproj.hip and w2b_kernels_embedback.hip, the host side in
+ * word2bits_amd/csrc/w2b_kernels_embed.hip, w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip and w2b_kernels_embedxent.hip, the host side in
  * w2b_embed.cpp.
  *
  * No CPU fallback: W2B_ENOGPU when no device is visible (the *_host functions below are the tests' twins of the kernels,
@@ -93,10 +94,59 @@
  *   lookup(cand[j]) bit for bit; (c) scaling every g by 2^s (staying in range) scales dx exactly; (d) it is the adjoint of
  *   the projection: at bitlevel 2, where q is exact, and with small integers, so that every sum is exact,
  *   sum_ij g[i][j] * project(x)[i][j] == sum_ia x[i][a] * dx[i][a] holds exactly.
+ * Cross-entropy (w2b_embed_xent*; softmax cross-entropy of the tied output layer, and its gradient with respect to x, without
+ *   an [n][m] array of logits, probabilities or gradients on the device).  Table, bitlevel, t_r[a], q, x, cand, padding
+ *   (id < 0) and the all-rows form (cand == NULL, m == rows) are those of the projection.  In addition target is int32 [n]:
+ *   target[i] is a candidate POSITION in [0, m) -- in the all-rows form that is the row --, and target[i] < 0 means that
+ *   vector i is ignored (torch's ignore_index).  With l[i][j] = the projection's float32 result for vector i and position j
+ *   (the chain, then * q), and LIVE = a position whose candidate is not padding:
+ *   1. expneg(r), for float32 r <= 0, is a defined sequence of individually rounded float32 operations, written once in
+ *      w2b_embed_shared.h (the host twin and the kernels compile the same text):
+ *          r < -64, or not r >= -64:   +0.0 exactly
+ *          otherwise   k = rintf(r * LOG2E)                     one multiply, one round to nearest even
+ *                      f = fmaf(k, -LN2_HI, r);  f = fmaf(k, -LN2_LO, f)
+ *                      p = Horner in f, explicit fmaf, degree 7, coefficients 1/i! rounded to float32 (hex patterns there)
+ *                      result = p * 2^k                         2^k built from integer bits; the multiply is exact
+ *      Every non-zero result is a normal number >= 2^-93, so nothing depends on how an instruction treats subnormals;
+ *      expneg(0) == 1.0f exactly; no result exceeds 1.  Within 1 ulp of exp(r) (0.881 ulp measured on a dense sample).
+ *   2. Segment statistics.  The positions 0 .. m - 1, padding included, are cut into segments of W2B_EMBED_XSEG = 256
+ *      consecutive positions counted from 0: the candidates ONE workgroup of the projection kernel holds in its accumulators
+ *      (four wavefronts x two interleaved 32-candidate tiles), so a segment is reduced where its logits already are.  A
+ *      contract constant like W2B_EMBED_WSEG.  Per vector and segment s:
+ *          M_s = the maximum of l over the segment's live positions                       exact, independent of order
+ *          U_s = the sum over the segment's live positions of (uint64) rint(expneg(l - M_s) * 2^32)
+ *                the subtraction ONE float32 operation, the scaling exact, the rounding to nearest even: each term an
+ *                integer in [0, 2^32].  Integer adds commute: as in the unweighted bag, the result does not depend on how
+ *                lanes, wavefronts or workgroups split a segment.
+ *      A segment without a live position does not take part.
+ *   3. Per vector.  mx = the maximum of M_s, exact.  se: start at +0, then for s in order
+ *          se = fmaf((float)U_s * 2^-32, expneg(M_s - mx), se)
+ *      one u64 -> f32 conversion (round to nearest even), one exact scaling, one fused multiply-add per segment, strictly
+ *      sequential.  tl = l[i][target[i]].  If no position is live: mx = se = +0.0.  For an ignored vector tl = +0.0; mx and se
+ *      are still as above.
+ *   4. The loss is (mx - tl) + log(se).  The logarithm is the one step outside the bit-for-bit contract: the C ABI returns
+ *      mx, se and tl; the numpy front computes the loss in float64, the torch front in float32 with torch.log.  The loss of
+ *      an ignored vector is 0.
+ *   5. Gradient.  For a live position g[i][j] = expneg(l - mx) / se: one subtraction, one correctly rounded division; at
+ *      j == target[i] one more float32 subtraction, - 1.0f.  g is +0.0 throughout for an ignored vector.  dx[i] is THE
+ *      BACK-PROJECTION of g[i] through the same candidates under its existing contract, bit for bit: the W2B_EMBED_WSEG
+ *      segments, one fmaf per position, then * q.  Padding positions are ignored, as there.  What does not carry over is the
+ *      back-projection's value rule: g is computed, not supplied, and may lie below 2^-60 (never below 2^-93 / 2^31: it is
+ *      normal).  A partial sum P_s could only become subnormal through the cancellation of terms below 2^-103, which needs
+ *      se > 2^10 times the largest of them; in that corner the result is what the chain produces on the device.
+ *   Consequences: (a) mx, tl and every l equal w2b_embed_project_host bit for bit; (b) dx equals
+ *   w2b_embed_backproject_host applied to the g of step 5, bit for bit, wherever that function admits the g; (c) permuting
+ *   the candidates WITHIN a segment changes neither mx, nor se, nor any U_s; (d) adding a padding-only segment changes
+ *   nothing; (e) with m == 1 and target 0: mx == tl, se == 1.0f, dx == +0.0.
+ *   Host form: a target >= m, or one that points at a padding position, is W2B_EINVAL naming the vector.  Device form: such
+ *   a target, or one on a refused candidate, makes the vector ignored and is counted once in w2b_embed_bad_ids; a candidate
+ *   >= rows is dead, as padding is, and is counted once; the values of x are not checked.
  *
  * ---- out of scope --------------------------------------------------------------------------------------------------
  * Gradients or training through the lookup (the table is read-only); gradients with respect to the table through the
- * projection, and second derivatives (the back-projection is once-differentiable: it is not itself recorded); bitlevels
+ * projection or the cross-entropy, and second derivatives (the back-projection and the cross-entropy's gradient are
+ * once-differentiable: they are not themselves recorded); class weights, label smoothing and 16-bit outputs of the
+ * cross-entropy; fusing the back-projection's contraction into the gradient kernel (the next step); bitlevels
  * other than 1 and 2; a handle built from a live trainer (w2b_export_packed + w2b_embed_create does it in two calls);
  * float input files.
  */
@@ -115,6 +165,7 @@ typedef struct w2b_embed w2b_embed;
 #define W2B_EMBED_MEAN 1
 #define W2B_EMBED_MAX_BAG (1 << 22)
 #define W2B_EMBED_WSEG 1024
+#define W2B_EMBED_XSEG 256
 
 /* A bit-packed .w2bp, read without expanding it; `threshold` caps the rows as in w2b_eval_load_bits (0 = off).  What is
  * wrong with the file is reported before a device is asked for: W2B_EIO "Input file not found" when it cannot be opened,
@@ -223,6 +274,38 @@ int w2b_embed_reserve_backproject(w2b_embed *e, int64_t max_n, int64_t max_m,
                                   void **dx_dev /* float[max_n][dim] */);
 int w2b_embed_backproject_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand);
 
+/* Cross-entropy, the semantics above.  Host form: validated before anything is launched, in the projection's order: what needs
+ * no handle (n or m negative or beyond 2^24 vectors / 0x7FFFFF00 candidates; x, target, mx, se or tl == NULL with n > 0), then
+ * the handle, then the candidates (cand == NULL with m != rows; the first id >= rows), then the first refused target (>= m, or
+ * on a padding position; W2B_EINVAL naming the vector), then the first refused value of x; each is W2B_EINVAL with its cause in
+ * w2b_last_error(), and the outputs are untouched.  n == 0 is W2B_OK.  mx, se, tl are float[n]; dx is float[n][dim], or NULL: no
+ * gradient is computed.  Large calls run in ranges of 4096 vectors; the candidate list is staged whole (16 bytes a candidate).
+ * Device form: w2b_embed_reserve_xent hands out x_dev = float[max_n][dim], cand_dev = int64[max_m], target_dev = int64[max_n],
+ * stats_dev = float[3][max_n] and dx_dev = float[max_n][dim], buffers of their own beside those of the four other reserve
+ * calls: a pointer goes stale only when that buffer itself grows (the four per-vector buffers grow together with max_n, cand_dev
+ * with max_m; a call that asks for no more than is there returns the same pointers).  The caller fills x_dev, target_dev (and
+ * cand_dev), launches, and after w2b_embed_synchronize reads stats_dev -- dense [3][n] for the n of the call: mx at 0, se at n,
+ * tl at 2 n -- and, with want_dx = 1, dx_dev, dense [n][dim]; with want_dx = 0 dx_dev is not touched.  use_cand = 0 means all
+ * rows: m must be rows.  W2B_EINVAL when n or m exceed what was reserved.  No content of the staging makes a kernel read or
+ * write outside its buffers: a candidate >= rows is dead, as padding is, and is counted once in w2b_embed_bad_ids; a target >= m,
+ * or on a dead position, makes its vector ignored and is counted once; the values of x are NOT checked.
+ * Device memory beyond the reserved buffers: the operand staging of the vectors (about n x dim x 4), a second candidate list
+ * (8 m), 12 bytes per (vector, segment) of one statistics launch -- at most 64 MiB, or one range of 64 vectors -- and, with
+ * want_dx, at most 64 MiB of g (one vector's candidate range is never cut below W2B_EMBED_WSEG positions) plus the
+ * back-projection's scratch: no [n][m] array exists.  The environment variable W2B_EMBED_XENT_SCRATCH (bytes, read per call)
+ * lowers the 64 MiB of g, so that the chunked gradient can be exercised at a small shape; the result does not depend on it.
+ * w2b_embed_timing_read counts one launch for the statistics of a call (per range of the host form) -- bytes n x dim x 4 for x,
+ * m x words per row x 8 for the rows, 8 per candidate id when candidates are given, 8 n of targets and 12 n of results -- and
+ * one per chunk of the gradient, n_c vectors x m_c candidate positions: 2 x (m_c x words per row x 8, and 8 m_c with
+ * candidates) for the rows read by the gradient kernel and by the back-projection, 2 x n_c x m_c x 4 for g written and read,
+ * and 2 x n_c x dim x 4 for x and dx. */
+int w2b_embed_xent(w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand /* or NULL */,
+                   const int32_t *target, float *mx, float *se, float *tl, float *dx /* or NULL: no gradient */);
+int w2b_embed_reserve_xent(w2b_embed *e, int64_t max_n, int64_t max_m, void **x_dev, void **cand_dev /* int64 */,
+                           void **target_dev /* int64[max_n] */, void **stats_dev /* float[3][max_n]: mx, se, tl */,
+                           void **dx_dev /* float[max_n][dim] */);
+int w2b_embed_xent_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t want_dx);
+
 /* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form. */
 int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                           int64_t n, const int32_t *ids, float *out);
@@ -238,6 +321,11 @@ int w2b_embed_project_host(const uint64_t *packed, int64_t rows, int64_t dim, in
 /* the back-projection: explicit fmaf per candidate position, the segments and the steps exactly as stated above */
 int w2b_embed_backproject_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
                                const float *g, int64_t m, const int32_t *cand, float *dx);
+
+/* the cross-entropy from the definition: explicit loops, the segments of W2B_EMBED_XSEG, dx through the back-projection's chains */
+int w2b_embed_xent_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
+                        int64_t m, const int32_t *cand, const int32_t *target, float *mx, float *se, float *tl, float *dx);
+float w2b_embed_expneg_host(float r);   /* the shared definition of expneg, for the tests */
 
 #ifdef __cplusplus
 }

@@ -343,7 +343,7 @@ int w2b_exchange_apply(w2b_trainer *t, int64_t chunk, float scale);
 int w2b_exchange_end(w2b_trainer *t, int64_t word_count_all_replicas);
 
 /* ---- the packed embedding layer --------------------------------------------------------------------------------------
- * Row lookup, bag pooling, the output projection and its back-projection straight from a bit-packed table: include/word2bits_embed.h has the
+ * Row lookup, bag pooling, the output projection, its back-projection and the cross-entropy straight from a bit-packed table: include/word2bits_embed.h has the
  * types, the constants and the semantics in full, and is the header a consumer includes.  This header is the list of everything the library
  * exports (bindings and the ABI test enumerate it), so the entry points are repeated here as bare prototypes; a unit that
  * includes both headers (csrc/w2b_embed.cpp does) has the compiler check that the two agree. */
@@ -390,6 +390,14 @@ int w2b_embed_reserve_backproject(struct w2b_embed *e, int64_t max_n, int64_t ma
 int w2b_embed_backproject_device(struct w2b_embed *e, int64_t n, int64_t m, int32_t use_cand);
 int w2b_embed_backproject_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
                                const float *g, int64_t m, const int32_t *cand, float *dx);
+int w2b_embed_xent(struct w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand, const int32_t *target,
+                   float *mx, float *se, float *tl, float *dx);
+int w2b_embed_reserve_xent(struct w2b_embed *e, int64_t max_n, int64_t max_m, void **x_dev, void **cand_dev, void **target_dev,
+                           void **stats_dev, void **dx_dev);
+int w2b_embed_xent_device(struct w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t want_dx);
+int w2b_embed_xent_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
+                        int64_t m, const int32_t *cand, const int32_t *target, float *mx, float *se, float *tl, float *dx);
+float w2b_embed_expneg_host(float r);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -58,7 +59,23 @@ struct BackStaging {
   void *scratch = nullptr;                   // the segments' partial sums, when the driver sends them through the scratch
   int64_t g_elems = 0, cap_m = 0, cap_n = 0, scratch_bytes = 0;
 };
+// device staging of one form of the cross-entropy: buffers of their own once more.  What a caller fills or reads (x, cand,
+// target, stats, dx) moves only when that buffer itself grows; the rest follows the call.
+struct XentStaging {
+  float *x = nullptr;                        // [cap_n][dim]
+  long long *cand = nullptr, *clean = nullptr;   // [cap_m]: the caller's candidates; ids >= rows made padding
+  long long *target = nullptr, *teff = nullptr;  // [cap_n]: the caller's targets; the effective ones (-1 = ignored)
+  float *stats = nullptr;                    // [3][n] for the n of a call: mx, se, tl
+  float *dx = nullptr;                       // [cap_n][dim]
+  void *operands = nullptr;                  // the vectors in fragment order (for cap_n vectors)
+  float *mseg = nullptr;                     // [nseg][vectors of a statistics launch]
+  unsigned long long *useg = nullptr;
+  float *g = nullptr;                        // the gradient's dense scratch, at most kXentScratch bytes
+  void *bscratch = nullptr;                  // the back-projection's own scratch
+  int64_t cap_n = 0, cap_m = 0, operand_bytes = 0, seg_slots = 0, g_bytes = 0, bscratch_bytes = 0;
+};
 struct Pending { hipEvent_t a, b; };
+constexpr int64_t kXentScratch = 64ll << 20;      // bytes of g per gradient launch, and of segment statistics per statistics launch
 }  // namespace
 
 struct w2b_embed {
@@ -74,6 +91,7 @@ struct w2b_embed {
   Staging user, host;
   ProjStaging puser, phost;
   BackStaging buser, bhost;
+  XentStaging xuser, xhost;
   std::vector<Pending> pending;
   double kernel_ms = 0, bytes = 0;
   int64_t launches = 0;
@@ -106,6 +124,13 @@ void free_back(BackStaging &s) {
   s = BackStaging();
 }
 
+void free_xent(XentStaging &s) {
+  void *all[] = {s.x, s.cand, s.clean, s.target, s.teff, s.stats, s.dx, s.operands, s.mseg, s.useg, s.g, s.bscratch};
+  for (void *p : all)
+    if (p) (void)hipFree(p);
+  s = XentStaging();
+}
+
 void embed_release(w2b_embed *e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
@@ -117,6 +142,8 @@ void embed_release(w2b_embed *e) {
   free_project(e->phost);
   free_back(e->buser);
   free_back(e->bhost);
+  free_xent(e->xuser);
+  free_xent(e->xhost);
   if (e->T) (void)hipFree(e->T);
   if (e->bad) (void)hipFree(e->bad);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -357,6 +384,119 @@ int launch_backproject(w2b_embed *e, BackStaging &s, int64_t n, int64_t m, bool 
     return w2b_launch_embed_backproject(e->T, e->rows, (int)e->dim, e->bitlevel, s.g, m, n, use_cand ? s.cand : nullptr, cand_base,
                                         (int)m, first, last, s.dx, use_scratch, segs, s.scratch, e->bad, e->stream);
   });
+}
+
+// the cross-entropy's caller-facing buffers for max_n vectors and max_m candidates; only ever grow, each on its own
+int ensure_xent(w2b_embed *e, XentStaging &s, int64_t max_n, int64_t max_m) {
+  if (max_n > s.cap_n || !s.x) {
+    int64_t have = 0;
+    s.cap_n = 0;                                           // (a failed allocation leaves nothing reserved)
+    if (int rc = grow(e, s.x, have, max_n * e->dim * 4, max_n)) return rc;
+    if (int rc = grow(e, s.target, have, max_n * 8, max_n)) return rc;
+    if (int rc = grow(e, s.teff, have, max_n * 8, max_n)) return rc;
+    if (int rc = grow(e, s.stats, have, max_n * 12, max_n)) return rc;
+    if (int rc = grow(e, s.dx, have, max_n * e->dim * 4, max_n)) return rc;
+    s.cap_n = max_n;
+  }
+  const int64_t need = (int64_t)w2b_embed_project_operand_bytes((int)e->dim, s.cap_n);
+  if (need > s.operand_bytes || !s.operands)
+    if (int rc = grow(e, s.operands, s.operand_bytes, need, need)) return rc;
+  if (max_m > s.cap_m || !s.cand) {
+    int64_t have = 0;
+    s.cap_m = 0;
+    if (int rc = grow(e, s.cand, have, max_m * 8, max_m)) return rc;
+    if (int rc = grow(e, s.clean, have, max_m * 8, max_m)) return rc;
+    s.cap_m = max_m;
+  }
+  return W2B_OK;
+}
+
+// the bytes of g a gradient launch may use: kXentScratch, or less by W2B_EMBED_XENT_SCRATCH (bytes, read per call; for tests
+// of the chunked path at small shapes)
+int64_t xent_scratch_bytes() {
+  int64_t b = kXentScratch;
+  if (const char *env = getenv("W2B_EMBED_XENT_SCRATCH")) {
+    const long long v = atoll(env);
+    if (v > 0 && v < b) b = v;
+  }
+  return b;
+}
+
+// The whole call on the staging s: n vectors of s.x against m candidates (those of s.cand, or every row), targets in s.target;
+// mx / se / tl into s.stats = [3][n], and dx into s.dx when want_dx.  The statistics run in ranges of vectors whose segment
+// scratch stays within kXentScratch, the gradient in ranges of whole vectors whose g fits the scratch (or, when one vector's m
+// candidates do not fit, of one vector x candidate ranges that are multiples of W2B_EMBED_WSEG, S carried by the back-projection).
+int launch_xent(w2b_embed *e, XentStaging &s, int64_t n, int64_t m, bool use_cand, bool want_dx) {
+  const int dim = (int)e->dim;
+  const int64_t nseg = (m + W2B_EMBED_XSEG - 1) / W2B_EMBED_XSEG;
+  float *mx = s.stats, *se = s.stats + n, *tl = s.stats + 2 * n;
+  const long long *clean = use_cand ? s.clean : nullptr;
+  const double cand_bytes = use_cand ? (double)m * 8 : 0.0, row_bytes = (double)m * (double)e->wpr * 8;
+  // statistics: ranges of vectors, multiples of 64 (the pairs of the operand staging)
+  int64_t sv = nseg > 0 ? kXentScratch / 12 / nseg / 64 * 64 : n;
+  sv = sv < 64 ? 64 : sv;
+  if (sv > n) sv = n;
+  if (sv * nseg > s.seg_slots || !s.mseg) {
+    const int64_t slots = sv * nseg > 0 ? sv * nseg : 1;
+    int64_t have = 0;
+    if (int rc = grow(e, s.mseg, have, slots * 4, slots)) return rc;
+    if (int rc = grow(e, s.useg, s.seg_slots, slots * 8, slots)) return rc;
+  }
+  const double bytes = (double)n * dim * 4 + row_bytes + cand_bytes + (double)n * 8 + (double)n * 12;
+  int rc = timed(e, bytes, [&] {
+    hipError_t he = w2b_launch_vec_operands(s.x, dim, (int)n, s.operands, e->stream);
+    if (he == hipSuccess && use_cand) he = w2b_launch_embed_xent_clean(s.cand, m, e->rows, s.clean, e->bad, e->stream);
+    for (int64_t v0 = 0; v0 < n && he == hipSuccess; v0 += sv) {
+      const int64_t v1 = v0 + sv < n ? v0 + sv : n;
+      he = w2b_launch_embed_xent_stats(e->T, e->rows, dim, e->bitlevel, s.operands, (int)v0, (int)v1, clean, (int)m, s.target,
+                                       s.mseg, s.useg, tl, e->stream);
+      if (he == hipSuccess)
+        he = w2b_launch_embed_xent_finish((int)v0, (int)v1, m, (int)nseg, s.mseg, s.useg, clean, s.target, mx, se, tl, s.teff,
+                                          e->bad, e->stream);
+    }
+    return he;
+  });
+  if (rc || !want_dx) return rc;
+  if (m == 0) {                                            // an empty sum: +0.0 rows, no launch
+    EHIP(hipMemsetAsync(s.dx, 0, (size_t)(n * e->dim) * 4, e->stream));
+    return W2B_OK;
+  }
+  // the gradient: whole vectors that fit the scratch, or one vector x candidate ranges
+  const int64_t room = xent_scratch_bytes() / 4;
+  int64_t gv = room / m, cm = m;
+  if (gv < 1) {
+    gv = 1;
+    cm = room / W2B_EMBED_WSEG * W2B_EMBED_WSEG;
+    if (cm < W2B_EMBED_WSEG) cm = W2B_EMBED_WSEG;
+    if (cm > m) cm = m;
+  }
+  if (gv > n) gv = n;
+  if (gv * cm * 4 > s.g_bytes || !s.g)
+    if (int rc2 = grow(e, s.g, s.g_bytes, gv * cm * 4, gv * cm * 4)) return rc2;
+  for (int64_t v0 = 0; v0 < n; v0 += gv) {
+    const int64_t nv = n - v0 < gv ? n - v0 : gv;
+    for (int64_t j0 = 0; j0 < m; j0 += cm) {
+      const int64_t cj = m - j0 < cm ? m - j0 : cm;
+      int use_scratch = 0, segs = 1;
+      long long need = 0;
+      w2b_embed_backproject_plan(dim, nv, cj, &use_scratch, &segs, &need);
+      if (need > s.bscratch_bytes)
+        if (int rc2 = grow(e, s.bscratch, s.bscratch_bytes, need, need)) return rc2;
+      const double cb = use_cand ? (double)cj * 8 : 0.0;
+      const double gbytes = 2.0 * (double)nv * dim * 4 + 2.0 * ((double)cj * (double)e->wpr * 8 + cb) + 2.0 * (double)nv * (double)cj * 4;
+      rc = timed(e, gbytes, [&] {
+        hipError_t he = w2b_launch_embed_xent_grad(e->T, e->rows, dim, e->bitlevel, s.operands, (int)v0, (int)(v0 + nv), clean, j0,
+                                                   (int)cj, mx, se, s.teff, s.g, e->stream);
+        if (he == hipSuccess)
+          he = w2b_launch_embed_backproject(e->T, e->rows, dim, e->bitlevel, s.g, cj, nv, clean ? clean + j0 : nullptr, j0, (int)cj,
+                                            j0 == 0, j0 + cj == m, s.dx + v0 * e->dim, use_scratch, segs, s.bscratch, e->bad,
+                                            e->stream);
+        return he;
+      });
+      if (rc) return rc;
+    }
+  }
+  return W2B_OK;
 }
 }  // namespace
 
@@ -601,7 +741,71 @@ extern "C" int w2b_embed_backproject(w2b_embed *e, int64_t n, const float *g, in
   return W2B_OK;
 }
 
+extern "C" int w2b_embed_xent(w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand, const int32_t *target,
+                              float *mx, float *se, float *tl, float *dx) {
+  const char *who = "w2b_embed_xent";
+  if (int rc = xent_check_args(who, n, x, m, target, mx, se, tl)) return rc;
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_xent: null handle");
+  if (int rc = project_check_cand(who, e->rows, m, cand)) return rc;
+  if (int rc = xent_check_targets(who, n, m, cand, target)) return rc;
+  if (int rc = project_check_values(who, n, e->dim, x)) return rc;
+  if (n == 0) return W2B_OK;
+  EHIP(hipSetDevice(e->device));
+  // ranges of whole vectors (they are independent); the candidate list is staged whole, 16 bytes per candidate
+  const int64_t nv = n < 4096 ? n : 4096;
+  if (int rc = ensure_xent(e, e->xhost, nv, m > 0 ? m : 1)) return rc;
+  XentStaging &s = e->xhost;
+  std::vector<long long> wide;
+  if (cand && m > 0) {
+    wide.assign(cand, cand + m);
+    EHIP(hipMemcpyAsync(s.cand, wide.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+  }
+  for (int64_t i0 = 0; i0 < n; i0 += nv) {
+    const int64_t ci = n - i0 < nv ? n - i0 : nv;
+    wide.assign(target + i0, target + i0 + ci);
+    EHIP(hipMemcpyAsync(s.x, x + i0 * e->dim, (size_t)(ci * e->dim) * 4, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipMemcpyAsync(s.target, wide.data(), (size_t)ci * 8, hipMemcpyHostToDevice, e->stream));
+    if (int rc = launch_xent(e, s, ci, m, cand != nullptr, dx != nullptr)) return rc;
+    EHIP(hipMemcpyAsync(mx + i0, s.stats, (size_t)ci * 4, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipMemcpyAsync(se + i0, s.stats + ci, (size_t)ci * 4, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipMemcpyAsync(tl + i0, s.stats + 2 * ci, (size_t)ci * 4, hipMemcpyDeviceToHost, e->stream));
+    if (dx) EHIP(hipMemcpyAsync(dx + i0 * e->dim, s.dx, (size_t)(ci * e->dim) * 4, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+  }
+  return W2B_OK;
+}
+
 // ------------------------------------------------------------------------------------ device form
+extern "C" int w2b_embed_reserve_xent(w2b_embed *e, int64_t max_n, int64_t max_m, void **x_dev, void **cand_dev,
+                                      void **target_dev, void **stats_dev, void **dx_dev) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_xent: null handle");
+  if (max_n < 0 || max_n > kProjectMaxVectors || max_m < 0 || max_m > 0x7FFFFF00ll || max_n * e->dim > (1ll << 40))
+    return efail(W2B_EINVAL, "w2b_embed_reserve_xent: bad sizes");
+  EHIP(hipSetDevice(e->device));
+  if (int rc = ensure_xent(e, e->xuser, max_n, max_m)) return rc;
+  if (x_dev) *x_dev = e->xuser.x;
+  if (cand_dev) *cand_dev = e->xuser.cand;
+  if (target_dev) *target_dev = e->xuser.target;
+  if (stats_dev) *stats_dev = e->xuser.stats;
+  if (dx_dev) *dx_dev = e->xuser.dx;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_xent_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t want_dx) {
+  if (!e) return efail(W2B_EINVAL, "w2b_embed_xent_device: null handle");
+  if (n < 0 || m < 0) return efail(W2B_EINVAL, "w2b_embed_xent_device: negative count");
+  if (use_cand != 0 && use_cand != 1) return efail(W2B_EINVAL, "w2b_embed_xent_device: use_cand must be 0 or 1");
+  if (want_dx != 0 && want_dx != 1) return efail(W2B_EINVAL, "w2b_embed_xent_device: want_dx must be 0 or 1");
+  if (n == 0) return W2B_OK;
+  XentStaging &s = e->xuser;
+  if (!s.x || !s.cand || n > s.cap_n || m > s.cap_m)
+    return efail(W2B_EINVAL, "w2b_embed_xent_device: more than w2b_embed_reserve_xent has set aside");
+  if (!use_cand && m != e->rows) return efail(W2B_EINVAL, "w2b_embed_xent_device: without candidates m must be rows");
+  EHIP(hipSetDevice(e->device));
+  return launch_xent(e, s, n, m, use_cand != 0, want_dx != 0);
+}
+
 extern "C" int w2b_embed_reserve_backproject(w2b_embed *e, int64_t max_n, int64_t max_m, void **g_dev, void **cand_dev,
                                              void **dx_dev) {
   if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_backproject: null handle");

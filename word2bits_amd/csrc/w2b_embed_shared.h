@@ -1,17 +1,104 @@
 // w2b_embed_shared.h -- what the host forms of the packed embedding's projection and back-projection (w2b_embed.cpp) and
 // their host twins (w2b_embed_twins.cpp) must refuse identically, written once: the validators of w2b_embed_project and
-// w2b_embed_backproject with their messages, in the order include/word2bits_embed.h states.  Host arithmetic only: no device header, no handle.  Every definition has
+// w2b_embed_backproject with their messages, in the order include/word2bits_embed.h states, and those of w2b_embed_xent; and the
+// arithmetic of the cross-entropy, which the kernels compile as well.  No device header, no handle.  Every definition has
 // internal linkage, so the library exports none of them.
 #pragma once
 #include "../../include/word2bits_embed.h"
 #include "../../include/word2bits_hip.h"
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
 
 int w2b_internal_fail(int code, const char *msg);   // sets w2b_last_error() (w2b_trainer.cpp)
+
+// ---- the arithmetic of the softmax cross-entropy (include/word2bits_embed.h, "Cross-entropy"), written ONCE: the host twin
+// (w2b_embed_twins.cpp) and the kernels (w2b_kernels_embedxent.hip) compile this text.  Every operation is one float32
+// operation rounded on its own: explicit fmaf, and products / differences / the quotient through W2B_XF* (on the device the
+// *_rn intrinsics, which the compiler never fuses; on the host the plain operator in a unit built with -ffp-contract=off).
+// (A kernel file defines W2B_EMBED_SHARED_DEVICE before it includes this header; every other unit sees host functions.)
+#if defined(W2B_EMBED_SHARED_DEVICE)
+#define W2B_XHD __host__ __device__ inline
+#else
+#define W2B_XHD inline
+#endif
+#if defined(W2B_EMBED_SHARED_DEVICE) && defined(__HIP_DEVICE_COMPILE__)
+#define W2B_XFMUL(a, b) __fmul_rn((a), (b))
+#define W2B_XFSUB(a, b) __fsub_rn((a), (b))
+#define W2B_XFDIV(a, b) __fdiv_rn((a), (b))
+#else
+#define W2B_XFMUL(a, b) ((a) * (b))
+#define W2B_XFSUB(a, b) ((a) - (b))
+#define W2B_XFDIV(a, b) ((a) / (b))
+#endif
+
+#define W2B_XENT_LOG2E 0x3FB8AA3Bu    /* log2(e) rounded to float32 */
+#define W2B_XENT_LN2_HI 0x3F317200u   /* 0.693145751953125: the leading 15 bits of ln 2, k * LN2_HI is exact for |k| < 2^9 */
+#define W2B_XENT_LN2_LO 0x35BFBE8Eu   /* ln 2 - LN2_HI rounded to float32 */
+#define W2B_XENT_C2 0x3F000000u       /* 1/2!  */
+#define W2B_XENT_C3 0x3E2AAAABu       /* 1/3!  */
+#define W2B_XENT_C4 0x3D2AAAABu       /* 1/4!  */
+#define W2B_XENT_C5 0x3C088889u       /* 1/5!  */
+#define W2B_XENT_C6 0x3AB60B61u       /* 1/6!  */
+#define W2B_XENT_C7 0x39500D01u       /* 1/7!  */
+
+namespace {
+W2B_XHD float w2b_xent_bits(uint32_t b) {
+  return __builtin_bit_cast(float, b);
+}
+
+// expneg(r) for r <= 0: +0.0 exactly unless r >= -64 (so for NaN too), else exp(r) by the steps of the header; every result
+// is then p * 2^k with 0.70 < p < 1.42 and -92 <= k <= 0: a normal number >= 2^-93, and expneg(0) == 1.
+W2B_XHD float w2b_expneg(float r) {
+  if (!(r >= -64.0f)) return 0.0f;
+  const float k = rintf(W2B_XFMUL(r, w2b_xent_bits(W2B_XENT_LOG2E)));                // to nearest, ties to even
+  float f = fmaf(k, -w2b_xent_bits(W2B_XENT_LN2_HI), r);
+  f = fmaf(k, -w2b_xent_bits(W2B_XENT_LN2_LO), f);
+  float p = w2b_xent_bits(W2B_XENT_C7);
+  p = fmaf(p, f, w2b_xent_bits(W2B_XENT_C6));
+  p = fmaf(p, f, w2b_xent_bits(W2B_XENT_C5));
+  p = fmaf(p, f, w2b_xent_bits(W2B_XENT_C4));
+  p = fmaf(p, f, w2b_xent_bits(W2B_XENT_C3));
+  p = fmaf(p, f, w2b_xent_bits(W2B_XENT_C2));
+  p = fmaf(p, f, 1.0f);
+  p = fmaf(p, f, 1.0f);
+  return W2B_XFMUL(p, w2b_xent_bits((uint32_t)((int)k + 127) << 23));                // 2^k from integer bits: exact
+}
+
+// one term of U_s: (uint64) rint(expneg(l - M) * 2^32), an integer in [0, 2^32]
+W2B_XHD uint64_t w2b_xent_term(float l, float M) {
+  const float t = W2B_XFMUL(w2b_expneg(W2B_XFSUB(l, M)), 4294967296.0f);               // exact: 0 or >= 2^-61
+  return (uint64_t)rintf(t);
+}
+
+// (float)u, u < 2^63, rounded to nearest even, from integer operations alone
+W2B_XHD float w2b_xent_u64_to_f32(uint64_t u) {
+  if (u == 0) return 0.0f;
+  const int lz = __builtin_clzll((unsigned long long)u);
+  const uint64_t nrm = u << lz;                                                      // the leading one at bit 63
+  uint32_t mant = (uint32_t)(nrm >> 40);                                             // 24 bits
+  const uint64_t rest = nrm & ((1ull << 40) - 1), half = 1ull << 39;
+  if (rest > half || (rest == half && (mant & 1u))) mant++;
+  int ex = 63 - lz;
+  if (mant == (1u << 24)) mant >>= 1, ex++;
+  return w2b_xent_bits(((uint32_t)(ex + 127) << 23) | (mant & 0x7FFFFFu));
+}
+
+// one step of se: se = fmaf((float)U * 2^-32, expneg(M - mx), se)
+W2B_XHD float w2b_xent_se_step(uint64_t U, float M, float mx, float se) {
+  const float u = W2B_XFMUL(w2b_xent_u64_to_f32(U), 2.3283064365386962890625e-10f);  // * 2^-32: exact
+  return fmaf(u, w2b_expneg(W2B_XFSUB(M, mx)), se);
+}
+
+// g of a live position of a vector that is not ignored
+W2B_XHD float w2b_xent_g(float l, float mx, float se, bool is_target) {
+  const float g = W2B_XFDIV(w2b_expneg(W2B_XFSUB(l, mx)), se);
+  return is_target ? W2B_XFSUB(g, 1.0f) : g;
+}
+}  // namespace
 
 namespace {
 constexpr int64_t kProjectMaxVectors = 1ll << 24;   // vectors of one call (their operand staging is indexed with 32 bits)
@@ -84,6 +171,35 @@ inline int backproject_check_values(const char *who, int64_t n, int64_t m, const
         return w2b_internal_fail(W2B_EINVAL, msg);
       }
     }
+  return W2B_OK;
+}
+
+// the cross-entropy (w2b_embed_xent*): its checks that need no handle and no table (dx may be NULL: no gradient)
+inline int xent_check_args(const char *who, int64_t n, const float *x, int64_t m, const int32_t *target, const float *mx,
+                           const float *se, const float *tl) {
+  const std::string w(who);
+  if (n < 0 || n > kProjectMaxVectors) return w2b_internal_fail(W2B_EINVAL, (w + ": bad vector count").c_str());
+  if (m < 0 || m > 0x7FFFFF00ll) return w2b_internal_fail(W2B_EINVAL, (w + ": bad candidate count").c_str());
+  if (n > 0 && !x) return w2b_internal_fail(W2B_EINVAL, (w + ": null vectors").c_str());
+  if (n > 0 && !target) return w2b_internal_fail(W2B_EINVAL, (w + ": null targets").c_str());
+  if (n > 0 && (!mx || !se || !tl)) return w2b_internal_fail(W2B_EINVAL, (w + ": null output").c_str());
+  return W2B_OK;
+}
+
+// the first target that is >= m or points at a padding position (a target < 0 means the vector is ignored)
+inline int xent_check_targets(const char *who, int64_t n, int64_t m, const int32_t *cand, const int32_t *target) {
+  char msg[200];
+  for (int64_t i = 0; i < n; i++) {
+    if (target[i] < 0) continue;
+    if (target[i] >= m) {
+      snprintf(msg, sizeof msg, "%s: vector %lld: target %d is not below m = %lld", who, (long long)i, (int)target[i], (long long)m);
+      return w2b_internal_fail(W2B_EINVAL, msg);
+    }
+    if (cand && cand[target[i]] < 0) {
+      snprintf(msg, sizeof msg, "%s: vector %lld: target %d is a padding position", who, (long long)i, (int)target[i]);
+      return w2b_internal_fail(W2B_EINVAL, msg);
+    }
+  }
   return W2B_OK;
 }
 }  // namespace

@@ -307,6 +307,22 @@ hipError_t w2b_launch_embed_backproject(const uint64_t *T, long long rows, int d
                                         long long ldg, long long n, const long long *cand, long long cand_base, int m,
                                         int first, int last, float *dx, int use_scratch, int segs, void *part,
                                         unsigned long long *bad, hipStream_t s);
+// the cross-entropy (w2b_kernels_embedxent.hip; include/word2bits_embed.h, "Cross-entropy").  X = the operand staging of ALL the
+// call's vectors (w2b_launch_vec_operands); a launch takes the vectors v0 .. v1 of it.  clean = the call's candidates with ids
+// >= rows made padding by w2b_launch_embed_xent_clean (nullptr: every row, m == rows); target = int64 [n].  Statistics: Mseg /
+// Useg = [ceil(m / W2B_EMBED_XSEG)][v1 - v0], tl = [n].  Finishing: mx / se / tl / teff = [n], teff the effective target (-1 =
+// ignored).  Gradient: the candidate positions jbase .. jbase + m of the call, g = dense [v1 - v0][m].
+hipError_t w2b_launch_embed_xent_clean(const long long *cand, long long m, long long rows, long long *clean,
+                                       unsigned long long *bad, hipStream_t s);
+hipError_t w2b_launch_embed_xent_stats(const uint64_t *T, long long rows, int dim, int bitlevel, const void *X, int v0, int v1,
+                                       const long long *clean, int m, const long long *target, float *Mseg,
+                                       unsigned long long *Useg, float *tl, hipStream_t s);
+hipError_t w2b_launch_embed_xent_finish(int v0, int v1, long long m, int nseg, const float *Mseg, const unsigned long long *Useg,
+                                        const long long *clean, const long long *target, float *mx, float *se, float *tl,
+                                        long long *teff, unsigned long long *bad, hipStream_t s);
+hipError_t w2b_launch_embed_xent_grad(const uint64_t *T, long long rows, int dim, int bitlevel, const void *X, int v0, int v1,
+                                      const long long *clean, long long jbase, int m, const float *mx, const float *se,
+                                      const long long *teff, float *g, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

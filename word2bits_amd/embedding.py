@@ -10,9 +10,11 @@
     scores = emb.torch_project(hidden, candidates=cand, dtype=torch.bfloat16)    # [..., m]: a candidate list only
     loss(emb.torch_project(hidden.requires_grad_())).backward() # hidden.grad comes from the packed rows too (no float table)
     mean = emb.torch_backproject(probs)                         # [..., dim]: the expected embedding probs @ E
+    loss = emb.torch_xent(hidden.requires_grad_(), y, reduction="mean")   # softmax cross-entropy of the tied output layer:
+    loss.backward()                                             # no [n, rows] logits, probabilities or gradient are ever held
 
-Lookup, pooling, the projection and its back-projection run on the MI355X (w2b_kernels_embed.hip,
-w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip); there is no CPU path in this module.
+Lookup, pooling, the projection, its back-projection and the cross-entropy run on the MI355X (w2b_kernels_embed.hip,
+w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip, w2b_kernels_embedxent.hip); there is no CPU path in this module.
 """
 import ctypes as C
 
@@ -62,6 +64,35 @@ def _project_function():
 
         _PROJECT_FUNCTION = PackedProject
     return _PROJECT_FUNCTION
+
+
+_XENT_FUNCTION = None
+REDUCTIONS = ("none", "mean", "sum")
+
+
+def _xent_function():
+    """The autograd hook of PackedEmbedding.torch_xent, defined on first use as PackedProject is."""
+    global _XENT_FUNCTION
+    if _XENT_FUNCTION is None:
+        import torch
+
+        class PackedXent(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, emb, target, candidates):
+                loss, dx = emb._torch_xent(x.detach(), target, candidates, True)
+                ctx.save_for_backward(dx)
+                ctx.x_shape, ctx.x_dtype, ctx.x_device = x.shape, x.dtype, x.device
+                return loss
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, grad_out):
+                dx, = ctx.saved_tensors
+                g = dx * grad_out.to(device=dx.device, dtype=torch.float32).reshape(-1, 1)
+                return g.reshape(ctx.x_shape).to(device=ctx.x_device, dtype=ctx.x_dtype), None, None, None
+
+        _XENT_FUNCTION = PackedXent
+    return _XENT_FUNCTION
 
 
 class PackedEmbedding:
@@ -181,6 +212,36 @@ class PackedEmbedding:
                                                  out.ctypes.data_as(_lib.f32p)))
         return out
 
+    def xent(self, x, target, candidates=None, grad=False):
+        """Softmax cross-entropy of the vectors `x` (float array [..., dim], cast to float32) against the rows `candidates`
+        (int array [m]; < 0 = padding) or every row: the loss as float64 x.shape[:-1], or (loss, dx) with dx float32
+        x.shape when grad=True.  `target` (int array x.shape[:-1]) holds candidate POSITIONS (rows, without candidates);
+        < 0 = ignored, whose loss is 0 and whose dx is +0.  The cross-entropy of the header: mx, se and tl are defined bit
+        for bit, and the loss is (mx - tl) + log(se) in float64."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim < 1 or x.shape[-1] != self.dim:
+            raise ValueError("x must be [..., %d]" % self.dim)
+        target = np.ascontiguousarray(target, np.int32)
+        if target.shape != x.shape[:-1]:
+            raise ValueError("target must have the shape of x without its last axis")
+        n = target.size
+        if candidates is None:
+            m, cand_p = self.rows, None
+        else:
+            cand = np.ascontiguousarray(candidates, np.int32).ravel()
+            m, cand_p = cand.size, cand.ctypes.data_as(_lib.i32p)
+        stats = np.empty((3, max(n, 1)), np.float32)
+        dx = np.empty(x.shape, np.float32) if grad else None
+        _lib.check(self._L.w2b_embed_xent(self._h, n, x.ctypes.data_as(_lib.f32p), m, cand_p, target.ctypes.data_as(_lib.i32p),
+                                          stats[0].ctypes.data_as(_lib.f32p), stats[1].ctypes.data_as(_lib.f32p),
+                                          stats[2].ctypes.data_as(_lib.f32p), None if dx is None else dx.ctypes.data_as(_lib.f32p)))
+        mx, se, tl = stats[:, :n].astype(np.float64)
+        live = target.ravel() >= 0
+        loss = np.zeros(n, np.float64)
+        loss[live] = (mx[live] - tl[live]) + np.log(se[live])
+        loss = loss.reshape(target.shape)
+        return (loss, dx) if grad else loss
+
     # ---- device form: library-owned staging, viewed by torch
     def reserve(self, max_ids, max_bags=0, dtype="float32"):
         """(ids_dev, offsets_dev, out_dev) addresses of the library's staging buffers (w2b_embed_reserve)."""
@@ -224,6 +285,16 @@ class PackedEmbedding:
 
     def backproject_device(self, n, m, use_candidates=True):
         _lib.check(self._L.w2b_embed_backproject_device(self._h, int(n), int(m), 1 if use_candidates else 0))
+
+    def reserve_xent(self, max_n, max_m):
+        """(x_dev, cand_dev, target_dev, stats_dev, dx_dev) addresses of the cross-entropy's staging buffers
+        (w2b_embed_reserve_xent): buffers of their own, each of which moves only when it grows itself."""
+        p = [C.c_void_p() for _ in range(5)]
+        _lib.check(self._L.w2b_embed_reserve_xent(self._h, int(max_n), int(max_m), *map(C.byref, p)))
+        return tuple(x.value for x in p)
+
+    def xent_device(self, n, m, use_candidates=True, want_dx=False):
+        _lib.check(self._L.w2b_embed_xent_device(self._h, int(n), int(m), 1 if use_candidates else 0, 1 if want_dx else 0))
 
     def synchronize(self):
         _lib.check(self._L.w2b_embed_synchronize(self._h))
@@ -283,6 +354,16 @@ class PackedEmbedding:
         return (self._view(g_p, max(max_n * max_m, 1), "<f4")[:max_n * max_m],
                 self._view(cand_p, max(max_m, 1), "<i8")[:max_m],
                 self._view(dx_p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim))
+
+    def staging_xent(self, max_n, max_m):
+        """torch views of the cross-entropy's staging buffers: x float32 [max_n, dim], candidates int64 [max_m], target
+        int64 [max_n], stats float32 flat [3 * max_n] (a call of n vectors leaves stats[:3 * n].view(3, n): mx, se, tl), dx
+        float32 [max_n, dim]; each valid until a later call makes that buffer grow."""
+        max_n, max_m = int(max_n), int(max_m)
+        x_p, cand_p, tgt_p, stats_p, dx_p = self.reserve_xent(max_n, max_m)
+        rows = lambda p: self._view(p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim)
+        return (rows(x_p), self._view(cand_p, max(max_m, 1), "<i8")[:max_m], self._view(tgt_p, max(max_n, 1), "<i8")[:max_n],
+                self._view(stats_p, max(3 * max_n, 1), "<f4")[:3 * max_n], rows(dx_p))
 
     def _finish(self, out, copy, what):
         self.synchronize()
@@ -372,6 +453,51 @@ class PackedEmbedding:
             torch.cuda.synchronize()                              # the library's stream does not wait for torch's
             self.backproject_device(n, m, candidates is not None or m == 0)
         return self._finish(dx[:n].view(tuple(g.shape[:-1]) + (self.dim,)), copy, "torch_backproject")
+
+    def _torch_xent(self, x, target, candidates, want_dx):
+        """(loss float32 [n] = (mx - tl) + log(se), 0 for an ignored vector; dx float32 [n, dim] or None), copies"""
+        import torch
+        n = x.numel() // self.dim
+        m = self.rows if candidates is None else candidates.numel()
+        x_t, cand_t, tgt_t, stats, dx = self.staging_xent(n, m)
+        if n:
+            x_t.copy_(x.reshape(n, self.dim))                     # copy_ casts to float32
+            tgt_t.copy_(target.reshape(-1))
+            if candidates is not None and m:
+                cand_t.copy_(candidates.reshape(-1))
+            torch.cuda.synchronize()                              # the library's stream does not wait for torch's
+            self.xent_device(n, m, candidates is not None or m == 0, want_dx)
+        mx, se, tl = self._finish(stats[:3 * n].view(3, n), True, "torch_xent")
+        live = tgt_t >= 0
+        loss = torch.where(live, (mx - tl) + torch.log(torch.where(live, se, torch.ones_like(se))), torch.zeros_like(se))
+        return loss, (dx[:n].clone() if want_dx else None)
+
+    def torch_xent(self, x, target, candidates=None, reduction="none"):
+        """Softmax cross-entropy of `x` (torch tensor [..., dim] on any device, cast to float32) against `candidates`
+        (integer tensor [m] on any device; < 0 = padding) or every row, with `target` (integer tensor x.shape[:-1]) the
+        candidate POSITION of every vector (the row, without candidates; < 0 = ignored): float32 on this handle's device,
+        x.shape[:-1] for reduction "none", a scalar for "sum" and for "mean", which divides by the number of vectors that
+        are not ignored, as torch does.  A candidate >= rows, a target >= m or one on a padding position raises.
+        Differentiable with respect to x, once: when x requires a gradient (and grad mode is on) the call also computes dx
+        on the device -- without a [n, m] array -- and backward returns dx times the incoming gradient, with x's shape,
+        dtype and device.  The table gets no gradient."""
+        import torch
+        if reduction not in REDUCTIONS:
+            raise ValueError("reduction must be 'none', 'mean' or 'sum'")
+        if x.dim() < 1 or x.shape[-1] != self.dim:
+            raise ValueError("x must be [..., %d]" % self.dim)
+        if tuple(target.shape) != tuple(x.shape[:-1]):
+            raise ValueError("target must have the shape of x without its last axis")
+        if x.requires_grad and torch.is_grad_enabled():
+            loss = _xent_function().apply(x, self, target, candidates)
+        else:
+            loss = self._torch_xent(x, target, candidates, False)[0]
+        if reduction == "none":
+            return loss.reshape(tuple(target.shape))
+        if reduction == "sum":
+            return loss.sum()
+        count = (target >= 0).sum().to(device=loss.device, dtype=torch.float32)
+        return loss.sum() / count
 
     def timing(self):
         """(kernel ms, launches, bytes moved: packed words (and weights) read + output written) since the last call."""
