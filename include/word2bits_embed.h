@@ -9,7 +9,7 @@
  * or for their sum / mean per sentence ("bag").  The rows stay packed on the device, [rows][w2b_packed_words_per_row(dim,
  * bitlevel)] 64-bit words, 1/32 (1/16) of the float table; no float table is ever built, on either side.  The kernels are in
  * word2bits_amd/csrc/w2b_kernels_embed.hip, w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip and w2b_kernels_embedxent.hip, the host side in
- * w2b_embed.cpp.
+ * w2b_embed.cpp (the handle, staging and launches), w2b_embed_shared.h (what is refused) and w2b_embed_twins.cpp (the *_host twins).
  *
  * No CPU fallback: W2B_ENOGPU when no device is visible (the *_host functions below are the tests' twins of the kernels,
  * as w2b_bits_scores_host is for the bits kernels).  Error codes and w2b_last_error() are those of word2bits_hip.h.
@@ -306,7 +306,8 @@ int w2b_embed_reserve_xent(w2b_embed *e, int64_t max_n, int64_t max_m, void **x_
                            void **dx_dev /* float[max_n][dim] */);
 int w2b_embed_xent_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t want_dx);
 
-/* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form. */
+/* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form.  All of them are in
+ * w2b_embed_twins.cpp, a host-only unit that the host sanitizers run on its own. */
 int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                           int64_t n, const int32_t *ids, float *out);
 int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n_ids,
@@ -315,7 +316,7 @@ int w2b_embed_bag_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_
 int w2b_embed_bag_weighted_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
                                 int64_t n_ids, const int32_t *ids, const float *weights,
                                 int64_t n_bags, const int64_t *offsets, int32_t mode, float *out);
-/* the projection: explicit fmaf per column, then the one multiply (w2b_embed_twins.cpp, a host-only unit) */
+/* the projection: explicit fmaf per column, then the one multiply */
 int w2b_embed_project_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n,
                            const float *x, int64_t m, const int32_t *cand, float *out);
 /* the back-projection: explicit fmaf per candidate position, the segments and the steps exactly as stated above */

@@ -4,6 +4,7 @@ for bit), the validation of the host form, and what w2b_embed_load reports befor
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -187,3 +188,16 @@ def test_load_reports_file_errors_before_it_asks_for_a_device(tmp_path):
     with pytest.raises(w2b.W2bError) as e:
         w2b.PackedEmbedding(path)
     assert e.value.code == _lib.W2B_EINVAL
+
+
+def test_the_twins_run_clean_under_the_host_sanitizers():
+    """tests/host/embed_bag_twin_main.cpp with w2b_embed_twins.cpp, built with -fsanitize=address,undefined as a program of
+    its own (the Makefile's host-check target for it) and run once: no library, no Python, no GPU under the sanitizer"""
+    csrc = os.path.join(ROOT, "word2bits_amd", "csrc")
+    r = subprocess.run(["make", "-C", csrc, "build/embed_bag_twin_check"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([os.path.join(csrc, "build", "embed_bag_twin_check")], capture_output=True, text=True,
+                       stdin=subprocess.DEVNULL)
+    assert r.returncode == 0 and r.stderr == "", r.stdout + r.stderr
+    for name in ("w2b_embed_lookup_host", "w2b_embed_bag_host", "w2b_embed_bag_weighted_host"):
+        assert re.search(r"^%s: \d+ calls ok, \d+ refused$" % name, r.stdout, flags=re.M), r.stdout + r.stderr

@@ -1,8 +1,8 @@
-// w2b_embed_shared.h -- what the host forms of the packed embedding's projection and back-projection (w2b_embed.cpp) and
-// their host twins (w2b_embed_twins.cpp) must refuse identically, written once: the validators of w2b_embed_project and
-// w2b_embed_backproject with their messages, in the order include/word2bits_embed.h states, and those of w2b_embed_xent; and the
-// arithmetic of the cross-entropy, which the kernels compile as well.  No device header, no handle.  Every definition has
-// internal linkage, so the library exports none of them.
+// w2b_embed_shared.h -- what the entry points of the packed embedding (w2b_embed.cpp) and their host twins
+// (w2b_embed_twins.cpp) must refuse identically, written once: every validator that needs no handle -- the table's shape, ids,
+// bags, weights, dtype, mode and flags, and the checks of w2b_embed_project, w2b_embed_backproject and w2b_embed_xent -- with
+// its message, in the order include/word2bits_embed.h states; and the arithmetic of the cross-entropy, which the kernels
+// compile as well.  No device header, no handle.  Every definition has internal linkage, so the library exports none of them.
 #pragma once
 #include "../../include/word2bits_embed.h"
 #include "../../include/word2bits_hip.h"
@@ -103,14 +103,96 @@ W2B_XHD float w2b_xent_g(float l, float mx, float se, bool is_target) {
 namespace {
 constexpr int64_t kProjectMaxVectors = 1ll << 24;   // vectors of one call (their operand staging is indexed with 32 bits)
 
+// "<who>: <what>" becomes w2b_last_error()
+inline int refuse(int code, const char *who, const std::string &what) {
+  return w2b_internal_fail(code, (std::string(who) + ": " + what).c_str());
+}
+
+// ---- arguments that every entry point refuses with the same words
+inline int elem_size(int32_t dtype) { return dtype == W2B_EMBED_F32 ? 4 : (dtype == W2B_EMBED_BF16 || dtype == W2B_EMBED_F16) ? 2 : 0; }
+
+inline int check_dtype(const char *who, int32_t dtype) {
+  return elem_size(dtype) ? W2B_OK : refuse(W2B_EINVAL, who, "dtype is none of W2B_EMBED_F32 / BF16 / F16");
+}
+
+inline int check_mode(const char *who, int32_t mode) {
+  if (mode != W2B_EMBED_SUM && mode != W2B_EMBED_MEAN) return refuse(W2B_EINVAL, who, "mode is neither W2B_EMBED_SUM nor W2B_EMBED_MEAN");
+  return W2B_OK;
+}
+
+// a flag of the device form (use_cand, want_dx)
+inline int check_flag(const char *who, const char *name, int32_t value) {
+  return value == 0 || value == 1 ? W2B_OK : refuse(W2B_EINVAL, who, std::string(name) + " must be 0 or 1");
+}
+
+// a float the host forms and the twins accept: finite, and 0 or within 2^-60 .. 2^60 (no subnormal and no overflow anywhere
+// downstream; the rule of w2b_eval_vectors)
+inline bool value_in_range(float v) {
+  const uint32_t a = __builtin_bit_cast(uint32_t, v) & 0x7FFFFFFFu;
+  return a == 0u || (a >= 0x21800000u && a <= 0x5D800000u);
+}
+
+// ---- the table, ids, bags and weights (lookup and bags)
+// the shape of a table: a handle needs a row (min_rows = 1), a twin takes an empty table (0)
+inline int check_shape(const char *who, int64_t rows, int64_t dim, int32_t bitlevel, int64_t min_rows) {
+  if (rows < min_rows || rows > 0x7FFFFF00ll || dim < 1 || dim > (1 << 24)) return refuse(W2B_EINVAL, who, "unsupported rows / dim");
+  if (bitlevel != 1 && bitlevel != 2) return refuse(W2B_EUNSUPPORTED, who, "bitlevel must be 1 or 2");
+  return W2B_OK;
+}
+
+// the table a twin is handed
+inline int check_table(const char *who, const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel) {
+  if (!packed) return refuse(W2B_EINVAL, who, "null table");
+  return check_shape(who, rows, dim, bitlevel, 0);
+}
+
+inline int check_ids(const char *who, int64_t rows, int64_t n, const int32_t *ids) {
+  if (n < 0) return refuse(W2B_EINVAL, who, "negative id count");
+  if (n > 0 && !ids) return refuse(W2B_EINVAL, who, "null ids");
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] >= rows) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "%s: ids[%lld] = %d is not below rows = %lld", who, (long long)i, (int)ids[i], (long long)rows);
+      return w2b_internal_fail(W2B_EINVAL, msg);
+    }
+  return W2B_OK;
+}
+
+inline int check_bags(const char *who, int64_t n_ids, int64_t n_bags, const int64_t *offsets, int32_t mode) {
+  if (n_bags < 0 || n_bags > 0x7FFFFF00ll) return refuse(W2B_EINVAL, who, "bad bag count");
+  if (int rc = check_mode(who, mode)) return rc;
+  if (!offsets) return n_bags == 0 && n_ids == 0 ? W2B_OK : refuse(W2B_EINVAL, who, "null offsets");
+  if (offsets[0] != 0) return refuse(W2B_EINVAL, who, "offsets[0] is not 0");
+  for (int64_t b = 0; b < n_bags; b++) {
+    if (offsets[b + 1] < offsets[b]) return refuse(W2B_EINVAL, who, "offsets decrease at bag " + std::to_string(b));
+    if (offsets[b + 1] - offsets[b] > W2B_EMBED_MAX_BAG)
+      return refuse(W2B_EINVAL, who, "bag " + std::to_string(b) + " is longer than W2B_EMBED_MAX_BAG");
+  }
+  if (offsets[n_bags] != n_ids) return refuse(W2B_EINVAL, who, "offsets[n_bags] is not n_ids");
+  return W2B_OK;
+}
+
+// the first weight on an id >= 0 that is not finite, or neither 0 nor within 2^-60 .. 2^60
+inline int check_weights(const char *who, int64_t n, const int32_t *ids, const float *weights) {
+  if (n > 0 && !weights) return refuse(W2B_EINVAL, who, "null weights");
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] >= 0 && !value_in_range(weights[i])) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "%s: weights[%lld] = %g is not finite, or neither 0 nor within 2^-60 .. 2^60", who, (long long)i,
+               (double)weights[i]);
+      return w2b_internal_fail(W2B_EINVAL, msg);
+    }
+  return W2B_OK;
+}
+
+// ---- the projection (w2b_embed_project*)
 // the checks that need no handle and no table: counts, dtype, NULL pointers with non-zero counts
-inline int project_check_args(const char *who, int64_t n, const float *x, int64_t m, bool dtype_ok, const void *out) {
-  const std::string w(who);
-  if (n < 0 || n > kProjectMaxVectors) return w2b_internal_fail(W2B_EINVAL, (w + ": bad vector count").c_str());
-  if (m < 0 || m > 0x7FFFFF00ll) return w2b_internal_fail(W2B_EINVAL, (w + ": bad candidate count").c_str());
-  if (!dtype_ok) return w2b_internal_fail(W2B_EINVAL, (w + ": dtype is none of W2B_EMBED_F32 / BF16 / F16").c_str());
-  if (n > 0 && !x) return w2b_internal_fail(W2B_EINVAL, (w + ": null vectors").c_str());
-  if (n > 0 && m > 0 && !out) return w2b_internal_fail(W2B_EINVAL, (w + ": null output").c_str());
+inline int project_check_args(const char *who, int64_t n, const float *x, int64_t m, int32_t dtype, const void *out) {
+  if (n < 0 || n > kProjectMaxVectors) return refuse(W2B_EINVAL, who, "bad vector count");
+  if (m < 0 || m > 0x7FFFFF00ll) return refuse(W2B_EINVAL, who, "bad candidate count");
+  if (int rc = check_dtype(who, dtype)) return rc;
+  if (n > 0 && !x) return refuse(W2B_EINVAL, who, "null vectors");
+  if (n > 0 && m > 0 && !out) return refuse(W2B_EINVAL, who, "null output");
   return W2B_OK;
 }
 
@@ -130,13 +212,10 @@ inline int project_check_cand(const char *who, int64_t rows, int64_t m, const in
   return W2B_OK;
 }
 
-// the first value that is not finite, or neither 0 nor within 2^-60 .. 2^60 (the rule of w2b_eval_vectors)
+// the first value that is not finite, or neither 0 nor within 2^-60 .. 2^60
 inline int project_check_values(const char *who, int64_t n, int64_t dim, const float *x) {
   for (int64_t i = 0; i < n * dim; i++) {
-    uint32_t bits;
-    memcpy(&bits, x + i, 4);
-    const uint32_t a = bits & 0x7FFFFFFFu;
-    if (a != 0u && (a < 0x21800000u || a > 0x5D800000u)) {
+    if (!value_in_range(x[i])) {
       char msg[200];
       snprintf(msg, sizeof msg, "%s: vector %lld, column %lld: %g is not finite, or neither 0 nor within 2^-60 .. 2^60", who,
                (long long)(i / dim), (long long)(i % dim), (double)x[i]);
@@ -146,13 +225,12 @@ inline int project_check_values(const char *who, int64_t n, int64_t dim, const f
   return W2B_OK;
 }
 
-// the back-projection (w2b_embed_backproject*): its checks that need no handle and no table
+// ---- the back-projection (w2b_embed_backproject*): its checks that need no handle and no table
 inline int backproject_check_args(const char *who, int64_t n, const float *g, int64_t m, const void *dx) {
-  const std::string w(who);
-  if (n < 0 || n > kProjectMaxVectors) return w2b_internal_fail(W2B_EINVAL, (w + ": bad vector count").c_str());
-  if (m < 0 || m > 0x7FFFFF00ll) return w2b_internal_fail(W2B_EINVAL, (w + ": bad candidate count").c_str());
-  if (n > 0 && m > 0 && !g) return w2b_internal_fail(W2B_EINVAL, (w + ": null g").c_str());
-  if (n > 0 && !dx) return w2b_internal_fail(W2B_EINVAL, (w + ": null output").c_str());
+  if (n < 0 || n > kProjectMaxVectors) return refuse(W2B_EINVAL, who, "bad vector count");
+  if (m < 0 || m > 0x7FFFFF00ll) return refuse(W2B_EINVAL, who, "bad candidate count");
+  if (n > 0 && m > 0 && !g) return refuse(W2B_EINVAL, who, "null g");
+  if (n > 0 && !dx) return refuse(W2B_EINVAL, who, "null output");
   return W2B_OK;
 }
 
@@ -161,10 +239,7 @@ inline int backproject_check_values(const char *who, int64_t n, int64_t m, const
   for (int64_t i = 0; i < n; i++)
     for (int64_t j = 0; j < m; j++) {
       if (cand && cand[j] < 0) continue;
-      uint32_t bits;
-      memcpy(&bits, g + i * m + j, 4);
-      const uint32_t a = bits & 0x7FFFFFFFu;
-      if (a != 0u && (a < 0x21800000u || a > 0x5D800000u)) {
+      if (!value_in_range(g[i * m + j])) {
         char msg[200];
         snprintf(msg, sizeof msg, "%s: vector %lld, candidate %lld: %g is not finite, or neither 0 nor within 2^-60 .. 2^60", who,
                  (long long)i, (long long)j, (double)g[i * m + j]);
@@ -174,15 +249,14 @@ inline int backproject_check_values(const char *who, int64_t n, int64_t m, const
   return W2B_OK;
 }
 
-// the cross-entropy (w2b_embed_xent*): its checks that need no handle and no table (dx may be NULL: no gradient)
+// ---- the cross-entropy (w2b_embed_xent*): its checks that need no handle and no table (dx may be NULL: no gradient)
 inline int xent_check_args(const char *who, int64_t n, const float *x, int64_t m, const int32_t *target, const float *mx,
                            const float *se, const float *tl) {
-  const std::string w(who);
-  if (n < 0 || n > kProjectMaxVectors) return w2b_internal_fail(W2B_EINVAL, (w + ": bad vector count").c_str());
-  if (m < 0 || m > 0x7FFFFF00ll) return w2b_internal_fail(W2B_EINVAL, (w + ": bad candidate count").c_str());
-  if (n > 0 && !x) return w2b_internal_fail(W2B_EINVAL, (w + ": null vectors").c_str());
-  if (n > 0 && !target) return w2b_internal_fail(W2B_EINVAL, (w + ": null targets").c_str());
-  if (n > 0 && (!mx || !se || !tl)) return w2b_internal_fail(W2B_EINVAL, (w + ": null output").c_str());
+  if (n < 0 || n > kProjectMaxVectors) return refuse(W2B_EINVAL, who, "bad vector count");
+  if (m < 0 || m > 0x7FFFFF00ll) return refuse(W2B_EINVAL, who, "bad candidate count");
+  if (n > 0 && !x) return refuse(W2B_EINVAL, who, "null vectors");
+  if (n > 0 && !target) return refuse(W2B_EINVAL, who, "null targets");
+  if (n > 0 && (!mx || !se || !tl)) return refuse(W2B_EINVAL, who, "null output");
   return W2B_OK;
 }
 
