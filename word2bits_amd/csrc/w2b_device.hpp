@@ -225,6 +225,7 @@ __device__ __forceinline__ unsigned long long lane_lt_mask(int lane) {
 // every window access also waited for the target rows in flight.)
 #define W2B_LDS __attribute__((address_space(3)))
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // LDS accesses of a thread's own 16-byte column of a row kept in LDS
 __device__ __forceinline__ Col<4> lds_ld(const W2B_LDS float *p) {
   const f32x4_t t = *(const W2B_LDS f32x4_t *)p;
@@ -515,6 +516,31 @@ __device__ __forceinline__ float log_sigmoid_term(const float f, const bool cent
   return logf(sg);
 }
 
+// ------------------------------------------------------------------------------------ lean row access
+// Row accesses of the lean form of process_word (below): 16-byte columns, two fixed buffer resources per table -- `m`, the
+// whole table (sc1: coherent), and `h`, this XCD's copies of its rows 1..nh (nt) -- and the row start in the scalar offset.
+// The bounds check of a raw buffer access looks at the per-lane offset `off` alone (the scalar offset is not part of it), so
+// a lane that must not take part passes W2B_NO_LANE: out of range for every resource below 4 GiB, all 16 bytes of the access
+// included.  Such a lane loads zeros and stores nothing, and no memory transaction is made for it.  `row` itself is always the
+// id of a real row.  Only the hot / master choice is a branch (the cache policy is part of the instruction), a wave-uniform
+// one with the master row as its fall-through.
+#define W2B_NO_LANE 0xFFFFFFF0u
+__device__ __forceinline__ Col<4> lean_ld(__amdgpu_buffer_rsrc_t m, __amdgpu_buffer_rsrc_t h, int nh, int rowb, int row, int off) {
+  u32x4 t;
+  if (__builtin_expect((unsigned)(row - 1) < (unsigned)nh, 0)) t = __builtin_amdgcn_raw_buffer_load_b128(h, off, (row - 1) * rowb, Aux<W2B_MM_XCD>::load);
+  else t = __builtin_amdgcn_raw_buffer_load_b128(m, off, row * rowb, Aux<0>::load);
+  Col<4> c;
+  c.e[0] = __uint_as_float(t.x); c.e[1] = __uint_as_float(t.y); c.e[2] = __uint_as_float(t.z); c.e[3] = __uint_as_float(t.w);
+  return c;
+}
+__device__ __forceinline__ void lean_st(__amdgpu_buffer_rsrc_t m, __amdgpu_buffer_rsrc_t h, int nh, int rowb, int row, int off,
+                                        const Col<4> &c) {
+  u32x4 t;
+  t.x = __float_as_uint(c.e[0]); t.y = __float_as_uint(c.e[1]); t.z = __float_as_uint(c.e[2]); t.w = __float_as_uint(c.e[3]);
+  if (__builtin_expect((unsigned)(row - 1) < (unsigned)nh, 0)) __builtin_amdgcn_raw_buffer_store_b128(t, h, off, (row - 1) * rowb, Aux<W2B_MM_XHOT_ST>::store);
+  else __builtin_amdgcn_raw_buffer_store_b128(t, m, off, row * rowb, Aux<0>::store);
+}
+
 // ------------------------------------------------------------------------------------ one centre word
 // Preconditions: L.ctx[0..cw), L.tgt[0..nt) and prep_lists() results published by a __syncthreads();
 // cw >= 1, nt >= 1.
@@ -544,6 +570,18 @@ __device__ __forceinline__ float log_sigmoid_term(const float f, const bool cent
 //   * QM == 1: q = +-fl(1/3) and rounding is symmetric in the sign, so avg * q = +-fl(avg * fl(1/3)) and g * q =
 //     +-fl(g * fl(1/3)): one product per element and word / per target, then a select on the same `x < 0` that quant<1>
 //     uses (-0, +0, NaN -> +), instead of a product per element and target in the dot product and in the error sum.
+//   * the exec masks around the row accesses (lean_ld / lean_st above state the bounds-check contract).  The lane predicate
+//     `active` is one per-thread offset, `lane_off`: the column's byte offset, or W2B_NO_LANE for a lane beyond the row.  The
+//     bounds check of a raw buffer access compares that per-lane offset alone with the resource's size -- the row start goes
+//     into the scalar offset, which is not checked -- so an idle lane loads zeros and stores nothing, without memory traffic,
+//     and no access needs `if (active)`.  Idle lanes run the arithmetic on those zeros; nothing of it is stored to a row, and
+//     they add 0 to the dot product (`active ? s : 0.f`, `avg` forced to 0).  The row predicates are wave-uniform.  Around a
+//     load they are a scalar compare and branch (as an offset, a slot beyond the chunk or the window still issues its load,
+//     and measured slower; for the target slots it also cost the bitlevel-0 instantiation 18 more spilled VGPRs).  The stores
+//     of phase C's stash slots take them as the offset: `lane_off` or W2B_NO_LANE (see there).  Every access, dropped or
+//     not, is made with the id of a real row: chunk_rows and the context slots clamp their list index.  What remains a branch
+//     per access is the hot / master choice, because the cache policy is part of the instruction.
+//     profiles/worker_bounds_resources.md has the counts and the launch times of every form.
 template <int QM, int VEC, bool LOSS, int MM, int ATOM = 0, int TB = -1, bool LEAN = false>
 __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &L, const QParam &qp,
                                              const int cw, const int nt, const float alpha,
@@ -569,6 +607,15 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
   };
   chunk_rows();
   const int nhu = (VEC == 4) ? X.nu : 0, nhv = (VEC == 4) ? X.nv : 0;
+  // LEAN: the lane predicate as an offset, the row length in bytes and the four buffer resources (lean_ld / lean_st)
+  [[maybe_unused]] const int rowb = dim * 4, lane_off = active ? col0 * 4 : (int)W2B_NO_LANE;
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t res_u, res_v, res_cu, res_cv;
+  if constexpr (LEAN) {
+    res_u = __builtin_amdgcn_make_buffer_rsrc((void *)P.u, 0, (int)P.tab_bytes, 0x27000);
+    res_v = __builtin_amdgcn_make_buffer_rsrc((void *)P.v, 0, (int)P.tab_bytes, 0x27000);
+    res_cu = __builtin_amdgcn_make_buffer_rsrc((void *)X.cu, 0, nhu * rowb, 0x27000);
+    res_cv = __builtin_amdgcn_make_buffer_rsrc((void *)X.cv, 0, nhv * rowb, 0x27000);
+  }
   // row accesses: a hot row at this XCD's copy (VEC == 4 only), every other row at its master address
   auto ld_u = [&](int row) -> Col<VEC> {
     if constexpr (VEC == 4) { if ((unsigned)(row - 1) < (unsigned)nhu) return xhot_ld(X.cu, row - 1, nhu, dim, col0); }
@@ -593,7 +640,11 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
     if constexpr (ATOM_V) { if (row <= atomic_rank) { add_col<VEC, TB>(P.v, row, dim, col0, d, P.tab_bytes); return; } }
     store_col<VEC, MM, TB>(P.v, row, dim, col0, val, P.tab_bytes);
   };
-  // one chunk of target rows
+  [[maybe_unused]] auto lean_ld_u = [&](int row) { return lean_ld(res_u, res_cu, nhu, rowb, row, lane_off); };
+  [[maybe_unused]] auto lean_ld_v = [&](int row) { return lean_ld(res_v, res_cv, nhv, rowb, row, lane_off); };
+  [[maybe_unused]] auto lean_st_u = [&](int row, const Col<4> &c) { lean_st(res_u, res_cu, nhu, rowb, row, lane_off, c); };
+  [[maybe_unused]] auto lean_st_v = [&](int row, const Col<4> &c) { lean_st(res_v, res_cv, nhv, rowb, row, lane_off, c); };
+  // one chunk of target rows (LEAN: `start + i < end` is wave-uniform, a scalar compare and branch; no exec mask)
   auto load_targets = [&](bool zero) {
 #pragma unroll
     for (int i = 0; i < TC; i++) {
@@ -601,7 +652,8 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
 #pragma unroll
         for (int e = 0; e < VEC; e++) x[i].e[e] = 0.f;
       }
-      if (active && start + i < end) x[i] = ld_v(rows[i]);
+      if constexpr (LEAN) { if (start + i < end) x[i] = lean_ld_v(rows[i]); }
+      else if (active && start + i < end) x[i] = ld_v(rows[i]);
     }
   };
   // issue the first chunk of target-row loads before the context phase so both gathers overlap
@@ -616,12 +668,21 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
   for (int e = 0; e < VEC; e++) avg.e[e] = 0.f;
   for (int j0 = 0; j0 < cw; j0 += W2B_CA) {
     Col<VEC> r[W2B_CA];
+    if constexpr (LEAN) {
+      // (one LDS read for the sub-chunk's row ids, clamped as in chunk_rows; idle lanes load zeros, and what they add up is
+      // neither stored to a row nor part of the average: their `avg` is forced to 0 below)
+      const int mine = L.ctx[min(j0 + lane, cw - 1)];
+#pragma unroll
+      for (int jj = 0; jj < W2B_CA; jj++)
+        if (j0 + jj < cw) r[jj] = lean_ld_u(__builtin_amdgcn_readlane(mine, jj));
+    } else {
+#pragma unroll
+      for (int jj = 0; jj < W2B_CA; jj++)
+        if (active && j0 + jj < cw) r[jj] = ld_u(__builtin_amdgcn_readfirstlane(L.ctx[j0 + jj]));
+    }
 #pragma unroll
     for (int jj = 0; jj < W2B_CA; jj++)
-      if (active && j0 + jj < cw) r[jj] = ld_u(__builtin_amdgcn_readfirstlane(L.ctx[j0 + jj]));
-#pragma unroll
-    for (int jj = 0; jj < W2B_CA; jj++)
-      if (active && j0 + jj < cw) {
+      if ((LEAN || active) && j0 + jj < cw) {
         if (j0 + jj < W2B_STASH) {
 #pragma unroll
           for (int e = 0; e < VEC; e++) L.stash[((j0 + jj) * blockDim.x + tid) * VEC + e] = r[jj].e[e];
@@ -728,7 +789,24 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
 #pragma unroll
           for (int e = 0; e < VEC; e++) dl.e[e] = 0.f;
         }
-        if (active) {
+        if constexpr (LEAN) {
+          // the same arithmetic on two-element vectors (packed fp32 instructions; as one block with the scalar code around it
+          // the element-wise form below is no longer packed by the compiler).  Idle lanes work on zeros, lane_off drops their store.
+#pragma unroll
+          for (int h = 0; h < 4; h += 2) {
+            f32x2_t xv = {x[i].e[h], x[i].e[h + 1]};
+            if (QM != 0) asm volatile("" : "+v"(xv));           // (opaque copy: see below)
+            f32x2_t ge;
+            if constexpr (THIRDS) { ge.x = (xv.x < 0.f) ? -g3 : g3; ge.y = (xv.y < 0.f) ? -g3 : g3; }
+            else { ge.x = quant<QM>(xv.x, qp); ge.y = quant<QM>(xv.y, qp); ge = g * ge; }
+            const f32x2_t ev = f32x2_t{err.e[h], err.e[h + 1]} + ge;
+            err.e[h] = ev.x; err.e[h + 1] = ev.y;
+            const f32x2_t d = g * f32x2_t{avg.e[h], avg.e[h + 1]} + 0.f;   // (-0 -> +0: what the generic form's `- ar2 * xv` does where it matters)
+            xv = xv + d;
+            x[i].e[h] = xv.x; x[i].e[h + 1] = xv.y;
+          }
+          lean_st_v(rows[i], x[i]);
+        } else if (active) {
 #pragma unroll
           for (int e = 0; e < VEC; e++) {
             float xv = x[i].e[e];
@@ -763,6 +841,54 @@ __device__ __forceinline__ void process_word(const W2bParams &P, const WordLds &
   // ---- phase C: u[ctx_j] += context_avge - 2*alpha*reg*u[ctx_j]   (ref :494-503)
   for (int j0 = 0; j0 < cw; j0 += W2B_CA) {
     Col<VEC> r[W2B_CA];
+    if constexpr (LEAN) {
+      // The sub-chunk's row ids (clamped, as in phase A) and what to do with each slot, one LDS read each and one v_readlane per
+      // use: how > 0: update the stashed value `how` times; how < 0: read the row again (rows 1..fresh_rank_u and every slot
+      // beyond the stash: see the generic form below) and update it -how times; 0: nothing (beyond the window, or a later
+      // occurrence of a row).
+      // Two passes, so that no store waits for the store before it.  With the stash read and the re-read of a slot as
+      // alternatives that fill the same registers, and every slot under a branch of its own, the compiler's wait-count pass
+      // must assume in each of those blocks that a load into its registers may be in flight: s_waitcnt vmcnt(0) before every
+      // LDS read and before every store -- the first waits for the target-row stores of phase B to drain, each later one for
+      // the store before it.  So: first the stash slots as straight-line code, every LDS read, then every update and store,
+      // with the slot's predicate as the store's offset; then, if the sub-chunk has one, the slots that are read again: the
+      // loads, one wait, the stores.
+      const int mine = L.ctx[min(j0 + lane, cw - 1)], mult = (j0 + lane < cw) ? L.umult[min(j0 + lane, cw - 1)] : 0;
+      const int how_l = (j0 + lane < W2B_STASH && mine > P.fresh_rank_u) ? mult : -mult;
+      if (j0 < W2B_STASH) {
+        static_assert(W2B_STASH % W2B_CA == 0, "a sub-chunk lies inside the stash or beyond it");
+        Col<4> rs[W2B_CA];
+#pragma unroll
+        for (int jj = 0; jj < W2B_CA; jj++) rs[jj] = lds_ld((const W2B_LDS float *)(L.stash + ((j0 + jj) * blockDim.x + tid) * VEC));
+#pragma unroll
+        for (int jj = 0; jj < W2B_CA; jj++) {
+          const int how = __builtin_amdgcn_readlane(how_l, jj);
+          for (int k = 0; k < how; k++) {          // a row that occurs m times in the window is updated m times
+#pragma unroll
+            for (int e = 0; e < VEC; e++) rs[jj].e[e] = rs[jj].e[e] + err.e[e];
+          }
+          lean_st(res_u, res_cu, nhu, rowb, __builtin_amdgcn_readlane(mine, jj), how > 0 ? lane_off : (int)W2B_NO_LANE, rs[jj]);
+        }
+      }
+      if (__ballot(lane < W2B_CA && how_l < 0) != 0ull) {
+#pragma unroll
+        for (int jj = 0; jj < W2B_CA; jj++)
+          if (__builtin_amdgcn_readlane(how_l, jj) < 0) r[jj] = lean_ld_u(__builtin_amdgcn_readlane(mine, jj));
+        __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0), here and for all of them: none of the stores below waits again
+#pragma unroll
+        for (int jj = 0; jj < W2B_CA; jj++) {
+          const int how = __builtin_amdgcn_readlane(how_l, jj);
+          if (how < 0) {
+            for (int k = 0; k < -how; k++) {
+#pragma unroll
+              for (int e = 0; e < VEC; e++) r[jj].e[e] = r[jj].e[e] + err.e[e];
+            }
+            lean_st_u(__builtin_amdgcn_readlane(mine, jj), r[jj]);
+          }
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int jj = 0; jj < W2B_CA; jj++)
       if (active && j0 + jj < cw && L.umult[j0 + jj] > 0) {
