@@ -3,12 +3,14 @@
  * bit-packed table of a 1-bit or 2-bit model (the .w2bp layout of include/word2bits_corpus.h), and the output projection
  * (logits) of a batch of float vectors against the same packed rows, with its back-projection (the gradient with respect
  * to those vectors; the expected embedding under a distribution over rows), and the softmax cross-entropy of that projection
- * with its gradient, computed without the logits ever being stored.
+ * with its gradient, computed without the logits ever being stored, and the k largest logits per vector with their
+ * positions, selected without the logits ever being stored either.
  *
  * The consumer of a packed model that is not the evaluator: a downstream model asks for the rows of a batch of token ids,
  * or for their sum / mean per sentence ("bag").  The rows stay packed on the device, [rows][w2b_packed_words_per_row(dim,
  * bitlevel)] 64-bit words, 1/32 (1/16) of the float table; no float table is ever built, on either side.  The kernels are in
- * word2bits_amd/csrc/w2b_kernels_embed.hip, w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip and w2b_kernels_embedxent.hip, the host side in
+ * word2bits_amd/csrc/w2b_kernels_embed.hip, w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip, w2b_kernels_embedxent.hip and
+ * w2b_kernels_embedtopk.hip, the host side in
  * w2b_embed.cpp (the handle, staging and launches), w2b_embed_shared.h (what is refused) and w2b_embed_twins.cpp (the *_host twins).
  *
  * No CPU fallback: W2B_ENOGPU when no device is visible (the *_host functions below are the tests' twins of the kernels,
@@ -141,13 +143,37 @@
  *   Host form: a target >= m, or one that points at a padding position, is W2B_EINVAL naming the vector.  Device form: such
  *   a target, or one on a refused candidate, makes the vector ignored and is counted once in w2b_embed_bad_ids; a candidate
  *   >= rows is dead, as padding is, and is counted once; the values of x are not checked.
+ * Top-k (w2b_embed_topk*; greedy and beam decoding, top-k sampling, re-ranking: per vector the k largest logits of the
+ *   projection and the candidate positions they stand at, without an [n][m] array on the device).  Table, bitlevel, t_r[a], q,
+ *   x, cand, padding (id < 0) and the all-rows form (cand == NULL, m == rows) are those of the projection.
+ *   Logit.  l[i][j] is the projection's float32 result (the fmaf chain in column order, then * q), bit for bit.
+ *   Live positions.  Only a LIVE position is an answer: one whose candidate is a row of the table.  A padding position never
+ *   is.  In the device form a candidate >= rows is never an answer either and is counted once in w2b_embed_bad_ids (in the
+ *   projection such a column is +0.0; here it does not exist).
+ *   Order.  Logit descending; equal logits in ascending candidate position (the evaluator's tie rule; torch.topk promises
+ *   none).  Precisely, the order of the 64-bit key  map(bits of l) << 32 | ~position,  where map is the order-preserving
+ *   integer map of float32 bits: all bits of a negative pattern flipped, the sign bit of a non-negative one set.  Negative
+ *   logits -- the common case here, unlike in the evaluator, whose keys assume a score > 0 -- therefore rank correctly.  A live
+ *   logit cannot be -0.0: the chain starts at +0 and rounds to nearest, so a sum is -0 only if every term is, and the first
+ *   step, fmaf(x, t, +0), never gives -0; nor does the product with q > 0 change a sign.  In the device form, where x is not
+ *   checked, a NaN stands where that map puts its bits (above +inf with the sign bit clear, below -inf with it set).
+ *   Output.  vals[i][0 .. k) float32 and pos[i][0 .. k), best first; pos is a candidate POSITION in [0, m) -- in the all-rows
+ *   form that is the row.  With fewer than k live positions the list ends in pos = -1, val = -inf (0xFF800000).
+ *   1 <= k <= W2B_EMBED_MAX_K, else W2B_EINVAL.
+ *   Consequences: (a) vals, pos equal the first k entries of a stable descending sort of w2b_embed_project_host's row i
+ *   restricted to the live positions, the values bit for bit; (b) k = 1 gives vals == mx of w2b_embed_xent for the same
+ *   operands (when a position is live); (c) the same row standing at several positions appears once per position, lowest
+ *   position first; (d) scaling x by 2^s, s >= 0 (staying in range), scales vals exactly and leaves pos unchanged; (e) the
+ *   result does not depend on how the call is cut into ranges of vectors, on how many vectors a launch takes, or on the
+ *   order in which workgroups run.
  *
  * ---- out of scope --------------------------------------------------------------------------------------------------
  * Gradients or training through the lookup (the table is read-only); gradients with respect to the table through the
  * projection or the cross-entropy, and second derivatives (the back-projection and the cross-entropy's gradient are
  * once-differentiable: they are not themselves recorded); class weights, label smoothing and 16-bit outputs of the
  * cross-entropy; fusing the back-projection's contraction into the gradient kernel (the next step); bitlevels
- * other than 1 and 2; a handle built from a live trainer (w2b_export_packed + w2b_embed_create does it in two calls);
+ * other than 1 and 2; gradients through the selection, top-p sampling, per-vector candidate lists and 16-bit outputs of the
+ * top-k selection; a handle built from a live trainer (w2b_export_packed + w2b_embed_create does it in two calls);
  * float input files.
  */
 #ifndef WORD2BITS_EMBED_H
@@ -166,6 +192,7 @@ typedef struct w2b_embed w2b_embed;
 #define W2B_EMBED_MAX_BAG (1 << 22)
 #define W2B_EMBED_WSEG 1024
 #define W2B_EMBED_XSEG 256
+#define W2B_EMBED_MAX_K 64
 
 /* A bit-packed .w2bp, read without expanding it; `threshold` caps the rows as in w2b_eval_load_bits (0 = off).  What is
  * wrong with the file is reported before a device is asked for: W2B_EIO "Input file not found" when it cannot be opened,
@@ -306,6 +333,38 @@ int w2b_embed_reserve_xent(w2b_embed *e, int64_t max_n, int64_t max_m, void **x_
                            void **dx_dev /* float[max_n][dim] */);
 int w2b_embed_xent_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t want_dx);
 
+/* Top-k, the semantics above.  Host form: validated before anything is launched, in the projection's order: what needs no
+ * handle (n or m negative or beyond 2^24 vectors / 0x7FFFFF00 candidates; k outside 1 .. W2B_EMBED_MAX_K; x == NULL, vals == NULL
+ * or pos == NULL with n > 0), then the handle, then the candidates (cand == NULL with m != rows; the first id >= rows), then the
+ * first refused value of x; each is W2B_EINVAL with its cause in w2b_last_error(), and the outputs are untouched.  n == 0 is
+ * W2B_OK; m == 0 writes empty lists (pos = -1, val = -inf).  vals is float[n][k], pos int32_t[n][k].  Large calls run in ranges
+ * of 4096 vectors; the candidate list is staged whole (16 bytes a candidate).
+ * Device form: w2b_embed_reserve_topk hands out x_dev = float[max_n][dim], cand_dev = int64[max_m], vals_dev =
+ * float[max_n][max_k] and pos_dev = int64[max_n][max_k] (torch's index type), buffers of their own beside those of the five
+ * other reserve calls: a pointer goes stale only when that buffer itself grows (vals_dev and pos_dev grow together with max_n x
+ * max_k; a call that asks for no more than is there returns the same pointers).  The caller fills x_dev (and cand_dev),
+ * launches, and after w2b_embed_synchronize reads vals_dev and pos_dev -- dense [n][k] for the n and k of the call.  use_cand =
+ * 0 means all rows: m must be rows.  W2B_EINVAL when n, m or n x k exceed what was reserved, or k is outside 1 ..
+ * W2B_EMBED_MAX_K.  No content of the staging makes a kernel read or write outside its buffers: a candidate >= rows is dead, as
+ * padding is, and is counted once in w2b_embed_bad_ids; the values of x are NOT checked.
+ * Device memory beyond the reserved buffers: the operand staging of the vectors (about n x dim x 4), a second candidate list
+ * (8 m), and the selection scratch: per vector of a range, for every UNIT of 64 consecutive candidate positions the unit's
+ * largest key (8 bytes), and a list of 64 k keys of 8 bytes -- the k-th largest of the unit maxima is a threshold that at most
+ * k units reach, and only keys at or above it are ever listed --, ceil(m / 64) x 8 + 512 k + 16 bytes a vector.  A range is as
+ * many vectors, a multiple of 64, as keep that within 64 MiB, or 64 vectors -- one pair of 32-vector tiles -- if those need
+ * more; a call of more vectors runs range after range.  No [n][m] array exists.  The environment variable
+ * W2B_EMBED_TOPK_SCRATCH (bytes, read per call) lowers the 64 MiB, so that the ranges can be exercised at a small shape; the
+ * result does not depend on it.
+ * w2b_embed_timing_read counts one launch per range of vectors (of n_c vectors).  A range runs the K loop over all m
+ * candidates TWICE (the unit maxima, then the keys at or above the threshold), so its bytes are 2 x (n_c x dim x 4 for x, m x
+ * words per row x 8 for the rows, 8 per candidate id when candidates are given), and n_c x k x 12 of results.  The traffic of
+ * the scratch (8 bytes per vector and unit written and read, the listed keys written and read) is not counted. */
+int w2b_embed_topk(w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand /* or NULL */, int32_t k,
+                   float *vals /* [n][k] */, int32_t *pos /* [n][k] */);
+int w2b_embed_reserve_topk(w2b_embed *e, int64_t max_n, int64_t max_m, int32_t max_k, void **x_dev, void **cand_dev /* int64[max_m] */,
+                           void **vals_dev /* float[max_n][max_k] */, void **pos_dev /* int64[max_n][max_k] */);
+int w2b_embed_topk_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t k);
+
 /* Host twins, pure C, no device: float32 results with the semantics above, the validation of the host form.  All of them are in
  * w2b_embed_twins.cpp, a host-only unit that the host sanitizers run on its own. */
 int w2b_embed_lookup_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel,
@@ -327,6 +386,9 @@ int w2b_embed_backproject_host(const uint64_t *packed, int64_t rows, int64_t dim
 int w2b_embed_xent_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
                         int64_t m, const int32_t *cand, const int32_t *target, float *mx, float *se, float *tl, float *dx);
 float w2b_embed_expneg_host(float r);   /* the shared definition of expneg, for the tests */
+/* the top-k selection from the definition: the projection's twin, the keys of the live positions, their k largest in order */
+int w2b_embed_topk_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
+                        int64_t m, const int32_t *cand, int32_t k, float *vals, int32_t *pos);
 
 #ifdef __cplusplus
 }

@@ -398,6 +398,13 @@ int w2b_embed_xent_device(struct w2b_embed *e, int64_t n, int64_t m, int32_t use
 int w2b_embed_xent_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
                         int64_t m, const int32_t *cand, const int32_t *target, float *mx, float *se, float *tl, float *dx);
 float w2b_embed_expneg_host(float r);
+int w2b_embed_topk(struct w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand, int32_t k, float *vals,
+                   int32_t *pos);
+int w2b_embed_reserve_topk(struct w2b_embed *e, int64_t max_n, int64_t max_m, int32_t max_k, void **x_dev, void **cand_dev,
+                           void **vals_dev, void **pos_dev);
+int w2b_embed_topk_device(struct w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t k);
+int w2b_embed_topk_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
+                        int64_t m, const int32_t *cand, int32_t k, float *vals, int32_t *pos);
 
 #ifdef __cplusplus
 }

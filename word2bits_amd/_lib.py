@@ -232,6 +232,12 @@ SIGNATURES = {
     "w2b_embed_xent_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, f32p, C.c_int64, i32p, i32p, f32p, f32p,
                                       f32p, f32p]),
     "w2b_embed_expneg_host": (C.c_float, [C.c_float]),
+    "w2b_embed_topk": (C.c_int, [vp, C.c_int64, f32p, C.c_int64, i32p, C.c_int32, f32p, i32p]),
+    "w2b_embed_reserve_topk": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(vp)]),
+    "w2b_embed_topk_device": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "w2b_embed_topk_host": (C.c_int, [u64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, f32p, C.c_int64, i32p, C.c_int32, f32p,
+                                      i32p]),
 }
 
 _lib = None

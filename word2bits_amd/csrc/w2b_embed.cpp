@@ -23,6 +23,7 @@ constexpr int64_t kHostOutBytes = 64ll << 20;     // output staging of one host-
 constexpr int64_t kHostIds = 1ll << 22;           // ids of one host-form chunk (a single bag may be this long)
 constexpr size_t kMaxPending = 256;               // event pairs kept before they are folded into the sums
 constexpr int64_t kXentScratch = 64ll << 20;      // bytes of g per gradient launch, and of segment statistics per statistics launch
+constexpr int64_t kTopkScratch = 64ll << 20;      // bytes of unit maxima and key lists per range of vectors (or one pair of vector tiles)
 
 int efail(int code, const std::string &msg) { return w2b_internal_fail(code, msg.c_str()); }
 #define EHIP(x)                                                                                   \
@@ -82,6 +83,16 @@ struct XentStaging {
   DevBuf<float> g;                           // bytes: the gradient's dense scratch, at most kXentScratch
   DevBuf<void> bscratch;                     // bytes: the back-projection's own scratch
 };
+// device staging of one form of the top-k selection: buffers of their own.  What a caller fills or reads (x, cand, vals, pos)
+// moves only when that buffer itself grows; the rest follows the call.
+struct TopkStaging {
+  DevBuf<float> x;                           // [cap][dim]
+  DevBuf<long long> cand, clean;             // [cap], one capacity: the caller's candidates; ids >= rows made padding
+  DevBuf<float> vals;                        // cap = max_n * max_k values reserved; a call's results are dense [n][k]
+  DevBuf<long long> pos;                     // shares the capacity of vals
+  DevBuf<void> operands;                     // bytes: the vectors in fragment order (for x.cap vectors)
+  DevBuf<void> umax, list, head;             // bytes, for one range of vectors: [.][units] maxima, [.][64 k] keys, [2][.] threshold and count
+};
 struct Pending { hipEvent_t a, b; };
 }  // namespace
 
@@ -99,6 +110,7 @@ struct w2b_embed {
   ProjStaging puser, phost;
   BackStaging buser, bhost;
   XentStaging xuser, xhost;
+  TopkStaging tuser, thost;
   std::vector<Pending> pending;
   double kernel_ms = 0, bytes = 0;
   int64_t launches = 0;
@@ -222,6 +234,21 @@ int ensure_xent(w2b_embed *e, XentStaging &s, int64_t max_n, int64_t max_m) {
   rc = reserve(e, s.cand, max_m, max_m * 8);
   if (!rc) rc = reserve(e, s.clean, max_m, max_m * 8);
   return all_or_none(rc, s.cand, s.clean);
+}
+
+// the top-k selection's caller-facing buffers for max_n vectors, max_m candidates and max_n * max_k results; only ever grow,
+// each on its own
+int ensure_topk(w2b_embed *e, TopkStaging &s, int64_t max_n, int64_t max_m, int64_t max_k) {
+  int rc = reserve(e, s.x, max_n, max_n * e->dim * 4);
+  if (rc) return rc;
+  const int64_t need = (int64_t)w2b_embed_project_operand_bytes((int)e->dim, s.x.cap);
+  if ((rc = reserve(e, s.operands, need, need))) return rc;
+  rc = reserve(e, s.cand, max_m, max_m * 8);
+  if (!rc) rc = reserve(e, s.clean, max_m, max_m * 8);
+  if (all_or_none(rc, s.cand, s.clean)) return rc;
+  rc = reserve(e, s.vals, max_n * max_k, max_n * max_k * 4);
+  if (!rc) rc = reserve(e, s.pos, max_n * max_k, max_n * max_k * 8);
+  return all_or_none(rc, s.vals, s.pos);
 }
 
 int fold_pending(w2b_embed *e) {
@@ -389,6 +416,53 @@ int launch_xent(w2b_embed *e, XentStaging &s, int64_t n, int64_t m, bool use_can
       });
       if (rc) return rc;
     }
+  }
+  return W2B_OK;
+}
+
+// the bytes of unit maxima and key lists a range of vectors may use: kTopkScratch, or less by W2B_EMBED_TOPK_SCRATCH (bytes,
+// read per call; for tests of the ranges of vectors at small shapes)
+int64_t topk_scratch_bytes() {
+  int64_t b = kTopkScratch;
+  if (const char *env = getenv("W2B_EMBED_TOPK_SCRATCH")) {
+    const long long v = atoll(env);
+    if (v > 0 && v < b) b = v;
+  }
+  return b;
+}
+
+// The whole call on the staging s: n vectors of s.x against m candidates (those of s.cand, or every row); the k best of every
+// vector into s.vals / s.pos = [n][k].  Ranges of vectors, multiples of 64 (the pairs of the operand staging), whose unit maxima
+// and key lists stay within the scratch -- or one pair, if that needs more: per range the four kernels of
+// w2b_kernels_embedtopk.hip, each K loop over all m candidates.
+int launch_topk(w2b_embed *e, TopkStaging &s, int64_t n, int64_t m, bool use_cand, int64_t k) {
+  const int dim = (int)e->dim;
+  const int64_t nunits = (m + W2B_TOPK_UNIT - 1) / W2B_TOPK_UNIT, per_vector = nunits * 8 + W2B_TOPK_UNIT * k * 8 + 16;
+  int64_t sv = topk_scratch_bytes() / per_vector / 64 * 64;
+  sv = sv < 64 ? 64 : sv;
+  if (sv > n) sv = n;
+  if (int rc = reserve_scratch(e, s.umax, sv * nunits * 8)) return rc;
+  if (int rc = reserve_scratch(e, s.list, sv * W2B_TOPK_UNIT * k * 8)) return rc;
+  if (int rc = reserve_scratch(e, s.head, sv * 16)) return rc;
+  const long long *clean = use_cand ? s.clean.p : nullptr;
+  unsigned long long *thr = (unsigned long long *)s.head.p;
+  unsigned int *count = (unsigned int *)(thr + sv);
+  for (int64_t v0 = 0; v0 < n; v0 += sv) {
+    const int64_t v1 = v0 + sv < n ? v0 + sv : n, nv = v1 - v0;
+    const double bytes = 2.0 * ((double)nv * dim * 4 + (double)m * (double)e->wpr * 8 + (use_cand ? (double)m * 8 : 0.0)) + (double)nv * (double)k * 12;
+    int rc = timed(e, bytes, [&] {
+      hipError_t he = hipSuccess;
+      if (v0 == 0) {                                       // once per call: the operands, the cleaned candidates
+        he = w2b_launch_vec_operands(s.x.p, dim, (int)n, s.operands.p, e->stream);
+        if (he == hipSuccess && use_cand) he = w2b_launch_embed_xent_clean(s.cand.p, m, e->rows, s.clean.p, e->bad, e->stream);
+      }
+      if (he == hipSuccess)
+        he = w2b_launch_embed_topk(e->T, e->rows, dim, e->bitlevel, s.operands.p, (int)v0, (int)v1, clean, (int)m, (int)k,
+                                   (unsigned long long *)s.umax.p, thr, count, (unsigned long long *)s.list.p, s.vals.p, s.pos.p,
+                                   e->stream);
+      return he;
+    });
+    if (rc) return rc;
   }
   return W2B_OK;
 }
@@ -654,7 +728,71 @@ extern "C" int w2b_embed_xent(w2b_embed *e, int64_t n, const float *x, int64_t m
   return W2B_OK;
 }
 
+extern "C" int w2b_embed_topk(w2b_embed *e, int64_t n, const float *x, int64_t m, const int32_t *cand, int32_t k, float *vals,
+                              int32_t *pos) {
+  const char *who = "w2b_embed_topk";
+  if (int rc = topk_check_args(who, n, x, m, k, vals, pos)) return rc;
+  if (!e) return refuse(W2B_EINVAL, who, "null handle");
+  if (int rc = project_check_cand(who, e->rows, m, cand)) return rc;
+  if (int rc = project_check_values(who, n, e->dim, x)) return rc;
+  if (n == 0) return W2B_OK;
+  EHIP(hipSetDevice(e->device));
+  // ranges of whole vectors (they are independent); the candidate list is staged whole, 16 bytes per candidate
+  const int64_t nv = n < 4096 ? n : 4096;
+  TopkStaging &s = e->thost;
+  if (int rc = ensure_topk(e, s, nv, m > 0 ? m : 1, k)) return rc;
+  std::vector<long long> wide;
+  if (cand && m > 0) {
+    wide.assign(cand, cand + m);
+    EHIP(hipMemcpyAsync(s.cand.p, wide.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+  }
+  wide.resize((size_t)(nv * k));
+  for (int64_t i0 = 0; i0 < n; i0 += nv) {
+    const int64_t ci = n - i0 < nv ? n - i0 : nv;
+    EHIP(hipMemcpyAsync(s.x.p, x + i0 * e->dim, (size_t)(ci * e->dim) * 4, hipMemcpyHostToDevice, e->stream));
+    if (int rc = launch_topk(e, s, ci, m, cand != nullptr, k)) return rc;
+    EHIP(hipMemcpyAsync(vals + i0 * k, s.vals.p, (size_t)(ci * k) * 4, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipMemcpyAsync(wide.data(), s.pos.p, (size_t)(ci * k) * 8, hipMemcpyDeviceToHost, e->stream));
+    EHIP(hipStreamSynchronize(e->stream));
+    for (int64_t c = 0; c < ci * k; c++) pos[i0 * k + c] = (int32_t)wide[(size_t)c];
+  }
+  return W2B_OK;
+}
+
 // ------------------------------------------------------------------------------------ device form
+extern "C" int w2b_embed_reserve_topk(w2b_embed *e, int64_t max_n, int64_t max_m, int32_t max_k, void **x_dev, void **cand_dev,
+                                      void **vals_dev, void **pos_dev) {
+  const char *who = "w2b_embed_reserve_topk";
+  if (!e) return refuse(W2B_EINVAL, who, "null handle");
+  if (int rc = topk_check_k(who, max_k)) return rc;
+  if (max_n < 0 || max_n > kProjectMaxVectors || max_m < 0 || max_m > 0x7FFFFF00ll || max_n * e->dim > (1ll << 40))
+    return refuse(W2B_EINVAL, who, "bad sizes");
+  EHIP(hipSetDevice(e->device));
+  TopkStaging &s = e->tuser;
+  if (int rc = ensure_topk(e, s, max_n, max_m, max_k)) return rc;
+  if (x_dev) *x_dev = s.x.p;
+  if (cand_dev) *cand_dev = s.cand.p;
+  if (vals_dev) *vals_dev = s.vals.p;
+  if (pos_dev) *pos_dev = s.pos.p;
+  return W2B_OK;
+}
+
+extern "C" int w2b_embed_topk_device(w2b_embed *e, int64_t n, int64_t m, int32_t use_cand, int32_t k) {
+  const char *who = "w2b_embed_topk_device";
+  if (!e) return refuse(W2B_EINVAL, who, "null handle");
+  if (n < 0 || m < 0) return refuse(W2B_EINVAL, who, "negative count");
+  if (int rc = check_flag(who, "use_cand", use_cand)) return rc;
+  if (int rc = topk_check_k(who, k)) return rc;
+  if (n == 0) return W2B_OK;
+  TopkStaging &s = e->tuser;
+  if (!s.x.p || !s.cand.p || !s.vals.p || n > s.x.cap || m > s.cand.cap || n * k > s.vals.cap)
+    return refuse(W2B_EINVAL, who, "more than w2b_embed_reserve_topk has set aside");
+  if (!use_cand && m != e->rows) return refuse(W2B_EINVAL, who, "without candidates m must be rows");
+  EHIP(hipSetDevice(e->device));
+  return launch_topk(e, s, n, m, use_cand != 0, k);
+}
+
 extern "C" int w2b_embed_reserve_xent(w2b_embed *e, int64_t max_n, int64_t max_m, void **x_dev, void **cand_dev,
                                       void **target_dev, void **stats_dev, void **dx_dev) {
   if (!e) return efail(W2B_EINVAL, "w2b_embed_reserve_xent: null handle");

@@ -1,8 +1,9 @@
 // w2b_embed_shared.h -- what the entry points of the packed embedding (w2b_embed.cpp) and their host twins
 // (w2b_embed_twins.cpp) must refuse identically, written once: every validator that needs no handle -- the table's shape, ids,
-// bags, weights, dtype, mode and flags, and the checks of w2b_embed_project, w2b_embed_backproject and w2b_embed_xent -- with
-// its message, in the order include/word2bits_embed.h states; and the arithmetic of the cross-entropy, which the kernels
-// compile as well.  No device header, no handle.  Every definition has internal linkage, so the library exports none of them.
+// bags, weights, dtype, mode and flags, and the checks of w2b_embed_project, w2b_embed_backproject, w2b_embed_xent and
+// w2b_embed_topk -- with its message, in the order include/word2bits_embed.h states; and the arithmetic of the cross-entropy
+// and the key order of the top-k selection, which the kernels compile as well.  No device header, no handle.  Every
+// definition has internal linkage, so the library exports none of them.
 #pragma once
 #include "../../include/word2bits_embed.h"
 #include "../../include/word2bits_hip.h"
@@ -98,6 +99,16 @@ W2B_XHD float w2b_xent_g(float l, float mx, float se, bool is_target) {
   const float g = W2B_XFDIV(w2b_expneg(W2B_XFSUB(l, mx)), se);
   return is_target ? W2B_XFSUB(g, 1.0f) : g;
 }
+
+// ---- the order of the top-k selection (include/word2bits_embed.h, "Top-k"), written ONCE for the host twin and the kernels
+// (w2b_kernels_embedtopk.hip).  The order-preserving integer map of float32 bits: all bits of a negative pattern flipped, the
+// sign bit of a non-negative one set; unsigned comparison of the images is the comparison of the floats (-0.0 just below
+// +0.0, NaNs where their bits put them).
+#define W2B_TOPK_UNIT 64              /* candidate positions whose keys one slot of the selection scratch collects */
+W2B_XHD uint32_t w2b_topk_map(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u); }
+W2B_XHD uint32_t w2b_topk_unmap(uint32_t image) { return (image & 0x80000000u) ? (image & 0x7FFFFFFFu) : ~image; }
+// the key of a live logit at candidate position j: larger = better; equal logits rank in ascending position.  Never 0.
+W2B_XHD uint64_t w2b_topk_key(uint32_t bits, uint32_t j) { return ((uint64_t)w2b_topk_map(bits) << 32) | (uint32_t)~j; }
 }  // namespace
 
 namespace {
@@ -257,6 +268,23 @@ inline int xent_check_args(const char *who, int64_t n, const float *x, int64_t m
   if (n > 0 && !x) return refuse(W2B_EINVAL, who, "null vectors");
   if (n > 0 && !target) return refuse(W2B_EINVAL, who, "null targets");
   if (n > 0 && (!mx || !se || !tl)) return refuse(W2B_EINVAL, who, "null output");
+  return W2B_OK;
+}
+
+// ---- the top-k selection (w2b_embed_topk*): its checks that need no handle and no table
+inline int topk_check_k(const char *who, int64_t k) {
+  if (k >= 1 && k <= W2B_EMBED_MAX_K) return W2B_OK;
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: k = %lld is not within 1 .. W2B_EMBED_MAX_K = %d", who, (long long)k, W2B_EMBED_MAX_K);
+  return w2b_internal_fail(W2B_EINVAL, msg);
+}
+
+inline int topk_check_args(const char *who, int64_t n, const float *x, int64_t m, int64_t k, const float *vals, const int32_t *pos) {
+  if (n < 0 || n > kProjectMaxVectors) return refuse(W2B_EINVAL, who, "bad vector count");
+  if (m < 0 || m > 0x7FFFFF00ll) return refuse(W2B_EINVAL, who, "bad candidate count");
+  if (int rc = topk_check_k(who, k)) return rc;
+  if (n > 0 && !x) return refuse(W2B_EINVAL, who, "null vectors");
+  if (n > 0 && (!vals || !pos)) return refuse(W2B_EINVAL, who, "null output");
   return W2B_OK;
 }
 

@@ -1,5 +1,5 @@
-// w2b_embed_twins.cpp -- the host twins of the packed embedding's kernels (include/word2bits_embed.h), all six: lookup, bags,
-// weighted bags, projection, back-projection and cross-entropy.  They are what every GPU test of the embedding compares the
+// w2b_embed_twins.cpp -- the host twins of the packed embedding's kernels (include/word2bits_embed.h), all seven: lookup, bags,
+// weighted bags, projection, back-projection, cross-entropy and top-k selection.  They are what every GPU test of the embedding compares the
 // kernels against.  They restate the header's definitions on the packed rows themselves: one decode of a row into its codes,
 // then the stated float32 steps in the stated order.  No handle, no stream and no device call: the unit includes no device
 // header, and a program that links nothing but this file and a w2b_internal_fail of its own can run it under a host sanitizer
@@ -7,7 +7,9 @@
 // Every product and sum here is one float32 operation: this file is built with -ffp-contract=off and each function says so again.
 #include "w2b_embed_shared.h"
 
+#include <algorithm>
 #include <cmath>
+#include <functional>
 #include <vector>
 
 namespace {
@@ -249,6 +251,39 @@ extern "C" int w2b_embed_xent_host(const uint64_t *packed, int64_t rows, int64_t
     for (int64_t j = 0; j < m; j++)
       g[(size_t)j] = target[i] >= 0 && (!cand || cand[j] >= 0) ? w2b_xent_g(l[(size_t)j], mx[i], se[i], j == target[i]) : 0.f;
     backproject_chains(packed, dim, bitlevel, 1, g.data(), m, cand, dx + i * dim);
+  }
+  return W2B_OK;
+}
+
+// The top-k selection, from the definition: per vector the logits of the projection (its twin above), the keys of the live
+// positions -- the order-preserving map of the logit's bits above the complement of the position --, and the k largest keys
+// in descending order; the list ends in pos = -1, val = -inf.
+extern "C" int w2b_embed_topk_host(const uint64_t *packed, int64_t rows, int64_t dim, int32_t bitlevel, int64_t n, const float *x,
+                                   int64_t m, const int32_t *cand, int32_t k, float *vals, int32_t *pos) {
+  const char *who = "w2b_embed_topk_host";
+  if (int rc = topk_check_args(who, n, x, m, k, vals, pos)) return rc;
+  if (int rc = check_table(who, packed, rows, dim, bitlevel)) return rc;
+  if (int rc = project_check_cand(who, rows, m, cand)) return rc;
+  if (int rc = project_check_values(who, n, dim, x)) return rc;
+  const int64_t block = 32;                                  // vectors whose logits are held at a time: a row is decoded once for them
+  std::vector<float> l((size_t)(block * m) + 1);
+  std::vector<uint64_t> keys;
+  for (int64_t i0 = 0; i0 < n; i0 += block) {
+    const int64_t ni = n - i0 < block ? n - i0 : block;
+    if (int rc = w2b_embed_project_host(packed, rows, dim, bitlevel, ni, x + i0 * dim, m, cand, l.data())) return rc;
+    for (int64_t i = i0; i < i0 + ni; i++) {
+      const float *li = l.data() + (i - i0) * m;
+      keys.clear();
+      for (int64_t j = 0; j < m; j++)
+        if (!cand || cand[j] >= 0) keys.push_back(w2b_topk_key(__builtin_bit_cast(uint32_t, li[j]), (uint32_t)j));
+      const size_t have = keys.size() < (size_t)k ? keys.size() : (size_t)k;
+      std::partial_sort(keys.begin(), keys.begin() + (std::ptrdiff_t)have, keys.end(), std::greater<uint64_t>());
+      for (size_t c = 0; c < (size_t)k; c++) {
+        const bool live = c < have;
+        vals[i * k + (int64_t)c] = __builtin_bit_cast(float, live ? w2b_topk_unmap((uint32_t)(keys[c] >> 32)) : 0xFF800000u);
+        pos[i * k + (int64_t)c] = live ? (int32_t)~(uint32_t)keys[c] : -1;
+      }
+    }
   }
   return W2B_OK;
 }

@@ -323,6 +323,13 @@ hipError_t w2b_launch_embed_xent_finish(int v0, int v1, long long m, int nseg, c
 hipError_t w2b_launch_embed_xent_grad(const uint64_t *T, long long rows, int dim, int bitlevel, const void *X, int v0, int v1,
                                       const long long *clean, long long jbase, int m, const float *mx, const float *se,
                                       const long long *teff, float *g, hipStream_t s);
+// the top-k selection (w2b_kernels_embedtopk.hip; include/word2bits_embed.h, "Top-k").  X and clean as for the cross-entropy; one
+// call takes the vectors v0 .. v1 against all m candidate positions through its four kernels.  Scratch for v1 - v0 vectors, all
+// written before it is read: umax = [.][ceil(m / 64)] keys, thr = [.] keys, count = [.], list = [.][64 k] keys.  vals / pos =
+// dense [n][k] of the call; with m == 0 it writes empty lists and touches neither umax nor list.
+hipError_t w2b_launch_embed_topk(const uint64_t *T, long long rows, int dim, int bitlevel, const void *X, int v0, int v1,
+                                 const long long *clean, int m, int k, unsigned long long *umax, unsigned long long *thr,
+                                 unsigned int *count, unsigned long long *list, float *vals, long long *pos, hipStream_t s);
 // bit-packed model files (w2b_corpus.cpp; format in include/word2bits_corpus.h)
 #include <string>
 #include <vector>

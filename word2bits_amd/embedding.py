@@ -12,9 +12,12 @@
     mean = emb.torch_backproject(probs)                         # [..., dim]: the expected embedding probs @ E
     loss = emb.torch_xent(hidden.requires_grad_(), y, reduction="mean")   # softmax cross-entropy of the tied output layer:
     loss.backward()                                             # no [n, rows] logits, probabilities or gradient are ever held
+    values, rows = emb.torch_topk(hidden, 8, log_probs=True)    # the 8 best rows per vector (beam search): no logits held either
+    token = emb.torch_sample(hidden, 40, temperature=0.8)       # top-k sampling
 
-Lookup, pooling, the projection, its back-projection and the cross-entropy run on the MI355X (w2b_kernels_embed.hip,
-w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip, w2b_kernels_embedxent.hip); there is no CPU path in this module.
+Lookup, pooling, the projection, its back-projection, the cross-entropy and the top-k selection run on the MI355X
+(w2b_kernels_embed.hip, w2b_kernels_embedproj.hip, w2b_kernels_embedback.hip, w2b_kernels_embedxent.hip,
+w2b_kernels_embedtopk.hip); there is no CPU path in this module.
 """
 import ctypes as C
 
@@ -25,6 +28,7 @@ from . import _lib
 DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
 MODES = {"sum": 0, "mean": 1}
 MAX_BAG = 1 << 22
+MAX_K = 64
 
 
 def _dtype_code(dtype):
@@ -242,6 +246,28 @@ class PackedEmbedding:
         loss = loss.reshape(target.shape)
         return (loss, dx) if grad else loss
 
+    def topk(self, x, k, candidates=None):
+        """The k largest logits of every vector of `x` (float array [..., dim], cast to float32) against the rows
+        `candidates` (int array [m]; < 0 = padding, never an answer) or against every row, and where they stand: (vals
+        float32, pos int32), both x.shape[:-1] + (k,), best first.  pos is a candidate POSITION (the row, without
+        candidates).  The top-k of the header: logit descending, equal logits in ascending position, the values the
+        projection's bit for bit; with fewer than k live positions a list ends in pos = -1, val = -inf.  1 <= k <= 64."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim < 1 or x.shape[-1] != self.dim:
+            raise ValueError("x must be [..., %d]" % self.dim)
+        n = x.size // self.dim
+        if candidates is None:
+            m, cand_p = self.rows, None
+        else:
+            cand = np.ascontiguousarray(candidates, np.int32).ravel()
+            m, cand_p = cand.size, cand.ctypes.data_as(_lib.i32p)
+        k = int(k)
+        shape = x.shape[:-1] + (max(k, 0),)
+        vals, pos = np.empty(shape, np.float32), np.empty(shape, np.int32)
+        _lib.check(self._L.w2b_embed_topk(self._h, n, x.ctypes.data_as(_lib.f32p), m, cand_p, k, vals.ctypes.data_as(_lib.f32p),
+                                          pos.ctypes.data_as(_lib.i32p)))
+        return vals, pos
+
     # ---- device form: library-owned staging, viewed by torch
     def reserve(self, max_ids, max_bags=0, dtype="float32"):
         """(ids_dev, offsets_dev, out_dev) addresses of the library's staging buffers (w2b_embed_reserve)."""
@@ -295,6 +321,16 @@ class PackedEmbedding:
 
     def xent_device(self, n, m, use_candidates=True, want_dx=False):
         _lib.check(self._L.w2b_embed_xent_device(self._h, int(n), int(m), 1 if use_candidates else 0, 1 if want_dx else 0))
+
+    def reserve_topk(self, max_n, max_m, max_k):
+        """(x_dev, cand_dev, vals_dev, pos_dev) addresses of the top-k selection's staging buffers (w2b_embed_reserve_topk):
+        buffers of their own, each of which moves only when it grows itself."""
+        p = [C.c_void_p() for _ in range(4)]
+        _lib.check(self._L.w2b_embed_reserve_topk(self._h, int(max_n), int(max_m), int(max_k), *map(C.byref, p)))
+        return tuple(x.value for x in p)
+
+    def topk_device(self, n, m, k, use_candidates=True):
+        _lib.check(self._L.w2b_embed_topk_device(self._h, int(n), int(m), 1 if use_candidates else 0, int(k)))
 
     def synchronize(self):
         _lib.check(self._L.w2b_embed_synchronize(self._h))
@@ -364,6 +400,17 @@ class PackedEmbedding:
         rows = lambda p: self._view(p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim)
         return (rows(x_p), self._view(cand_p, max(max_m, 1), "<i8")[:max_m], self._view(tgt_p, max(max_n, 1), "<i8")[:max_n],
                 self._view(stats_p, max(3 * max_n, 1), "<f4")[:3 * max_n], rows(dx_p))
+
+    def staging_topk(self, max_n, max_m, max_k):
+        """torch views of the top-k selection's staging buffers: x float32 [max_n, dim], candidates int64 [max_m], vals
+        float32 and pos int64, both flat [max_n * max_k] (a call of n vectors and k answers leaves vals[:n * k].view(n, k)
+        and pos[:n * k].view(n, k)); each valid until a later call makes that buffer grow."""
+        max_n, max_m, max_k = int(max_n), int(max_m), int(max_k)
+        x_p, cand_p, vals_p, pos_p = self.reserve_topk(max_n, max_m, max_k)
+        return (self._view(x_p, max(max_n * self.dim, 1), "<f4")[:max_n * self.dim].view(max_n, self.dim),
+                self._view(cand_p, max(max_m, 1), "<i8")[:max_m],
+                self._view(vals_p, max(max_n * max_k, 1), "<f4")[:max_n * max_k],
+                self._view(pos_p, max(max_n * max_k, 1), "<i8")[:max_n * max_k])
 
     def _finish(self, out, copy, what):
         self.synchronize()
@@ -498,6 +545,73 @@ class PackedEmbedding:
             return loss.sum()
         count = (target >= 0).sum().to(device=loss.device, dtype=torch.float32)
         return loss.sum() / count
+
+    def torch_topk(self, x, k, candidates=None, log_probs=False, copy=True):
+        """(values float32, indices int64), both x.shape[:-1] + (k,) on this handle's device, in the shape of torch.topk:
+        the k largest logits of `x` (torch tensor [..., dim] on any device, cast to float32) against `candidates` (integer
+        tensor [m] on any device; < 0 = padding, never an answer) or every row, best first, and the candidate POSITIONS
+        they stand at (the rows, without candidates).  The top-k of the header: no [n, m] logits are held, the values are
+        torch_project's bit for bit, equal logits come in ascending position, and with fewer than k live positions a
+        list ends in index -1, value -inf.  NOT differentiable: the result carries no grad_fn, whatever x requires.
+        log_probs=True turns the values into log-probabilities normalised over ALL live candidates, l - mx - log(se) in
+        float32 with torch.log, mx and se from one statistics call of the cross-entropy over the same operands with every
+        target ignored (one more pass over the table; the logarithm is outside the bit-for-bit contract, as in
+        torch_xent); entries with index -1 stay -inf.  A candidate >= rows raises; copy=False returns views of the library's buffers, valid until the next
+        call on this handle (with log_probs the values are always a new tensor)."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError("k must be within 1 .. %d" % MAX_K)
+        if x.dim() < 1 or x.shape[-1] != self.dim:
+            raise ValueError("x must be [..., %d]" % self.dim)
+        x = x.detach()
+        n = x.numel() // self.dim
+        m = self.rows if candidates is None else candidates.numel()
+        x_t, cand_t, vals, pos = self.staging_topk(n, m, k)
+        if n:
+            x_t.copy_(x.reshape(n, self.dim))                     # copy_ casts to float32
+            if candidates is not None and m:
+                cand_t.copy_(candidates.reshape(-1))
+            torch.cuda.synchronize()                              # the library's stream does not wait for torch's
+            self.topk_device(n, m, k, candidates is not None or m == 0)
+        shape = tuple(x.shape[:-1]) + (k,)
+        values = self._finish(vals[:n * k].view(shape), copy, "torch_topk")
+        indices = pos[:n * k].view(shape)
+        indices = indices.clone() if copy else indices
+        if log_probs and n:
+            # mx and se of every vector: the statistics of the cross-entropy with every target ignored
+            xs, cs, tgt, stats, _ = self.staging_xent(n, m)
+            xs.copy_(x_t[:n])
+            tgt.fill_(-1)
+            if candidates is not None and m:
+                cs.copy_(cand_t[:m])
+            torch.cuda.synchronize()
+            self.xent_device(n, m, candidates is not None or m == 0, False)
+            mx, se, _ = self._finish(stats[:3 * n].view(3, n), True, "torch_topk")
+            one = shape[:-1] + (1,)                               # (se is 0 only where nothing is live: all indices -1)
+            log_se = torch.log(torch.where(se > 0, se, torch.ones_like(se)))
+            values = torch.where(indices >= 0, (values - mx.reshape(one)) - log_se.reshape(one),
+                                 torch.full_like(values, float("-inf")))
+        return values, indices
+
+    def torch_sample(self, x, k, temperature=1.0, generator=None):
+        """Top-k sampling over every row: per vector of `x` one row, drawn from the softmax of the k largest logits divided
+        by `temperature`: int64 x.shape[:-1] on this handle's device.  Plain torch on top of torch_topk: softmax over the k values, then torch.multinomial with
+        `generator`.  k = 1 is greedy decoding.  A vector with no live candidate returns -1."""
+        import torch
+        if not temperature > 0:
+            raise ValueError("temperature must be positive")
+        values, indices = self.torch_topk(x, k)
+        shape = indices.shape[:-1]
+        values, indices = values.reshape(-1, indices.shape[-1]), indices.reshape(-1, indices.shape[-1])
+        if values.shape[0] == 0:
+            return indices[:, 0].reshape(shape)
+        dead = indices[:, 0] < 0
+        safe = torch.where(dead[:, None], torch.zeros_like(values), values)     # a row of -inf has no softmax
+        probs = torch.softmax(safe / float(temperature), dim=1)
+        pick = torch.multinomial(probs, 1, generator=generator)
+        out = torch.gather(indices, 1, pick)[:, 0]
+        return torch.where(dead, torch.full_like(out, -1), out).reshape(shape)
 
     def timing(self):
         """(kernel ms, launches, bytes moved: packed words (and weights) read + output written) since the last call."""
